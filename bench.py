@@ -1,7 +1,16 @@
 #!/usr/bin/env python
 """bench.py -- images/sec, forward + backward (+ loss + SGD step), TransCeption 224x224, B=16 per GPU.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dtype f32|bf16] [--batch 16] [--size 224] [--no-cpu]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dtype f32|bf16] [--batch 16] [--size 224] [--full [--no-cpu] [--no-side]]
+                    [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the line: the headline figure and what the timed steps themselves give
+(final loss, per-step event times, launches per step).  --full adds everything else, each taken after the timed steps: the side
+figures and roofline passes below, the CPU baseline, config.comm_plan and, for N>1 or --force-split, allreduce_exposed_ms.
+--dump-outputs DIR writes what the last timed step computed, as float32 .npy files (rank 0; under 49 MiB in all): loss.npy,
+ce.npy, dice.npy, logits.npy ([B, 9, S, S]; a captured step only; beyond 8 Mi elements a fixed, seeded sample of them) and
+parameters.npy (a fixed, seeded sample of 4 Mi entries of the fp32 parameter arena after the step's SGD update).  The inputs of a
+run depend on its arguments only, so two builds can be compared output for output.
 
 N>1: launched by the driver as `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ...
 bench.py --gpus N ...`; started WITHOUT a rendezvous environment, `--gpus N` re-executes itself through that very launcher, so a
@@ -23,6 +32,7 @@ per-step HIP-event times is reported beside it (config.median_ms_per_step).  Ran
   roofline_hbm  the memory-bound family with the largest share of the step, timed the same way, with its PMC traffic;
   cpu_baseline  the CPU oracle (a port of the reference arithmetic; the reference's Python cannot travel) timed on this box's
                 host cores on a bounded sample of the same workload (rank 0, N=1 only): median of 3 steps + the config-1 figure.
+Those figures (and the config.* rates of the side figures) come with --full only.
 """
 from __future__ import annotations
 
@@ -100,8 +110,38 @@ def _loader_fed_step(args, dev, rank, world, n_needed, make_step):
         st = steps.get(slot["index"])
         if st is None:
             st = steps[slot["index"]] = make_step(loader.slot_preprocess(slot))
+        step.last = st                                           # (--dump-outputs reads the logits of the step that ran last)
         return st()
     return step, steps, it
+
+
+DUMP_MAX_ELEMENTS = {"logits": 8 << 20, "parameters": 4 << 20}   # float32: 32 + 16 MiB at most
+
+
+def _dump_sample(name: str, t: torch.Tensor) -> torch.Tensor:
+    """t flattened to a fixed, seeded sample of DUMP_MAX_ELEMENTS[name] entries (sorted indices) when it holds more; else t."""
+    n, k = t.numel(), DUMP_MAX_ELEMENTS[name]
+    if n <= k:
+        return t
+    import numpy as np
+    idx = np.sort(np.random.default_rng(20240).choice(n, k, replace=False))
+    return t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+
+
+def dump_outputs(out_dir: str, step, loss, ce, dice, model):
+    """What the last timed step computed, as float32 .npy files in out_dir: loss / ce / dice, the logits of a captured step ([B, C, H, W]
+    as the model's forward returns them; an eager step keeps none) and the fp32 parameter arena after the update (sampled)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"loss": loss, "ce": ce, "dice": dice}
+    last = getattr(step, "last", step)
+    lg = getattr(last, "_logits", None)
+    if lg is not None:
+        B, C, H, W = last._shape
+        arrays["logits"] = _dump_sample("logits", lg.float().reshape(B, H, W, C).permute(0, 3, 1, 2).contiguous())
+    arrays["parameters"] = _dump_sample("parameters", model.flat_parameters())
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.detach().float().cpu().numpy())
 
 
 # ----------------------------------------------------------------------------------------------------------------- CPU baseline
@@ -237,8 +277,11 @@ def main():
     ap.add_argument("--dtype", default="bf16", choices=["f32", "bf16", "f16"])
     ap.add_argument("--batch", type=int, default=16)
     ap.add_argument("--size", type=int, default=224)
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-side", action="store_true", help="skip the side figures (forward-only, fp32, loader-fed, roofline passes)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also take the side figures, roofline passes, CPU baseline, comm plan and exposed all-reduce time")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed to DIR/<name>.npy (float32)")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-side", action="store_true", help="with --full: skip the side figures (forward-only, fp32, loader-fed, roofline passes)")
     ap.add_argument("--eager", action="store_true", help="launch every kernel from Python instead of replaying the captured hipGraph")
     ap.add_argument("--force-split", action="store_true", help="use the 3-graph multi-GPU step structure even on one GPU")
     ap.add_argument("--resident", action="store_true", help="time the step on ONE HBM-resident noise batch (the headline of rounds 1-4) instead of the "
@@ -247,10 +290,12 @@ def main():
                     help="feed the timed steps from transception_amd.data.DeviceLoader (synthetic Synapse npz files on local disk -> "
                          "HBM -> device augmentation/resize) instead of one HBM-resident batch; the default keeps BASELINE's definition")
     ap.add_argument("--comm-plan", type=int, default=8, metavar="N",
-                    help="attach config.comm_plan: what a data-parallel step of N GPUs would send (pieces, buckets, expected xGMI ring time) -- "
-                         "computed on this rank, nothing is sent")
+                    help="with --full: attach config.comm_plan: what a data-parallel step of N GPUs would send (pieces, buckets, expected "
+                         "xGMI ring time) -- computed on this rank, nothing is sent")
     ap.add_argument("--cpu-baseline-worker", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.cpu_baseline_worker:
         print(json.dumps(_cpu_baseline_worker(args.batch, args.size)))
         return
@@ -350,6 +395,8 @@ def main():
     sync()
     elapsed = time.perf_counter() - t0
     per_step = [marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps)]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, step, loss, ce, dice, model)
     fed_launches = None
     if feed is not None:
         feed.close()
@@ -360,7 +407,7 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
-        if not args.eager:
+        if args.full and not args.eager:
             # the same captured step without its collectives: the difference is the all-reduce time the step does not hide
             k = min(args.steps, 20)
             sync()
@@ -376,7 +423,7 @@ def main():
 
     launches = None if args.eager else (fed_launches or (step.kernel_nodes() if hasattr(step, "kernel_nodes") else None))
     extra, roofs = {}, {}
-    if rank == 0 and world == 1 and not args.no_side:
+    if rank == 0 and world == 1 and args.full and not args.no_side:
         extra, roofs = side_figures(args, dev, model, loss_fn, opt, step, x, y, build_model, engine, train_step, GraphedStep, FusedSGD, SegLoss,
                                      extra_step_seconds=(elapsed / args.steps,))
 
@@ -386,10 +433,10 @@ def main():
             "unit": "images/sec", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": args.dtype,
-            "data": ("synthetic (one HBM-resident batch of uniform-noise slices in [-1, 1] with random labels; config.loader_fed_images_per_sec "
-                     "is the same step fed from synthetic Synapse npz files)" if not args.loader else
+            "data": ("synthetic (one HBM-resident batch of uniform-noise slices in [-1, 1] with random labels; with --full, "
+                     "config.loader_fed_images_per_sec is the same step fed from synthetic Synapse npz files)" if not args.loader else
                      "synthetic Synapse npz files (512x512 smooth-blob slices) through DeviceLoader: read, H2D, augment, resize inside the timed region; "
-                     "config.resident_batch_images_per_sec is the same step on one HBM-resident batch") + (f" [{loader_note}]" if loader_note else ""),
+                     "with --full, config.resident_batch_images_per_sec is the same step on one HBM-resident batch") + (f" [{loader_note}]" if loader_note else ""),
             "config": {"workload": f"TransCeption (MSTransception) {args.size}x{args.size} B={args.batch}/GPU fwd+bwd+SGD, "
                                    + ("random-noise batch resident in HBM" if not args.loader else "synthetic Synapse npz slices via the device loader")
                                    + ", name-seeded random-init weights",
@@ -406,11 +453,11 @@ def main():
             out["config"]["collective_backend"] = backend + (" (all ranks on one GPU: drill, not a measurement)" if one_gpu_drill else "") + \
                 (" (one rank: the split step's collectives run on a 1-rank communicator -- the N=1 floor of allreduce_exposed_ms)" if rccl1 else "")
             out["config"]["allreduce_exposed_ms"] = exposed
-        if args.comm_plan > 1:
+        if args.full and args.comm_plan > 1:
             from transception_amd.train import comm_plan
             out["config"]["comm_plan"] = comm_plan(model, max(world, args.comm_plan) if world == 1 else world)
         out.update(roofs)
-        if world == 1 and not args.no_cpu:
+        if world == 1 and args.full and not args.no_cpu:
             out["cpu_baseline"] = cpu_baseline(args.batch, args.size)
         print(json.dumps(out))
     if comm:

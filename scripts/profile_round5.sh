@@ -23,14 +23,14 @@ bash scripts/pmc_stage.sh pmc_stage_r5 > gpurun_out/pmc_stage_r5.log 2>&1
 cp gpurun_out/pmc_stage_r5/ripm_iff_hbm.json $O/r5_ripm_iff_hbm.json
 python scripts/provenance.py stamp $O/r5_attn_pmc.json $O/r5_hbm_by_kernel.json $O/r5_step_timeline.json $O/r5_seg_timeline.json $O/r5_ripm_iff_hbm.json > $O/provenance.log 2>&1
 cp $O/r5_*.json profiles/ 2>/dev/null     # (on the box: so that the bench lines below see the fresh, stamped profiles)
-cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d /root/repo/$O/stats -- python /root/repo/bench.py > /root/repo/$O/bench.json 2> /root/repo/$O/bench.err
-rocprofv3 --kernel-trace --stats --output-format csv -d /root/repo/$O/stats_c5 -- python /root/repo/bench.py --size 384 --batch 8 --dtype f16 --no-cpu > /root/repo/$O/bench_c5_384_b8_f16.json 2> /root/repo/$O/bench_c5.err
-rocprofv3 --kernel-trace --stats --output-format csv -d /root/repo/$O/stats_c4 -- python /root/repo/bench.py --size 512 --batch 8 --no-cpu > /root/repo/$O/bench_c4_512_b8_bf16.json 2> /root/repo/$O/bench_c4.err
+REPO=$PWD; cd /tmp && export TMPDIR=/tmp
+rocprofv3 --kernel-trace --stats --output-format csv -d $REPO/$O/stats -- python $REPO/bench.py --full > $REPO/$O/bench.json 2> $REPO/$O/bench.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $REPO/$O/stats_c5 -- python $REPO/bench.py --full --size 384 --batch 8 --dtype f16 --no-cpu > $REPO/$O/bench_c5_384_b8_f16.json 2> $REPO/$O/bench_c5.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $REPO/$O/stats_c4 -- python $REPO/bench.py --full --size 512 --batch 8 --no-cpu > $REPO/$O/bench_c4_512_b8_bf16.json 2> $REPO/$O/bench_c4.err
 cd /root/repo
 for d in stats stats_c5 stats_c4; do cp $(find $O/$d -name "*kernel_stats.csv" | head -1) $O/${d}_kernel_stats.csv 2>/dev/null; done
 find $O -name "*kernel_trace.csv" -delete; find $O -name "*agent_info.csv" -delete
-python bench.py --gpus 1 --force-split --steps 20 --warmup 5 --no-cpu --no-side > $O/bench_split.json 2> $O/bench_split.err
+python bench.py --full --gpus 1 --force-split --steps 20 --warmup 5 --no-cpu --no-side > $O/bench_split.json 2> $O/bench_split.err
 ls -R $O | head -40
 # round-5 evidence that is not rocprofv3 output: per-phase cycles of the fused MHCA kernels (a -DTC_MHCA_TIMING library built in the container:
 # bash scripts/exp/build_variant.sh mhcatiming factoratt.hip -DTC_MHCA_TIMING), fused vs op-by-op launch times, the grid-barrier probe

@@ -78,7 +78,7 @@ def test_bench_force_split_runs_on_a_one_rank_rccl_group():
     """`python bench.py --gpus 1 --force-split`: the split step with its collectives on a 1-rank RCCL communicator; the line says so."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--force-split", "--steps", "3", "--warmup", "1",
-                        "--batch", "2", "--no-cpu", "--no-side"], capture_output=True, text=True, env=env, timeout=900)
+                        "--batch", "2", "--full", "--no-cpu", "--no-side"], capture_output=True, text=True, env=env, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert out["n_gpus"] == 1 and out["rccl_ranks"] == 1 and out["config"]["collective_backend"].startswith("nccl")
