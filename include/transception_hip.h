@@ -741,6 +741,31 @@ int tc_linear_ln_fwd(const void* x, int ldx, const void* w, const void* b, long 
                      const void* beta, long long gstride, void* t, int ldt, void* xn, int ldn, float* mean, float* rstd, int groups,
                      int rows, int C, float eps, int dtype, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Legacy Transception encoder (networks/Transception.py, MiT_3inception, :362-551).  Every pointer 16-byte aligned, every C / Cin, row
+ * stride and batch stride a multiple of 8 elements (TC_ERR_ARG otherwise); channels move in 16-byte pieces.  No atomics: the adjoints
+ * gather, so their results are the same run to run.
+ *
+ * tc_im2col_dil: patches of a k x k convolution (k in {1, 3}) with any stride / pad / dilation -- the Conv2d of each
+ * OverlapPatchEmbeddings_fuse branch (EffSegformer.py:117-131; 3x3 s2 p0 d2, 3x3 s2 p1 d1 and 1x1 s2 here).  x token-major [B*H*W, Cin]
+ * (row stride ldx) -> cols [B*Ho*Wo, ldc], tap-major: column (ky*k + kx)*Cin + c = x(b, oy*stride - pad + ky*dil, ox*stride - pad + kx*dil, c),
+ * zero outside the map; Ho = (H + 2 pad - dil (k - 1) - 1) / stride + 1.  The product with the [Cout, Cin, k, k] weight read as
+ * [Cout, k*k*Cin] is the convolution.  tc_col2im_dil: dx (+)= for each input pixel the sum of the column gradients of the taps that read it. */
+int tc_im2col_dil(const void* x, int ldx, void* cols, int ldc, int B, int Cin, int H, int W, int k, int stride, int pad, int dil, int dtype, void* stream);
+int tc_col2im_dil(const void* dcols, int ldc, void* dx, int lddx, int B, int Cin, int H, int W, int k, int stride, int pad, int dil, int accumulate,
+                  int dtype, void* stream);
+/* tc_nearest_concat_fwd: the split of the normalised two-branch sequence, F.interpolate(branch 1, [Ho, Wo]) (mode nearest:
+ * src = min((int)floorf(dst * (float)in / out), in - 1) per axis) and torch.cat((branch 1, branch 2), channels) (Transception.py:432-447,
+ * 461-476, 490-505) in one gather: y [B*Ho*Wo, ldy], columns [0, C) branch 1 resampled, [C, 2C) branch 2.  Token t of image b of branch 1
+ * ([H1*W1] tokens) lives at x1 + b*sb1 + t*ldx, of branch 2 ([Ho*Wo] tokens) at x2 + b*sb2 + t*ldx (elements): the per-image sequence
+ * [B, n1+n2, C] is x2 = x1 + n1*ldx, sb1 = sb2 = (n1+n2)*ldx; branch-major rows are x2 = x1 + B*n1*ldx, sb1 = n1*ldx, sb2 = n2*ldx.
+ * y feeds conv1_1_sK as one GEMM, or SK_Block with its two column halves as the two branch maps.
+ * tc_nearest_concat_bwd: dx1 (+)= per branch-1 token the sum of the dy rows of the pixels that picked it; dx2 (+)= dy's second half. */
+int tc_nearest_concat_fwd(const void* x1, long long sb1, const void* x2, long long sb2, int ldx, void* y, int ldy, int B, int H1, int W1, int Ho,
+                          int Wo, int C, int dtype, void* stream);
+int tc_nearest_concat_bwd(const void* dy, int ldy, void* dx1, long long sb1, void* dx2, long long sb2, int lddx, int B, int H1, int W1, int Ho,
+                          int Wo, int C, int accumulate, int dtype, void* stream);
+
 /* profiling aid: an empty launch of id + 1 workgroups that marks a section boundary in a kernel trace (no reference counterpart) */
 int tc_seg_marker(int id, void* stream);
 

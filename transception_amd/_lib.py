@@ -216,6 +216,10 @@ SIGNATURES = {
     "tc_fill_f32": [vp, i64, f32, vp],
     "tc_cast": [vp, vp, i64, i32, i32, vp],
     "tc_seg_marker": [i32, vp],
+    "tc_im2col_dil": [vp, i32, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp],
+    "tc_col2im_dil": [vp, i32, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp],
+    "tc_nearest_concat_fwd": [vp, i64, vp, i64, i32, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp],
+    "tc_nearest_concat_bwd": [vp, i32, vp, i64, vp, i64, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp],
     "tc_linear_ln_supported": [i32, i32],
     "tc_linear_ln_fwd": [vp, i32, vp, vp, i64, vp, i32, vp, vp, i64, vp, i32, vp, i32, vp, vp, i32, i32, i32, f32, i32, vp],
     "tc_ripm_supported": [i32, i32],

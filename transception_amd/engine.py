@@ -764,23 +764,27 @@ class Graph:
         self._rec(bwd)
         return [it[3] for it in items]
 
-    def linear_multi(self, x: Var, Ws: List[P], bs: List[P], out: Var) -> Var:
+    def linear_multi(self, x: Var, Ws: List[P], bs: List[P], out: Var, stacked: bool = False) -> Var:
         """n Linear layers with the same [N, K] shape on the SAME input, written side by side into out [M, n*N], as ONE batched
         GEMM (weight i lives a constant stride after weight 0 in the parameter arena) -- EfficientAttention's keys / queries /
         values (MSTr.py:109-111).  Backward: dX is one K = n*N product over the gapped weight stack (TcGemm.bgap), the n weight
-        gradients one batched GEMM; both share a launch (tc_gemm_pair)."""
+        gradients one batched GEMM; both share a launch (tc_gemm_pair).
+        stacked: out is [n*M, N] instead, layer i in rows [i*M, (i+1)*M) -- each output a dense [M, N] block (FuseEfficientAttention reads its
+        keys / queries / values flat, Transception.py:50-53); dX is then n accumulating products."""
         n = len(Ws)
         N, K = Ws[0].data.shape
         M = x.rows
         es = Ws[0].data.element_size()
         sw = (Ws[1].data.data_ptr() - Ws[0].data.data_ptr()) // es
-        assert self.ngroups == 1 and out.rows == M and out.cols == n * N and x.cols == K
+        assert self.ngroups == 1 and x.cols == K
+        assert (out.rows == n * M and out.cols == N) if stacked else (out.rows == M and out.cols == n * N)
         assert all(W.data.shape == (N, K) and W.data.is_contiguous() for W in Ws)
         assert all((Ws[i].data.data_ptr() - Ws[0].data.data_ptr()) // es == i * sw and
                    (bs[i].data.data_ptr() - bs[0].data.data_ptr()) // es == i * sw for i in range(n))
         assert N % 64 == 0 and (sw - N * K) % 8 == 0
+        so = M * out.ld if stacked else N
         self._gemm(_ptr(x.data), x.ld, _ptr(Ws[0].data), K, _ptr(out.data), out.ld, M, N, K, 0, 1, bias=_ptr(bs[0].data), nb1=n,
-                   sA=(0, 0), sB=(sw, 0), sC=(N, 0), sbias=sw)
+                   sA=(0, 0), sB=(sw, 0), sC=(so, 0), sbias=sw)
 
         def bwd():
             dy = self.grad_of(out)
@@ -788,6 +792,18 @@ class Graph:
                 return
             have_w = Ws[0].grad is not None
             gsw = (Ws[1].grad.data_ptr() - Ws[0].grad.data_ptr()) // 4 if have_w else 0
+            if stacked:
+                sdy = M * dy.stride(0)
+                if x.requires_grad:
+                    gx, acc = self.wgrad(x)
+                    for i in range(n):
+                        self._gemm(dy.data_ptr() + i * sdy * dy.element_size(), dy.stride(0), _ptr(Ws[i].data), K, _ptr(gx), gx.stride(0), M, K,
+                                   N, 0, 0, acc=int(acc or i > 0))
+                if have_w:
+                    self._gemm(_ptr(dy), dy.stride(0), _ptr(x.data), x.ld, _ptr(Ws[0].grad), K, N, K, M, 1, 0, acc=1,
+                               splitk=self._splitk(N, K, M), c_f32=1, nb1=n, sA=(sdy, 0), sB=(0, 0), sC=(gsw, 0),
+                               rowsum=_ptr(bs[0].grad) if bs[0].grad is not None else None, srow=gsw)
+                return
             ga = gb = None
             if x.requires_grad:
                 gx, acc = self.wgrad(x)
@@ -2118,6 +2134,52 @@ class Graph:
             self.L.tc_col2im3s2(_ptr(d), d.stride(0), _ptr(gx), gx.stride(0), B, Cin, H, W, acc, self.dt, self.stream)
         self._rec(bwd)
         return cols
+
+    def im2col_dil(self, x: Var, B: int, H: int, W: int, k: int, stride: int, pad: int, dil: int) -> Var:
+        """Patches of a k x k convolution (k in {1, 3}, any stride / pad / dilation) of the token-major map x [B*H*W, Cin]: [B*Ho*Wo, k*k*Cin],
+        tap-major columns (ky*k + kx)*Cin + c -- the weight goes with it as permuted_weight([Cout, Cin*k*k], Cout, Cin, k*k).  The gradient
+        comes back through tc_col2im_dil (a gather per input pixel)."""
+        Cin = x.cols
+        Ho, Wo = (H + 2 * pad - dil * (k - 1) - 1) // stride + 1, (W + 2 * pad - dil * (k - 1) - 1) // stride + 1
+        cols = self.new(B * Ho * Wo, k * k * Cin)
+        self.n_launch += 1
+        self.L.tc_im2col_dil(_ptr(x.data), x.ld, _ptr(cols.data), cols.ld, B, Cin, H, W, k, stride, pad, dil, self.dt, self.stream)
+
+        def bwd():
+            d = self.grad_of(cols)
+            if d is None or not x.requires_grad:
+                return
+            gx, acc = self.wgrad(x)
+            self.n_launch += 1
+            self.L.tc_col2im_dil(_ptr(d), d.stride(0), _ptr(gx), gx.stride(0), B, Cin, H, W, k, stride, pad, dil, acc, self.dt, self.stream)
+        self._rec(bwd)
+        return cols
+
+    def nearest_concat(self, seq: Var, B: int, H1: int, W1: int, Ho: int, Wo: int, branch_major: bool = True) -> Var:
+        """The two-branch sequence seq ([B*(n1 + n2), C]; branch_major: all images' branch-1 tokens, then all images' branch-2 tokens, else
+        per image [n1 | n2]) -> [B*Ho*Wo, 2C]: branch 1 resized to Ho x Wo by PyTorch's nearest rule, concatenated with branch 2 along the
+        channels (tc_nearest_concat_fwd); the gradient goes back through tc_nearest_concat_bwd."""
+        C, n1, n2 = seq.cols, H1 * W1, Ho * Wo
+        assert seq.rows == B * (n1 + n2) and seq.data.is_contiguous()
+        es = seq.data.element_size()
+        ld = seq.ld
+        off2, sb1, sb2 = (B * n1 * ld, n1 * ld, n2 * ld) if branch_major else (n1 * ld, (n1 + n2) * ld, (n1 + n2) * ld)
+        out = self.new(B * n2, 2 * C)
+        x1 = seq.data.data_ptr()
+        self.n_launch += 1
+        self.L.tc_nearest_concat_fwd(x1, sb1, x1 + off2 * es, sb2, ld, _ptr(out.data), out.ld, B, H1, W1, Ho, Wo, C, self.dt, self.stream)
+
+        def bwd():
+            d = self.grad_of(out)
+            if d is None or not seq.requires_grad:
+                return
+            g, acc = self.wgrad(seq)
+            g1 = g.data_ptr()
+            self.n_launch += 1
+            self.L.tc_nearest_concat_bwd(_ptr(d), d.stride(0), g1, sb1, g1 + off2 * es, sb2, g.stride(0), B, H1, W1, Ho, Wo, C, acc, self.dt,
+                                         self.stream)
+        self._rec(bwd)
+        return out
 
     def attention(self, q: Var, k: Var, v: Var, B: int, Nq: int, Nk: int, scale: float, out: Optional[Var] = None) -> Var:
         """softmax(q k^T * scale) v per batch (single head, d = q.cols)."""

@@ -405,7 +405,7 @@ class MSTransception(nn.Module):
         #   have_bridge  ... | "sp" (BridgeBlock_sp, :2728-2757: SpatialAwareTrans -- per-scale Linear to 64 channels, windows of 8 / 4 / 2 / 1 pixels,
         #                  num_sp InterTransBlocks of 8-head attention over the 85 tokens of a window + MLP_FFN with Dropout(0.1), windows back, Linear
         #                  to the scale's width -- ahead of four all-spatial bridge layers)
-        # the reference.  Not built: the legacy networks/Transception.py class.
+        # the reference.  The legacy networks/Transception.py class is transception_amd.legacy.Transception.
         br = [bool(b) for b in br_ch_att_list]
         if (token_mlp_mode not in ("mix_skip", "mix") or concat not in ("coord", "normal", "se", "3d", "skn", "cbam", "cam", "cam_fact")
                 or (Stage_3or4 == 4 and concat not in ("coord", "normal", "se", "cbam", "skn")) or len(br) != 4 or (have_bridge == "sp" and int(num_sp) < 0)):
@@ -641,7 +641,7 @@ class MSTransception(nn.Module):
             L.tc_cast(xin.data_ptr(), xl.data_ptr(), xin.numel(), TC_F32, self._tc_dtype(), stream)
             xin = xl
         self._tok_logits = token_logits
-        out_var = _forward(self, G, xin, B, in_ch, H)
+        out_var = self._graph_forward(G, xin, B, in_ch, H)
         self._tok_logits = False
         logits = out_var.data if token_logits else out_var.data.view(B, self.num_classes, H, W)
         if self.compute_dtype != torch.float32 and not token_logits:
@@ -658,6 +658,10 @@ class MSTransception(nn.Module):
                     m.num_batches_tracked += 1
         self.last_launches = G.n_launch
         return logits, G, out_var
+
+    def _graph_forward(self, G: Graph, x: torch.Tensor, B: int, in_ch: int, S: int) -> Var:
+        """The forward pass as engine calls (the class's network); _run wraps it with the casts, the BatchNorm counters and the logits' layout."""
+        return _forward(self, G, x, B, in_ch, S)
 
     def late_gradient_offset(self) -> int:
         """First element of the flat arenas that belongs to the bridge / decoders: parameters are laid out in registration
@@ -810,11 +814,11 @@ def _mixffn(M, G, x, name, B, H, W, residual, out=None, pre_ln=None):
     return G.linear(a, *_lin(M, G, name + ".fc2"), out=out, residual=residual)
 
 
-def _mixffn_plain(M, G, x, name, B, H, W, residual):
+def _mixffn_plain(M, G, x, name, B, H, W, residual, out=None):
     """MixFFN (token_mlp_mode = "mix"), MSTr.py:35-46: fc2(GELU(dw3x3(fc1(x)))) + residual -- an ablation variant, run op by op."""
     h = G.linear(x, *_lin(M, G, name + ".fc1"))
     d = G.dwconv(h, M._P(G, name + ".dwconv.dwconv.weight"), M._P(G, name + ".dwconv.dwconv.bias"), B, H, W, 3, 1, False)
-    return G.linear(G.gelu(d), *_lin(M, G, name + ".fc2"), residual=residual)
+    return G.linear(G.gelu(d), *_lin(M, G, name + ".fc2"), residual=residual, out=out)
 
 
 def _eff_attention(M, G, n1: Var, name: str, B: int, N: int, residual: Optional[Var] = None, ln=None):
@@ -1054,24 +1058,7 @@ def _mhca_stage(M, G, stack: Var, name: str, layers: int, B: int, side: int, out
         G.linear(cat, Wc, None, out=z, accumulate=True)
         return _bn(M, G, z, agg + ".conv2d_bn_act.1", ACT_RELU, out=out)
     if M.concat == "skn":                                                        # SK_Block, MSTr.py:1076-1107
-        agg = name + ".aggregate"
-        N = side * side
-        pooled = G.chan_pool(cat, B, N)                                          # [B, 4C]: S = mean(sum_k x_k) = sum_k mean(x_k)
-        Wf, bf = _lin(M, G, agg + ".fc")
-        Z = G.new(B, Wf.data.shape[0])
-        nbr = cat.cols // C                                                      # branch maps: four (three in the first stage of MSViT_4Stages)
-        for k in range(nbr):                                                     # fc(S): the same weight on the column blocks, accumulated
-            G.linear(pooled.colslice(k * C, (k + 1) * C), Wf, bf if k == 0 else None, out=Z, accumulate=k > 0)
-        A = G.new(B, nbr * C)
-        for k in range(nbr):
-            G.linear(Z, *_lin(M, G, f"{agg}.fcs.{k}"), out=A.colslice(k * C, (k + 1) * C))
-        att = G.softmax(A.reshape(B * nbr, C), B, 0).reshape(B, nbr * C)         # softmax over the paths, per image and channel
-        gated = G.chan_gate(cat, att, B, N)
-        Wc, bc = _lin(M, G, agg + ".conv_bn_ac.0")
-        z = G.new(rows, Wc.data.shape[0])
-        for k in range(nbr):                                                     # conv(sum_k a_k x_k)
-            G.linear(gated.colslice(k * C, (k + 1) * C), Wc, bc if k == 0 else None, out=z, accumulate=k > 0)
-        return _bn(M, G, G.relu(z), agg + ".conv_bn_ac.2", ACT_NONE, out=out)
+        return _sk_block(M, G, cat, name + ".aggregate", B, side * side, C, out)
     if M.concat == "se":                                                         # SE_Block, MSTr.py:584-593
         agg = name + ".aggregate"
         y = G.relu(G.linear(G.chan_pool(cat, B, side * side), *_lin(M, G, agg + ".excitation.0", bias=False)))
@@ -1080,6 +1067,28 @@ def _mhca_stage(M, G, stack: Var, name: str, layers: int, B: int, side: int, out
         return _bn(M, G, z, agg + ".bn", ACT_RELU, out=out)
     y = G.linear(cat, *_lin(M, G, name + ".aggregate.conv", bias=False), bn_shift=_bn_shift(M, name + ".aggregate.bn"))   # "normal": Conv2d_BN with Hardswish, MSTr.py:1384-1390
     return _bn(M, G, y, name + ".aggregate.bn", ACT_HSWISH, out=out)
+
+
+def _sk_block(M, G, cat: Var, agg: str, B: int, N: int, C: int, out: Optional[Var] = None) -> Var:
+    """SK_Block (MSTr.py:1054-1107, Transception.py:306-353) over the branch maps side by side in cat [B*N, nbr*C]: per-channel softmax over
+    the branches from their pooled sum, then Conv1x1 + ReLU + BatchNorm of the gated sum."""
+    rows = cat.rows
+    pooled = G.chan_pool(cat, B, N)                                          # [B, 4C]: S = mean(sum_k x_k) = sum_k mean(x_k)
+    Wf, bf = _lin(M, G, agg + ".fc")
+    Z = G.new(B, Wf.data.shape[0])
+    nbr = cat.cols // C                                                      # branch maps: four (three in the first stage of MSViT_4Stages)
+    for k in range(nbr):                                                     # fc(S): the same weight on the column blocks, accumulated
+        G.linear(pooled.colslice(k * C, (k + 1) * C), Wf, bf if k == 0 else None, out=Z, accumulate=k > 0)
+    A = G.new(B, nbr * C)
+    for k in range(nbr):
+        G.linear(Z, *_lin(M, G, f"{agg}.fcs.{k}"), out=A.colslice(k * C, (k + 1) * C))
+    att = G.softmax(A.reshape(B * nbr, C), B, 0).reshape(B, nbr * C)         # softmax over the paths, per image and channel
+    gated = G.chan_gate(cat, att, B, N)
+    Wc, bc = _lin(M, G, agg + ".conv_bn_ac.0")
+    z = G.new(rows, Wc.data.shape[0])
+    for k in range(nbr):                                                     # conv(sum_k a_k x_k)
+        G.linear(gated.colslice(k * C, (k + 1) * C), Wc, bc if k == 0 else None, out=z, accumulate=k > 0)
+    return _bn(M, G, G.relu(z), agg + ".conv_bn_ac.2", ACT_NONE, out=out)
 
 
 def _channel_att(M, G, n: Var, X: Optional[Var], name: str, B: int, ntok: List[int], R: List[int], N6: int) -> Var:
@@ -1384,16 +1393,20 @@ def _bridge_and_decoder(M: MSTransception, G: Graph, Xb: Var, B: int, S: int, si
             X = _bridge_layer(M, G, X, li, B, sides, ntok, R, N6)
             if tap:
                 M.taps[f"bridge{li}"] = image_major(X)
-    # decoder
+    return _decoders(M, G, [stage_map(X, s) for s in range(4)], B, sides, tap)
+
+
+def _decoders(M, G: Graph, maps: List[Var], B: int, sides, tap: bool) -> Var:
+    """decoder_3 .. decoder_0 (MSTr.py:2843-2850, Transception.py:1048-1053) over the four encoder maps (token-major [B*side^2, C])."""
     G.segment("dec3")
-    d3 = _patch_expand(M, G, stage_map(X, 3), "decoder_3.layer_up", B, sides[3], 2)
+    d3 = _patch_expand(M, G, maps[3], "decoder_3.layer_up", B, sides[3], 2)
     G.segment("dec2")
-    d2 = _decoder(M, G, d3, stage_map(X, 2), "decoder_2", B, sides[2], False)
+    d2 = _decoder(M, G, d3, maps[2], "decoder_2", B, sides[2], False)
     G.segment("dec1")
-    d1 = _decoder(M, G, d2, stage_map(X, 1), "decoder_1", B, sides[1], False)
+    d1 = _decoder(M, G, d2, maps[1], "decoder_1", B, sides[1], False)
     if tap:
         M.taps["dec1"] = d1.data.float().view(B, sides[0] * sides[0], d1.cols).clone()
     G.segment("dec0")
-    out = _decoder(M, G, d1, stage_map(X, 0), "decoder_0", B, sides[0], True)
+    out = _decoder(M, G, d1, maps[0], "decoder_0", B, sides[0], True)
     G.segment("loss")
     return out
