@@ -1154,7 +1154,7 @@ def test_factor_att_core_fused(G, Bt, N, heads, Ch):
 
 def test_dwconv_backward_as_two_launches(G, monkeypatch):
     """The default backward of a stride-1 depthwise convolution is ONE launch for both gradients (tc_dwconv_bwd, tc_dwconv_multi mode 3);
-    the two-launch form stays for the side-stream mode: same checks against torch with the merge switched off."""
+    the two-launch form is the form `_DW_BWD_ONE = False` selects: same checks against torch with the merge switched off."""
     import transception_amd.engine as E
     monkeypatch.setattr(E, "_DW_BWD_ONE", False)
     test_dwconv(G, 64, 14, 3, 1, True, True)

@@ -1163,7 +1163,7 @@ extern "C" int tc_attn_bwd_seg(const void* Q, int ldq, const void* K, int ldk, c
     // workgroups of 4 key waves (measured: 4 waves x 2 workgroups per CU beats 5 x 1); query chunks so that ~2 workgroups per CU exist
     const int kt = (Nk + 31) / 32, nw = 4;
     const int kb = (kt + nw - 1) / nw, ntiles = sg.t32[nseg];
-    static const int dkv_slots = getenv("TC_DKV_SLOTS") ? atoi(getenv("TC_DKV_SLOTS")) : 512;   // resident workgroups aimed for
+    constexpr int dkv_slots = 512;   // resident workgroups aimed for
     int zs = dkv_slots / (kb * B);
     zs = zs < 1 ? 1 : (zs > (ntiles + 1) / 2 ? (ntiles + 1) / 2 : zs);
     int tpc = (ntiles + zs - 1) / zs;
@@ -1177,8 +1177,7 @@ extern "C" int tc_attn_bwd_seg(const void* Q, int ldq, const void* K, int ldk, c
     const float qs = qscaled ? 1.0f : scale * LOG2E, kscale = qscaled ? LN2 : scale;    // dK = dS^T Q: ln 2 when Q is stored as q * scale * log2(e)
     const int wide_dq = !(lddq & 7) && !((uintptr_t)dQ & 15);
     const int wide_rows = !((ldo | lddo) & 7) && !(((uintptr_t)O | (uintptr_t)dO) & 15);
-    static const int fuse_env = getenv("TC_ATTN_FUSE_DELTA") ? atoi(getenv("TC_ATTN_FUSE_DELTA")) : 1;
-    const bool fuse_delta = wide_rows && fuse_env;
+    const bool fuse_delta = wide_rows;
     // the hand-scheduled dK/dV stream: Q stored scaled, 16-byte rows, every query chunk at least two tiles long, and room for the per-tile
     // statistics (B x tiles x 64 floats) in the LAST of the TC_ATTN_DKV_SPLITS partial buffers
     const int dkv_asm_env = getenv("TC_ATTN_DKV_ASM") ? atoi(getenv("TC_ATTN_DKV_ASM")) : 1;

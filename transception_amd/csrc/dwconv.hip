@@ -10,8 +10,8 @@
 
 namespace {
 // workgroups a weight-gradient launch aims for (A/B switches; defaults = one tile walker per CU)
-inline int tc_dw_wg_target() { static const int v = getenv("TC_DW_WG") ? atoi(getenv("TC_DW_WG")) : 512; return v; }   // 256 while every launch folded at its tail; with the deferred fold: 12.07 / 12.03 / 12.01 / 12.03 ms at 256 / 384 / 512 / 768
-inline int tc_mid_wg_target() { static const int v = getenv("TC_MID_WG") ? atoi(getenv("TC_MID_WG")) : 384; return v; }   // (re-swept with the other two: 256 / 384 / 512 -> 12.07 / 12.03 / 12.06 ms)
+constexpr int tc_dw_wg_target() { return 512; }   // 256 while every launch folded at its tail; with the deferred fold: 12.07 / 12.03 / 12.01 / 12.03 ms at 256 / 384 / 512 / 768
+constexpr int tc_mid_wg_target() { return 384; }   // (re-swept with the other two: 256 / 384 / 512 -> 12.07 / 12.03 / 12.06 ms)
 
 
 // STRIDE is a template parameter (the strided form serves the first depthwise convolution of every RIPM stage, stride 2): with a run-time
@@ -1451,7 +1451,7 @@ __device__ __forceinline__ void ffn_mid_bwd_body(const FfnSegDev& a, long long w
     }
     __syncthreads();
     MSTAMP(8);
-    if (dbg_nofold) return;                                       // timing what-if only (TC_DEBUG_FFN_NOFOLD=1): parameter gradients are dropped
+    if (dbg_nofold) return;                                       // timing what-if only (the host passes 0): parameter gradients are dropped
     float* lflat = &lacc[0][0];
     int gm = 1;
     const float* pgroup = nullptr;
@@ -1539,10 +1539,8 @@ template <typename T>
 int launch_ffn_mid_bwd(const TcFfnSeg* segs, int nseg, int groups, long long wstride, void* ws, long long ws_bytes, hipStream_t s) {
     using D = FfnTile<T>;
     static_assert(D::smem_q * 16 <= 64 * 1024, "static dynamic-LDS limit");
-    static const int nth = getenv("TC_FFN_MID_THREADS") ? atoi(getenv("TC_FFN_MID_THREADS")) : 512;   // A/B switch: 256 = one wave per SIMD (14.18 vs 13.95 ms per step)
-    static const int nofold = getenv("TC_DEBUG_FFN_NOFOLD") ? atoi(getenv("TC_DEBUG_FFN_NOFOLD")) : 0;
     FfnMultiDev q;
-    q.n = nseg; q.wstride = wstride; q.dbg_nofold = nofold;
+    q.n = nseg; q.wstride = wstride; q.dbg_nofold = 0;
     long long blk = 0, part_floats = 0, cnts = 0;
     const bool defer = ws && ws_bytes < 0;                       // the walkers' sums go to the caller's own buffer (tc_dw_fold adds them later)
     if (defer && (uintptr_t)ws % 16) return TC_ERR_ARG;
@@ -1577,8 +1575,8 @@ int launch_ffn_mid_bwd(const TcFfnSeg* segs, int nseg, int groups, long long wst
     if (have_ws && (cnts > 4096 || 16384 + part_floats * 4 > ws_bytes))
         for (int i = 0; i < nseg; ++i) { q.s[i].wsc = nullptr; q.s[i].wsp = nullptr; }
     const size_t smem = (size_t)D::smem_q * 16;
-    if (nth == 256) hipLaunchKernelGGL((ffn_mid_bwd_kernel<T, 256>), dim3((unsigned)blk, groups), dim3(256), smem, s, q);
-    else hipLaunchKernelGGL((ffn_mid_bwd_kernel<T, 512>), dim3((unsigned)blk, groups), dim3(512), smem, s, q);
+    // 512 threads: two waves per SIMD (one wave per SIMD, 256 threads: 14.18 vs 13.95 ms per step)
+    hipLaunchKernelGGL((ffn_mid_bwd_kernel<T, 512>), dim3((unsigned)blk, groups), dim3(512), smem, s, q);
     return tc_launch_status();
 }
 
@@ -1759,7 +1757,7 @@ extern "C" int tc_dwconv_bwd_weight(const void* dy, int lddy, const void* x, int
     dim3 grid(tc_blocks(npix, 4 * 16, 256), (C + 63) / 64), block(256);
     hipStream_t s = (hipStream_t)stream;
     if (k == 3 && (ldx & 3) == 0 && (lddy & 3) == 0 && npix < 0x7fffffffLL) {
-        static const int wg3 = getenv("TC_DW_WGRAD3_WG") ? atoi(getenv("TC_DW_WGRAD3_WG")) : 64;
+        constexpr int wg3 = 64;
         const dim3 g3(tc_blocks(npix, 16 * 8, wg3), (C + 63) / 64);
         TC_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((dw_wgrad3_kernel<T>), g3, block, 0, s, (const T*)dy, lddy, (const T*)x, ldx, dw, db, B, H, W,
                                                     Ho, Wo, C, stride));

@@ -1149,7 +1149,7 @@ bool gemm_plan(const TcGemm* g, GemmDev& d, dim3& grid, bool& use128_out, bool f
     const long long big = (long long)((g->M + 127) / 128) * ((g->N + 127) / 128) * nb;
     // 128x128 tiles only for very large grids: on this model's shapes (K <= 2048, M <= 800k) 64x64 tiles measured 2-3 % faster
     // end to end at every threshold tried (more workgroups in flight per CU, and the dX/dW pair launch needs small tiles)
-    static const long long thr128 = getenv("TC_GEMM_THR128") ? atoll(getenv("TC_GEMM_THR128")) : 100000;
+    constexpr long long thr128 = 100000;                            // the same number as engine.py's _THR128: change both together
     const bool use128 = !force64 && big >= thr128 && g->M >= 96 && g->N >= 96;
     const int BM = use128 ? 128 : 64, BN = use128 ? 128 : 64;
     constexpr int BK = sizeof(T) == 4 ? 16 : 64;
@@ -1195,10 +1195,8 @@ bool gemm_plan(const TcGemm* g, GemmDev& d, dim3& grid, bool& use128_out, bool f
     grid = dim3((g->N + BN - 1) / BN, (g->M + BM - 1) / BM, nb * d.splitk);
     d.m_splitk = fdiv_make(d.splitk, 65536); d.m_nb2 = fdiv_make(d.nb2, 65536);
     d.m_gx = fdiv_make(grid.x, (unsigned long long)grid.x * grid.y * grid.z);          // (every linear index the launchers divide by gx is below the block count)
-    {   // XCD-aware tile numbering pays where several N-tiles share an A tile and there are enough tiles to spread (A/B: TC_GEMM_XCD=0)
-        static const int xcd_on = getenv("TC_GEMM_XCD") ? atoi(getenv("TC_GEMM_XCD")) : 1;
-        d.xcd = (xcd_on && grid.x > 1 && (long long)grid.x * grid.y >= 64) ? 1 : 0;
-    }
+    // XCD-aware tile numbering pays where several N-tiles share an A tile and there are enough tiles to spread
+    d.xcd = (grid.x > 1 && (long long)grid.x * grid.y >= 64) ? 1 : 0;
     use128_out = use128;
     if (g->bn_part) {                                               // statistics come from the LDS-staged plain-store epilogue of ONE product
         if (sizeof(T) != 2 || g->c_f32 || g->accumulate || g->atomic || d.splitk != 1 || nb != 1 || !d.vec8C || g->ffn_mode || g->act != TC_ACT_NONE)
@@ -1285,8 +1283,7 @@ extern "C" int tc_gemm_pair(const TcGemm* a, const TcGemm* b, void* stream) {
         if (!bigA && !bigB && nA + nB < 0x7fffffffLL) {
             q.nA = (int)nA; q.gxA = ga.x; q.gyA = ga.y; q.gxB = gb.x; q.gyB = gb.y;
             q.mgxA = fdiv_make(ga.x, nA + nB); q.mgyA = fdiv_make(ga.y, nA + nB); q.mgxB = fdiv_make(gb.x, nA + nB); q.mgyB = fdiv_make(gb.y, nA + nB);
-            static const int xcd_b = getenv("TC_PAIR_XCD_B") ? atoi(getenv("TC_PAIR_XCD_B")) : 1;   // A/B switch
-            if (xcd_b && gb.x * gb.y > 1) q.b.xcd |= 2;
+            if (gb.x * gb.y > 1) q.b.xcd |= 2;
             if (a->dtype == TC_BF16) hipLaunchKernelGGL(gemm_pair_kernel<bf16_t>, dim3((unsigned)(nA + nB)), dim3(256), 0, s, q);
             else hipLaunchKernelGGL(gemm_pair_kernel<f16_t>, dim3((unsigned)(nA + nB)), dim3(256), 0, s, q);
             return tc_launch_status();
@@ -1321,12 +1318,11 @@ extern "C" int tc_gemm_multi(const TcGemm* g, int n, void* stream) {
         // workgroups are dispatched in index order: the problems whose workgroups run the longest K loops go first, so the launch
         // does not end on a few long-running stragglers (measured 5-12 % on the bridge's four-scale MixFFN launches)
         std::stable_sort(order, order + n, [&](int a, int b) { return plan[a].kchunk > plan[b].kchunk; });
-        static const int xcd_b = getenv("TC_MULTI_XCD_B") ? atoi(getenv("TC_MULTI_XCD_B")) : 1;   // A/B switch
         for (int j = 0; j < n; ++j) {
             const int i = order[j];
             q.p[j] = plan[i]; q.kind[j] = kinds[i]; q.gx[j] = grids[i].x; q.gy[j] = grids[i].y; q.blk0[j] = (int)blk;
             q.mgy[j] = fdiv_make(grids[i].y, (unsigned long long)grids[i].x * grids[i].y * grids[i].z);
-            if (xcd_b && (kinds[i] == 2 || kinds[i] == 5) && grids[i].x * grids[i].y > 1) q.p[j].xcd |= 2;
+            if ((kinds[i] == 2 || kinds[i] == 5) && grids[i].x * grids[i].y > 1) q.p[j].xcd |= 2;
             blk += (long long)grids[i].x * grids[i].y * grids[i].z;
             if (blk > 0x7fffffffLL) ok = false;
         }

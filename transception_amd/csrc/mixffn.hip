@@ -468,8 +468,6 @@ int ffn_num_cus() {
 template <int C>
 void ffn_pick_tile(int H, int W, long long images, int fth, int ftw, int& TH, int& TW) {
     using K = FfnCfg<C>;
-    static const int eth = getenv("TC_FFN_TH") ? atoi(getenv("TC_FFN_TH")) : 0, etw = getenv("TC_FFN_TW") ? atoi(getenv("TC_FFN_TW")) : 0;
-    if (!(fth && ftw)) { fth = eth; ftw = etw; }
     const double ncu = ffn_num_cus();
     double best = 1e30;
     TH = 1; TW = 2;

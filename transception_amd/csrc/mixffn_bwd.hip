@@ -851,8 +851,6 @@ int bwd_num_cus() {
 template <int C>
 void dw_pick_tile(int H, int W, long long images, int gxmax, int fth, int ftw, int& TH, int& TW) {
     using K = DwCfg<C>;
-    static const int eth = getenv("TC_FFN_BWD_TH") ? atoi(getenv("TC_FFN_BWD_TH")) : 0, etw = getenv("TC_FFN_BWD_TW") ? atoi(getenv("TC_FFN_BWD_TW")) : 0;
-    if (!(fth && ftw)) { fth = eth; ftw = etw; }
     double best = 1e30;
     TH = 1; TW = 1;
     for (int th = 1; th <= K::THMAX && th <= H; ++th)

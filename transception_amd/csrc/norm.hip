@@ -11,13 +11,11 @@ constexpr int LN_MAXC = 2048;
 #define LN_FOLD 8
 #endif
 constexpr int LN_BWD_MAX_BLOCKS = 4096, LN_BWD_ROWS_PER_GROUP = 4;   // fused dx + parameter-gradient launch
-inline int ln_bwd_wg_min() { static const int v = getenv("TC_LN_WG_MIN") ? atoi(getenv("TC_LN_WG_MIN")) : 1024; return v < 16 ? 16 : v; }   // 512 with the fold at the tail; deferred: 256 / 512 / 1024 -> 12.11 / 12.07 / 12.04 ms
-inline int ln_bwd_blocks(bool deferred) {   // A/B switch (<= LN_BWD_MAX_BLOCKS, which sizes the scratch)
+constexpr int LN_BWD_WG_MIN = 1024;   // workgroups before rows are stacked per lane group (>= 16).  512 with the fold at the tail; deferred: 256 / 512 / 1024 -> 12.11 / 12.07 / 12.04 ms
+inline int ln_bwd_blocks(bool deferred) {   // (16 .. LN_BWD_MAX_BLOCKS, which sizes the scratch)
     // launches that fold at their own tail: 1024 (every block is one more partial to park and fold in-kernel); deferred fold: 4096
     // (1024 / 2048 / 4096 -> 11.87 / 11.85 / 11.84 ms per step)
-    static const int v = getenv("TC_LN_BWD_BLOCKS") ? atoi(getenv("TC_LN_BWD_BLOCKS")) : 0;
-    const int w = v > 0 ? v : (deferred ? LN_BWD_MAX_BLOCKS : 1024);
-    return w < 16 ? 16 : (w > LN_BWD_MAX_BLOCKS ? LN_BWD_MAX_BLOCKS : w);
+    return deferred ? LN_BWD_MAX_BLOCKS : 1024;
 }
 
 // ---------------------------------------------------------------------------------------------- LayerNorm
@@ -469,8 +467,8 @@ __global__ __launch_bounds__(256) void ln_param_grad_kernel(const T* __restrict_
 #ifndef BN_MAX_CHUNKS
 #define BN_MAX_CHUNKS 128
 #endif
-inline int bn_chunk_cap() { static const int v = getenv("TC_BN_CHUNKS") ? atoi(getenv("TC_BN_CHUNKS")) : BN_MAX_CHUNKS; return v < 1 ? 1 : (v > 128 ? 128 : v); }
-inline int bn_nchunk(int rows) { int n = (rows + 63) / 64; const int cap = bn_chunk_cap(); return n < 1 ? 1 : (n > cap ? cap : n); }
+static_assert(BN_MAX_CHUNKS >= 1 && BN_MAX_CHUNKS <= 128, "the apply kernels and tc_bn_scratch_floats size for at most 128 chunks");
+inline int bn_nchunk(int rows) { int n = (rows + 63) / 64; constexpr int cap = BN_MAX_CHUNKS; return n < 1 ? 1 : (n > cap ? cap : n); }
 
 // mode 0 (forward stats):  S1 = sum(x - shift), S2 = sum((x-shift)^2), shift = x[0, c]
 // mode 1 (backward sums):  S1 = sum(dz), S2 = sum(dz * xhat), dz = dy * act'(z)
@@ -737,9 +735,8 @@ __global__ __launch_bounds__(256) void ln_fold_kernel(const LnFoldDev q) {
 inline int ln_bwd_nblk(int rows, int C, bool with_params, bool deferred) {
     const int quads = C >> 2;
     const int GS = quads <= 16 ? 16 : (quads <= 32 ? 32 : 64);
-    static const int ilp_on = getenv("TC_LN_BWD_ILP") ? atoi(getenv("TC_LN_BWD_ILP")) : 1;
-    const bool ilp = ilp_on && quads <= 64 && rows >= 8192;
-    int rpg = with_params ? rows / ((256 / GS) * ln_bwd_wg_min()) : 1;   // rows per lane group: >= 512 workgroups before rows are stacked
+    const bool ilp = quads <= 64 && rows >= 8192;
+    int rpg = with_params ? rows / ((256 / GS) * LN_BWD_WG_MIN) : 1;   // rows per lane group: >= 512 workgroups before rows are stacked
     rpg = rpg < 1 ? 1 : (rpg > LN_BWD_ROWS_PER_GROUP ? LN_BWD_ROWS_PER_GROUP : rpg);
     if (ilp && rpg < 2) rpg = 2;
     return tc_blocks(rows, (256 / GS) * rpg, with_params ? ln_bwd_blocks(deferred) : 8192);
@@ -755,9 +752,8 @@ static int ln_fwd_impl(const void* x, int ldx, const void* gamma, const void* be
         return TC_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
     {   // 16-bit rows of 64 / 128 / 256 / 512 channels, every row piece 16-byte aligned, large maps: eight channels per lane (ln_fwd_v8_kernel)
-        static const int v8_on = getenv("TC_LN_FWD_V8") ? atoi(getenv("TC_LN_FWD_V8")) : 1;
         const bool al = !((ldx | ldy) & 7) && !(pstride & 7) && !(((uintptr_t)x | (uintptr_t)y | (uintptr_t)gamma | (uintptr_t)beta) & 15);
-        if (v8_on && (dtype == TC_BF16 || dtype == TC_F16) && act == TC_ACT_NONE && al && rows >= 65536 && (C == 64 || C == 128 || C == 256 || C == 512)) {
+        if ((dtype == TC_BF16 || dtype == TC_F16) && act == TC_ACT_NONE && al && rows >= 65536 && (C == 64 || C == 128 || C == 256 || C == 512)) {
             const dim3 grid(tc_blocks(rows, (2048 / C) * 4, 2048), groups);
 #define TC_LNF8(T_, GS_) hipLaunchKernelGGL((ln_fwd_v8_kernel<T_, GS_, 4>), grid, dim3(256), 0, s, (const T_*)x, ldx, (const T_*)gamma, (const T_*)beta,   \
                                             (T_*)y, ldy, mean, rstd, rows, eps, pstride, map)
@@ -818,10 +814,9 @@ static int ln_bwd_impl(const void* dy, int lddy, const void* x, int ldx, const v
     int nblk = 0;
     float* partial = nullptr;
     {   // 16-bit rows of 64 / 128 / 256 / 512 channels, every row piece 16-byte aligned: eight channels per lane (ln_bwd_v8_kernel)
-        static const int v8_on = getenv("TC_LN_BWD_V8") ? atoi(getenv("TC_LN_BWD_V8")) : 1;
         const bool al = !((lddy | ldx | lddx | (dres ? ldres : 0)) & 7) && !(pstride & 7) &&
                         !(((uintptr_t)dy | (uintptr_t)x | (uintptr_t)dx | (uintptr_t)gamma | (dres ? (uintptr_t)dres : 0)) & 15);
-        if (v8_on && (dtype == TC_BF16 || dtype == TC_F16) && act == TC_ACT_NONE && al && (C == 64 || C == 128 || C == 256 || C == 512)) {
+        if ((dtype == TC_BF16 || dtype == TC_F16) && act == TC_ACT_NONE && al && (C == 64 || C == 128 || C == 256 || C == 512)) {
             nblk = ln_bwd_nblk(rows, C, dgamma != nullptr, defer_part != nullptr);
             partial = defer_part ? defer_part :
                       (dgamma && scratch && (uintptr_t)scratch % 16 == 0 && scratch_floats >= 4096 + (long long)groups * nblk * 2 * C &&
@@ -848,8 +843,7 @@ static int ln_bwd_impl(const void* dy, int lddy, const void* x, int ldx, const v
                                           dbeta, rows, C, act, pstride, partial, reinterpret_cast<int*>(scratch), map, defer_part ? 1 : 0)
 #define TC_LNB(GS, NV) {                                                                                                                  \
         constexpr int RPT = 2;   /* rows in flight per lane group (narrow rows): 14.16 vs 14.19 ms per step; 4 rows: 14.21 vs 14.22 */                                                         \
-        static const int ilp_on = getenv("TC_LN_BWD_ILP") ? atoi(getenv("TC_LN_BWD_ILP")) : 1;                                             \
-        const bool ilp = ilp_on && NV == 1 && rows >= 8192;                                                                                \
+        const bool ilp = NV == 1 && rows >= 8192;                                                                                          \
         nblk = ln_bwd_nblk(rows, C, dgamma != nullptr, defer_part != nullptr);                                                             \
         partial = defer_part ? defer_part :                                                                                               \
                   (dgamma && scratch && (uintptr_t)scratch % 16 == 0 && scratch_floats >= 4096 + (long long)groups * nblk * 2 * C &&      \
@@ -959,7 +953,7 @@ extern "C" int tc_bn_fwd(const void* x, int ldx, const void* gamma, const void* 
         }
         // rows per workgroup of the apply pass: these maps are a few MB, the pass is bound by its round trips, not by bytes -- more, shorter
         // workgroups win although each folds the chunk partials again (RIPM stages alone: 536 us at 64 rows, 527 at 32, 523 at 16, 594 at 256)
-        static const int rpw = getenv("TC_BN_ROWS_PER_WG") ? atoi(getenv("TC_BN_ROWS_PER_WG")) : 16;
+        constexpr int rpw = 16;
         const int rb = tc_blocks(rows, rpw, 2048);
         hipLaunchKernelGGL((bn_apply_kernel<T>), dim3(rb, cb), dim3(256), 0, s, (const T*)x, ldx, (const T*)gamma,
                            (const T*)beta, running_mean, running_var, (const T*)res, ldres, (T*)y, ldy, save_mean, save_rstd,
@@ -980,7 +974,7 @@ extern "C" int tc_bn_bwd(const void* dy, int lddy, const void* x, int ldx, const
     TC_DISPATCH_DTYPE(dtype, {
         hipLaunchKernelGGL((bn_partial_kernel<T, 1>), dim3(nchunk, cb), dim3(256), 0, s, (const T*)x, ldx, (const T*)dy, lddy,
                            (const T*)gamma, (const T*)beta, save_mean, save_rstd, partial, rows, C, act);
-        static const int rpwb = getenv("TC_BN_BWD_ROWS_PER_WG") ? atoi(getenv("TC_BN_BWD_ROWS_PER_WG")) : 16;
+        constexpr int rpwb = 16;
         const int rb = tc_blocks(rows, rpwb, 2048);
         hipLaunchKernelGGL((bn_bwd_apply_kernel<T>), dim3(rb, cb), dim3(256), 0, s, (const T*)dy, lddy, (const T*)x, ldx,
                            (const T*)gamma, (const T*)beta, save_mean, save_rstd, (T*)dx, lddx, dgamma, dbeta, partial, nchunk,

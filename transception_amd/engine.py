@@ -27,7 +27,6 @@ _DT = {torch.float32: TC_F32, torch.bfloat16: TC_BF16, torch.float16: TC_F16}
 # launches with HIP events on the launching stream (the events are recorded on torch's current stream, which is the
 # stream every kernel here is launched on).
 PROFILE: Optional[dict] = None
-BN_STATS_IN_GEMM = os.environ.get("TC_BN_STATS_IN_GEMM", "1") != "0"     # A/B switch: BatchNorm statistics in the producing GEMM's epilogue
 
 
 SEG_MARKS = os.environ.get("TC_SEG_MARKS", "")      # json path: section markers on (Graph.segment)
@@ -149,47 +148,32 @@ def _ptr(t: Optional[torch.Tensor]):
     return None if t is None else t.data_ptr()
 
 
-_SIDE_STREAMS: Dict[str, list] = {}
-
-
-def _side_streams(device, n: int):
-    key = str(device)
-    pool = _SIDE_STREAMS.setdefault(key, [])
-    while len(pool) < n:
-        pool.append(torch.cuda.Stream(device))
-    return pool[:n]
-
-
-_WORKSPACES: Dict[Tuple[str, int, str], torch.Tensor] = {}
+_WORKSPACES: Dict[Tuple[str, str], torch.Tensor] = {}
 WORKSPACE_BYTES = 16384 + 1024 * 16384             # arrival counters + 1024 fp32 64x64 partial tiles
 
 
-def _workspace(device, stream_ptr: int, tag: str = "") -> torch.Tensor:
-    """Split-K fix-up workspace of the kernels launched on `stream_ptr` (include/transception_hip.h, TcGemm.ws): launches on one
-    stream never overlap, so one buffer per stream is enough; zeroed once, every launch leaves its counters zero.  `tag`: a
+def _workspace(device, tag: str = "") -> torch.Tensor:
+    """Split-K fix-up workspace of the kernels launched on `device` (include/transception_hip.h, TcGemm.ws): the engine's launches on a
+    device never overlap, so one buffer per (device, tag) is enough; zeroed once, every launch leaves its counters zero.  `tag`: a
     separate buffer for launches that cut it into per-problem slices (their counter areas must never have held partial tiles)."""
-    # Single-stream mode (the default): warm-up stream, capture stream and replay stream take turns and never run launches
-    # concurrently, so they share ONE workspace -- a workspace per stream pointer was created (and zero-filled: 134 MB for the
-    # "many" one) INSIDE the capture of a step, whose stream is new, and the fill was replayed with every step.
-    key = (str(device), int(stream_ptr or 0) if Graph.use_streams else 0, tag)
-    # CONSTRAINT (ADVICE r3): this holds only while the engine launches of a device are serialized -- one training / evaluation loop at a
-    # time.  Two loops driving the engine concurrently on one device (an evaluation thread beside the training thread, two models on two
-    # streams) would share split-K counters and partial tiles; run them with TC_STREAMS=1 (a workspace per stream) or one after the
-    # other.  (Not asserted here: autograd runs the backward of a step on its own worker thread, so thread identity says nothing.)
+    # Warm-up stream, capture stream and replay stream take turns and never run launches concurrently, so they share ONE workspace
+    # -- a workspace per stream pointer was created (and zero-filled: 134 MB for the "many" one) INSIDE the capture of a step, whose
+    # stream is new, and the fill was replayed with every step.
+    key = (str(device), tag)
+    # CONSTRAINT (ADVICE r3): the engine serialises the launches of a device -- every launch of a Graph goes to its one stream -- and
+    # this buffer relies on it.  Two loops driving the engine on one device (an evaluation thread beside the training thread, two
+    # models on two streams) would share split-K counters and partial tiles, so they run one after the other.  (Not asserted here:
+    # autograd runs the backward of a step on its own worker thread, so thread identity says nothing.)
     ws = _WORKSPACES.get(key)
     if ws is None:
         ws = _WORKSPACES[key] = torch.zeros(WORKSPACE_BYTES * (8 if tag == "many" else 1), dtype=torch.uint8, device=device)
     return ws
 
 
-_SPLITK_CAP = int(os.environ.get("TC_SPLITK_CAP", "128"))
-_SPLITK_BLOCKS = int(os.environ.get("TC_SPLITK_BLOCKS", "512"))
-_SPLITK_KMIN = int(os.environ.get("TC_SPLITK_KMIN", "384"))              # shortest K range of a split of a weight-gradient product: 256 / 320 / 384 / 448 / 512 -> 12.00 / 11.94 / 11.95 / 12.11 / 12.20 ms (fewer fp32 atomics against longer serial K loops)
-_THR128 = int(os.environ.get("TC_GEMM_THR128", "100000"))     # keep in step with gemm.hip (gemm_plan)
-_GEMM_PAIR = os.environ.get("TC_GEMM_PAIR", "1") != "0"
-_N_WSTREAMS = int(os.environ.get("TC_WGRAD_STREAMS", "4"))
-_NO_PENDING = bool(os.environ.get("TC_DEBUG_NO_PENDING"))   # timing what-if only (racy)
-_SKIP_WGRAD = bool(os.environ.get("TC_DEBUG_SKIP_WGRAD"))
+_SPLITK_CAP = 128
+_SPLITK_BLOCKS = 512
+_SPLITK_KMIN = 384              # shortest K range of a split of a weight-gradient product: 256 / 320 / 384 / 448 / 512 -> 12.00 / 11.94 / 11.95 / 12.11 / 12.20 ms (fewer fp32 atomics against longer serial K loops)
+_THR128 = 100000     # the same number as gemm.hip's thr128 (gemm_plan): change both together
 _FFN_STORE_ACT = os.environ.get("TC_FFN_STORE_ACT", "1") != "0"   # MixFFN: keep GELU(LN(d)) from the forward pass (0: recompute it in dW2's loader)
 _FFN_LN_GEMM_MAXC = int(os.environ.get("TC_FFN_LN_GEMM_MAXC", "64"))  # widest fc2 output for which LayerNorm + GELU run in its A loader
 _FFN_TILED = os.environ.get("TC_FFN_TILED", "1") != "0"        # MixFFN forward as one spatially tiled kernel where the library supports the width (csrc/mixffn.hip)
@@ -227,12 +211,8 @@ _ZERO_NEED: Dict[Tuple[str, torch.dtype], int] = {}
 
 
 class _ZeroArena:
-    def __init__(self, device, dtype, shared: bool = True):
-        """shared=False (the TC_STREAMS=1 mode): every request gets its own torch.zeros storage -- Graph._pending keys the events of
-        side-stream weight-gradient kernels by gradient STORAGE, and one arena storage under several gradient buffers would let one
-        buffer's event overwrite another's; the single zero fill would also run on whichever branch stream asked first."""
+    def __init__(self, device, dtype):
         self.key = (str(device), dtype)
-        self.shared = shared
         self.device, self.dtype = device, dtype
         self.buf: Optional[torch.Tensor] = None
         self.used = 0
@@ -240,8 +220,6 @@ class _ZeroArena:
 
     def zeros_like(self, t: torch.Tensor) -> torch.Tensor:
         n = (t.numel() + 127) // 128 * 128                       # keep 256-byte alignment of every sub-buffer
-        if not self.shared:
-            return torch.zeros_like(t)
         self.asked += n
         if self.buf is None:
             need = _ZERO_NEED.get(self.key, 0)
@@ -255,52 +233,6 @@ class _ZeroArena:
 
     def close(self):
         _ZERO_NEED[self.key] = max(self.asked, 0)
-
-
-class _Branch:
-    def __init__(self, G, stream):
-        self.G, self.stream, self.ctx, self.prev = G, stream, None, None
-
-    def __enter__(self):
-        G = self.G
-        self.prev = (G.cur, G.stream)
-        G.cur, G.stream = self.stream, self.stream.cuda_stream
-        self.ctx = torch.cuda.stream(self.stream)
-        self.ctx.__enter__()
-        return self
-
-    def __exit__(self, *a):
-        self.ctx.__exit__(*a)
-        self.G.cur, self.G.stream = self.prev
-
-
-class _Parallel:
-    """Fork/join of independent sub-graphs over HIP streams (branch 0 stays on the main stream).  In a captured hipGraph the
-    branches become parallel node chains; the tape replays them in reverse with the fork and join swapped."""
-
-    def __init__(self, G, n: int, shared=()):
-        self.G, self.n = G, n
-        self.shared = [v.root for v in shared]      # buffers several branches write gradient slices of
-        self.sides = _side_streams(G.dev, n - 1) if (n > 1 and G.use_streams and torch.device(G.dev).type == "cuda") else []
-
-    def __enter__(self):
-        G = self.G
-        for s in self.sides:
-            s.wait_stream(G.cur)
-        if G.record and self.sides:
-            G.tape.append(("join", G.cur, self.sides))          # backward: main waits for the branches
-        return self
-
-    def branch(self, i: int):
-        G = self.G
-        return _Branch(G, self.sides[i - 1] if (i > 0 and self.sides) else G.cur)
-
-    def __exit__(self, *a):
-        G = self.G
-        for s in self.sides:
-            G.cur.wait_stream(s)
-        if G.record and self.sides:
-            G.tape.append(("fork", G.cur, self.sides, self.shared))   # backward: the branches wait for main
 
 
 class _Grouped:
@@ -317,20 +249,16 @@ class _Grouped:
 
 
 class Graph:
-    # Side streams are OFF by default.  Measured on MI355X (ROCm 7.2): a captured step executes at the SUM of its kernel times
-    # whether its branches are captured on 1 stream or 8 (kernels from different HW queues overlap only at their tails, and a
-    # graph wider than the 4 HW queues shares queues), while the single-stream graph runs every kernel un-contended and
-    # back-to-back -- 671 vs 634-648 img/s -- and avoids the hipStreamEndCapture crashes some multi-stream shapes trigger.
-    use_streams = os.environ.get("TC_STREAMS", "0") == "1"
-    overlap_wgrad = os.environ.get("TC_NO_WGRAD_OVERLAP", "0") != "1"
+    # Every launch of a Graph goes to ONE stream (self.stream), forward and backward.  Measured on MI355X (ROCm 7.2): a captured
+    # step executes at the SUM of its kernel times whether its branches are captured on 1 stream or 8 (kernels from different HW
+    # queues overlap only at their tails, and a graph wider than the 4 HW queues shares queues), while the single-stream graph runs
+    # every kernel un-contended and back-to-back -- 671 vs 634-648 img/s (DESIGN_HISTORY.md) -- and a captured step has no parallel
+    # branches, which hipStreamEndCapture crashed on for some shapes.
     ngroups = 1          # ops with parameters run `ngroups` stacked row blocks, block g with the weights at +g*P.gs
     pgs = 0
 
     def grouped(self, n: int, pgs: int) -> _Grouped:
         return _Grouped(self, n, pgs)
-
-    def parallel(self, n: int, shared=()) -> _Parallel:
-        return _Parallel(self, n, shared)
 
     def __init__(self, dtype: torch.dtype, device, training: bool, record: bool):
         self.L = lib()
@@ -339,11 +267,7 @@ class Graph:
         self.dev = device
         self.training = training
         self.record = record
-        self.tape: List[Callable[[], None]] = []
-        self._wnext = 0
-        self._wstream = None          # side stream for weight-gradient kernels (nothing downstream in backward needs them)
-        self._pending: Dict[int, torch.cuda.Event] = {}     # gradient storage -> last weight-gradient kernel still reading it
-        self._keep: list = []
+        self.tape: list = []                                 # backward closures, plus ("mark", name) cuts
         self._ln_pending: list = []                          # LayerNorm backward launches whose dgamma / dbeta partials wait for the leg's fold
         self._dw_pending: list = []                          # depthwise backward launches whose weight-gradient sums wait for the leg's fold
         self.cur = torch.cuda.current_stream(device) if torch.device(device).type == "cuda" else None
@@ -352,7 +276,7 @@ class Graph:
         self._seg_prev = None
         if SEG_MARKS:
             del SEG_LABELS[:]
-        self._zeros = _ZeroArena(device, dtype, shared=not self.use_streams)
+        self._zeros = _ZeroArena(device, dtype)
 
     # ------------------------------------------------------------------ memory
     def new(self, rows: int, cols: int, requires_grad: bool = True, covered: bool = False) -> Var:
@@ -393,10 +317,6 @@ class Graph:
             r.whole_written = True
         else:
             r.written.append(reg)
-        if self._pending and not _NO_PENDING:
-            ev = self._pending.pop(r.grad_t.untyped_storage().data_ptr(), None)
-            if ev is not None:
-                self.cur.wait_event(ev)                  # a weight-gradient kernel on the side stream still reads this buffer
         return v.apply_path(r.grad_t), int(acc)
 
     def _region_grad(self, root: Var, off: int, nelem: int) -> torch.Tensor:
@@ -440,28 +360,6 @@ class Graph:
             self.L.tc_add(_ptr(g), g.stride(0), _ptr(tmp), tmp.stride(0), _ptr(g), g.stride(0), g.shape[0], g.shape[1],
                           self.dt, self.stream)
 
-    def _weight_grad(self, fn: Callable[[], None], reads: Optional[torch.Tensor] = None):
-        """Run a weight-gradient kernel on the side stream: dW / dw / db are only consumed by the optimizer, so they overlap
-        with the activation-gradient chain.  `reads` = the upstream gradient buffer the kernel reads: a later in-place
-        accumulation into that buffer (aliased residual gradients) must wait for this kernel (see wgrad)."""
-        if _SKIP_WGRAD:                                  # timing what-if only (results are wrong): critical-path analysis
-            return
-        if not (self.overlap_wgrad and self.use_streams and self.cur is not None):
-            fn()
-            return
-        if self._wstream is None:
-            self._wstream = _side_streams(self.dev, 3 + _N_WSTREAMS)[3:]
-        ws = self._wstream[self._wnext % len(self._wstream)]   # independent kernels: round-robin so they also overlap each other
-        self._wnext += 1
-        ws.wait_stream(self.cur)
-        with _Branch(self, ws):
-            fn()
-        if reads is not None:
-            ev = torch.cuda.Event()
-            ev.record(ws)
-            self._pending[reads.untyped_storage().data_ptr()] = ev
-            self._keep.append(reads)
-
     def mark(self, name: str):
         """A named cut in the tape: backward(until=name) stops there, so a caller can start exchanging the gradients that are
         complete (everything recorded after the mark) while the rest of the backward sweep runs."""
@@ -487,40 +385,14 @@ class Graph:
 
     def backward(self, until: Optional[str] = None) -> bool:
         """Runs the tape in reverse.  With `until`, stops at that mark and returns False (call again to finish)."""
-        main = (self.cur, self.stream)
         while self.tape:
             entry = self.tape.pop()
-            if entry[0] == "mark":
-                if entry[1] == until:
-                    self.cur, self.stream = main
-                    self._flush_param_folds()
-                    if self._wstream is not None:
-                        for ws in self._wstream:
-                            self.cur.wait_stream(ws)
-                    return False
-            elif entry[0] == "join":                       # forward fork point: everything the branches produced flows back to main
-                for s in entry[2]:
-                    entry[1].wait_stream(s)
-            elif entry[0] == "fork":                     # forward join point: branch backward starts after main's upstream work
-                for r in entry[3]:                       # gradient buffers shared by the branches are created (zeroed) on main
-                    if r.grad_t is None:                 # first, so no branch's lazy zero-fill can race another branch's write
-                        r.grad_t = self._zeros.zeros_like(r.data)
-                for s in entry[2]:
-                    s.wait_stream(entry[1])
-            else:
-                fn, st = entry
-                if st is None or st is self.cur:
-                    fn()
-                else:
-                    with _Branch(self, st):
-                        fn()
-        self.cur, self.stream = main
+            if callable(entry):
+                entry()
+            elif entry[1] == until:                      # ("mark", name)
+                self._flush_param_folds()
+                return False
         self._flush_param_folds()
-        if self._wstream is not None:
-            for ws in self._wstream:
-                self.cur.wait_stream(ws)                 # all weight gradients are in the arena before anything follows
-        self._pending.clear()
-        self._keep.clear()
         self.tape = []
         self._zeros.close()
         if SEG_MARKS:
@@ -556,7 +428,7 @@ class Graph:
 
     def _rec(self, fn):
         if self.record:
-            self.tape.append((fn, self.cur))
+            self.tape.append(fn)
 
     # ------------------------------------------------------------------ GEMM plumbing
     def _gemm(self, A, lda, B, ldb, Cm, ldc, M, N, K, tA, tB, bias=None, R=None, ldr=0, alpha=1.0, acc=0, act=ACT_NONE,
@@ -572,7 +444,7 @@ class Graph:
     def _gemm_desc(self, A, lda, B, ldb, Cm, ldc, M, N, K, tA, tB, bias=None, R=None, ldr=0, alpha=1.0, acc=0, act=ACT_NONE,
                    splitk=1, nb1=1, nb2=1, sA=(0, 0), sB=(0, 0), sC=(0, 0), sR=(0, 0), c_f32=0, atomic=0, rowsum=None, sbias=0,
                    srow=0, use_ws=True, bgap=(0, 0)) -> TcGemm:
-        ws = _workspace(self.dev, self.stream) if use_ws else None
+        ws = _workspace(self.dev) if use_ws else None
         return TcGemm(A, B, Cm, bias, R, M, N, K, lda, ldb, ldc, ldr, tA, tB, nb1, nb2, sA[0], sA[1], sB[0], sB[1], sC[0], sC[1],
                       sR[0], sR[1], alpha, acc, act, splitk, self.dt, c_f32, atomic, rowsum, sbias, srow, bgap[0], bgap[1],
                       ws.data_ptr() if ws is not None else None, ws.numel() if ws is not None else 0)
@@ -629,7 +501,7 @@ class Graph:
         if post_scale is not None:
             assert act == ACT_NONE and not accumulate
         bn_part = None
-        if (bn_shift is not None and BN_STATS_IN_GEMM and self.training and self.dtype != torch.float32 and nb == 1 and not accumulate
+        if (bn_shift is not None and self.training and self.dtype != torch.float32 and nb == 1 and not accumulate
                 and act == ACT_NONE and post_scale is None and N % 8 == 0 and out.ld % 8 == 0 and out.data.data_ptr() % 16 == 0):
             tiles = (M + 63) // 64
             bn_part = self.f32(N * (1 + 2 * max(tiles, 128)))        # (also the scratch of the BatchNorm's backward sums)
@@ -651,7 +523,7 @@ class Graph:
                 dz = torch.empty_like(dy)
                 self.L.tc_sigmoid_bwd(_ptr(dy), _ptr(out.data), _ptr(dz), dy.numel(), self.dt, self.stream)
             want_db = b is not None and b.grad is not None
-            paired = (_GEMM_PAIR and x.requires_grad and W.grad is not None and self.dtype != torch.float32
+            paired = (x.requires_grad and W.grad is not None and self.dtype != torch.float32
                       and self._small_tiles(M, K, nb) and self._small_tiles(N, K, nb))
             if paired:
                 # dX and dW (+db) of this layer share one launch: two short grids fill the CUs together (tc_gemm_pair)
@@ -663,7 +535,7 @@ class Graph:
                                      splitk=self._splitk(N, K, M), c_f32=1, nb1=nb, sA=(so, 0), sB=(sx, 0), sC=(sw, 0),
                                      atomic=int(nb > 1 and not grouped), rowsum=_ptr(b.grad) if want_db else None, srow=sw,
                                      use_ws=False)
-                if gb.splitk > 128:                      # the one workspace of this stream goes to the problem that folds partials
+                if gb.splitk > 128:                      # the one workspace goes to the problem that folds partials
                     gb.ws, gb.ws_bytes, ga.ws, ga.ws_bytes = ga.ws, ga.ws_bytes, None, 0
                 self.n_launch += 1
                 _timed_gemm("pair", [ga, gb], lambda: self.L.tc_gemm_pair(C.byref(ga), C.byref(gb), self.stream))
@@ -675,10 +547,9 @@ class Graph:
                 pass
             elif W.grad is not None:
                 gW = W.grad if wcols is None else W.grad[:, wcols[0]:wcols[1]]
-                self._weight_grad(lambda: self._gemm(
-                    _ptr(dz), dz.stride(0), _ptr(x.data), x.ld, _ptr(gW), gW.stride(0), N, K, M, 1, 0, acc=1,
-                    splitk=self._splitk(N, K, M), c_f32=1, nb1=nb, sA=(so, 0), sB=(sx, 0), sC=(sw, 0),
-                    atomic=int(nb > 1 and not grouped), rowsum=_ptr(b.grad) if want_db else None, srow=sw), reads=dz)
+                self._gemm(_ptr(dz), dz.stride(0), _ptr(x.data), x.ld, _ptr(gW), gW.stride(0), N, K, M, 1, 0, acc=1,
+                           splitk=self._splitk(N, K, M), c_f32=1, nb1=nb, sA=(so, 0), sB=(sx, 0), sC=(sw, 0),
+                           atomic=int(nb > 1 and not grouped), rowsum=_ptr(b.grad) if want_db else None, srow=sw)
             elif want_db:
                 assert not grouped
                 self.L.tc_colsum(_ptr(dz), M, N, dz.stride(0), nb, so, _ptr(b.grad), 1, self.dt, self.stream)
@@ -699,7 +570,7 @@ class Graph:
         n = len(items)
         assert self.ngroups == 1 and n >= 1
         items = [tuple(it) + (None,) * (7 - len(it)) for it in items]
-        wsb = _workspace(self.dev, self.stream, "many")
+        wsb = _workspace(self.dev, "many")
         sl = (wsb.numel() // 8) & ~16383                    # a private, full-size workspace slice per problem (counters + partials)
 
         def desc(i, *a, **k):
@@ -853,7 +724,7 @@ class Graph:
         assert n >= 1 and (Gn == 1 or n == 1)
         gs = self.pgs if Gn > 1 else 0
         many = n > 1
-        wsb = _workspace(self.dev, self.stream, "many") if many else None
+        wsb = _workspace(self.dev, "many") if many else None
         sl = (wsb.numel() // 8) & ~16383 if many else 0
 
         def desc(i, *a, **k):
@@ -1031,7 +902,7 @@ class Graph:
                                    _ptr(t["lg"].grad) if hg else None, _ptr(t["lb"].grad) if hg else None,
                                    t["C4"], t["C4"], t["C4"], t["C4"], t["C4"], t["B"], t["H"], t["W"], t["nch2"])
             nf = 0
-            if _DW_DEFER and not self.use_streams and all(t["wd"].grad is not None for t in st):     # the walkers' sums parked; one tc_dw_fold per backward leg
+            if _DW_DEFER and all(t["wd"].grad is not None for t in st):     # the walkers' sums parked; one tc_dw_fold per backward leg
                 from ._lib import TcDwFold
                 sites, offs = (TcDwFold * n)(), (C.c_longlong * n)()
                 nf = int(L.tc_ffn_mid_plan(segs, n, Gn, self.dt, sites, offs))
@@ -1047,7 +918,7 @@ class Graph:
                     sf.dw, sf.db, sf.dgamma, sf.dbeta = _ptr(t["wd"].grad), _ptr(t["bd"].grad), _ptr(t["lg"].grad), _ptr(t["lb"].grad)
                     self._dw_pending.append((sf, part))
             else:
-                ws = _workspace(self.dev, self.stream)
+                ws = _workspace(self.dev)
                 _timed("hbm:ffn_mid_bwd (MixFFN LayerNorm backward + dw3x3 input/weight gradients)",
                        sum(4.0 * t["x"].rows * t["C4"] * t["h"].element_size() for t in st),
                        lambda: L.tc_ffn_mid_bwd(segs, n, Gn, gs, ws.data_ptr(), ws.numel(), self.dt, self.stream))
@@ -1088,7 +959,7 @@ class Graph:
         the op-by-op path, which handles any subset."""
         if self.record and (not t.requires_grad or (params is not None and any(p.grad is None for p in params))):
             return False
-        return (_EFFATT_FUSED and self.ngroups == 1 and not self.use_streams and self.dt != TC_F32
+        return (_EFFATT_FUSED and self.ngroups == 1 and self.dt != TC_F32
                 and bool(self.L.tc_effatt_supported(t.cols, self.dt)) and t.data.is_contiguous())
 
     def eff_attention_block(self, t: Var, ln: Tuple[P, P], keys: Tuple[P, P], queries: Tuple[P, P], values: Tuple[P, P],
@@ -1159,8 +1030,8 @@ class Graph:
             if dy is None or not x.requires_grad:
                 return
             gx, acc = self.wgrad(x)
-            fused = g.grad is not None and not (self.overlap_wgrad and self.use_streams)
-            nblk = int(self.L.tc_layernorm_bwd_nblk(rows, Cc)) if (fused and _LN_DEFER and not self.use_streams) else 0
+            fused = g.grad is not None
+            nblk = int(self.L.tc_layernorm_bwd_nblk(rows, Cc)) if (fused and _LN_DEFER) else 0
             if nblk > 0:                                 # dx + per-workgroup dgamma / dbeta partials; the partials of ALL LayerNorms of a backward
                 nf = Gn * nblk * 2 * Cc                  # leg are added up by one launch when the leg ends (_flush_param_folds)
                 part = self.f32(nf)
@@ -1173,20 +1044,16 @@ class Graph:
                     self._flush_param_folds()
                 return
             if fused:                                    # one pass: dx + per-workgroup dgamma/dbeta partials + a tiny folding launch
-                ws = _workspace(self.dev, self.stream)
+                ws = _workspace(self.dev)
                 scratch, n = ws, ws.numel() // 4
                 _timed("hbm:layernorm_bwd", (3.0 + acc) * x.rows * Cc * es, lambda: self.L.tc_layernorm_bwd(
                     _ptr(dy), dy.stride(0), _ptr(x.data), x.ld, _ptr(g.data), _ptr(b.data), _ptr(mean), _ptr(rstd), _ptr(gx), gx.stride(0),
                     _ptr(gx) if acc else None, gx.stride(0), _ptr(g.grad), _ptr(b.grad), rows, Cc, act, Gn, g.gs, _ptr(scratch), n, self.dt,
                     self.stream))
                 return
-            self.L.tc_layernorm_bwd(_ptr(dy), dy.stride(0), _ptr(x.data), x.ld, _ptr(g.data), _ptr(b.data), _ptr(mean),
+            self.L.tc_layernorm_bwd(_ptr(dy), dy.stride(0), _ptr(x.data), x.ld, _ptr(g.data), _ptr(b.data), _ptr(mean),      # (frozen gamma / beta: dx alone)
                                     _ptr(rstd), _ptr(gx), gx.stride(0), _ptr(gx) if acc else None, gx.stride(0),
                                     None, None, rows, Cc, act, Gn, g.gs, None, 0, self.dt, self.stream)
-            if g.grad is not None:
-                self._weight_grad(lambda: self.L.tc_layernorm_bwd_params(
-                    _ptr(dy), dy.stride(0), _ptr(x.data), x.ld, _ptr(g.data), _ptr(b.data), _ptr(mean), _ptr(rstd), _ptr(g.grad),
-                    _ptr(b.grad), rows, Cc, act, Gn, g.gs, self.dt, self.stream), reads=dy)
         self._rec(bwd)
         return out
 
@@ -1209,7 +1076,7 @@ class Graph:
                 return
             gx, acc = self.wgrad(x)
             assert not acc, "the expanded map has one consumer"
-            ws = _workspace(self.dev, self.stream)
+            ws = _workspace(self.dev)
             _timed("hbm:layernorm_bwd", 3.0 * rows * c * es, lambda: self.L.tc_layernorm_ps_bwd(
                 _ptr(dy), dy.stride(0), _ptr(x.data), x.ld, _ptr(g.data), _ptr(b.data), _ptr(mean), _ptr(rstd), _ptr(gx), gx.stride(0),
                 _ptr(g.grad), _ptr(b.grad), B, H, W, p, c, _ptr(ws) if g.grad is not None else None, ws.numel() // 4, self.dt, self.stream))
@@ -1220,7 +1087,7 @@ class Graph:
         c = x.cols // max(p * p, 1)
         if p >= 2 and B * H * p * W * p * max(H, W) * p >= 1 << 32:        # the kernels' pixel-shuffle addressing divides by multiplication (csrc/lncls.hip, ps_map)
             return False
-        return (_LN_CLS_FUSED and self.dt != TC_F32 and self.ngroups == 1 and not self.use_streams and bc is not None and x.ld % 8 == 0
+        return (_LN_CLS_FUSED and self.dt != TC_F32 and self.ngroups == 1 and bc is not None and x.ld % 8 == 0
                 and all(q.data.data_ptr() % 16 == 0 for q in (x, g, b, Wc)) and Wc.data.is_contiguous() and Wc.data.shape[1] == c
                 and bool(self.L.tc_ln_cls_supported(c, Wc.data.shape[0], self.dt)))
 
@@ -1258,7 +1125,7 @@ class Graph:
     def linear_ln_supported(self, x: Var, W: P, residual: Optional[Var], *params: P) -> bool:
         """params: the bias / gamma / beta the call will pass (their 16-byte alignment is the kernel's: it loads them as whole 8-element pieces)"""
         Cc = x.cols
-        return (all(q.data.data_ptr() % 16 == 0 for q in params) and _LIN_LN_FUSED and self.dt != TC_F32 and not self.use_streams and tuple(W.data.shape) == (Cc, Cc) and W.data.is_contiguous()
+        return (all(q.data.data_ptr() % 16 == 0 for q in params) and _LIN_LN_FUSED and self.dt != TC_F32 and tuple(W.data.shape) == (Cc, Cc) and W.data.is_contiguous()
                 and x.ld % 8 == 0 and x.data.data_ptr() % 16 == 0 and (residual is None or (residual.ld % 8 == 0 and residual.data.data_ptr() % 16 == 0))
                 and (self.ngroups == 1 or self.pgs % 8 == 0) and bool(self.L.tc_linear_ln_supported(Cc, self.dt)))
 
@@ -1282,7 +1149,7 @@ class Graph:
         return t, xn
 
     def dw_ln_supported(self, x: Var) -> bool:
-        return (_DW_LN_FUSED and self.dt != TC_F32 and not self.use_streams and x.ld % 8 == 0 and x.data.data_ptr() % 16 == 0
+        return (_DW_LN_FUSED and self.dt != TC_F32 and x.ld % 8 == 0 and x.data.data_ptr() % 16 == 0
                 and (self.pgs % 8 == 0 or self.ngroups == 1) and bool(self.L.tc_dw_ln_supported(x.cols, self.dt)))
 
     def dw_ln(self, x: Var, w: P, b: P, g: P, beta: P, B: int, H: int, W: int, eps: float) -> Tuple[Var, Var]:
@@ -1317,13 +1184,13 @@ class Graph:
             dy = self.grad_of(out)
             if dy is None:
                 return
-            if x.requires_grad and w.grad is not None and stride == 1 and _DW_BWD_ONE and not (self.overlap_wgrad and self.use_streams):
+            if x.requires_grad and w.grad is not None and stride == 1 and _DW_BWD_ONE:
                 gx, acc = self.wgrad(x)                       # both gradients in one launch (they share dy and nothing else)
                 vec = 16 // es
                 from ._lib import TcDwFold
                 site = TcDwFold()
                 nf = (int(self.L.tc_dwconv_bwd_plan(B, H, W, Cc, k, Gn, self.dt, C.byref(site)))
-                      if (_DW_DEFER and not self.use_streams and not (x.ld % vec or dy.stride(0) % vec or gx.stride(0) % vec or _ptr(dy) % 16 or _ptr(x.data) % 16 or _ptr(gx) % 16))
+                      if (_DW_DEFER and not (x.ld % vec or dy.stride(0) % vec or gx.stride(0) % vec or _ptr(dy) % 16 or _ptr(x.data) % 16 or _ptr(gx) % 16))
                       else 0)
                 if nf > 0:                                    # the walkers' sums parked in a buffer of this launch's own; one tc_dw_fold per backward leg
                     part = self.f32(nf)
@@ -1334,7 +1201,7 @@ class Graph:
                     site.part, site.dw, site.db, site.wstride = _ptr(part), _ptr(w.grad), _ptr(b.grad) if b is not None else None, w.gs
                     self._dw_pending.append((site, part))
                     return
-                ws = _workspace(self.dev, self.stream)
+                ws = _workspace(self.dev)
                 _timed("hbm:dwconv_bwd (input + weight gradient, one launch)", (2.0 * x.rows * (1 + acc) + 2.0 * out.rows) * Cc * es,
                        lambda: self.L.tc_dwconv_bwd(_ptr(dy), dy.stride(0), _ptr(x.data), x.ld, _ptr(w.data), _ptr(gx), gx.stride(0), _ptr(w.grad),
                                                     _ptr(b.grad) if b is not None else None, B, H, W, Cc, k, int(add_input), acc, Gn, w.gs,
@@ -1346,12 +1213,10 @@ class Graph:
                     _ptr(dy), dy.stride(0), _ptr(w.data), _ptr(gx), gx.stride(0), B, H, W, Cc, k, stride, int(add_input), acc, Gn, w.gs,
                     self.dt, self.stream))
             if w.grad is not None:
-                def dwgrad():
-                    ws = _workspace(self.dev, self.stream)           # of the stream this actually runs on
-                    _timed("hbm:dwconv_bwd_weight", (x.rows + out.rows) * Cc * es, lambda: self.L.tc_dwconv_bwd_weight(
-                        _ptr(dy), dy.stride(0), _ptr(x.data), x.ld, _ptr(w.grad), _ptr(b.grad) if b is not None else None, B, H, W, Cc, k,
-                        stride, Gn, w.gs, ws.data_ptr(), ws.numel(), self.dt, self.stream))
-                self._weight_grad(dwgrad, reads=dy)
+                ws = _workspace(self.dev)
+                _timed("hbm:dwconv_bwd_weight", (x.rows + out.rows) * Cc * es, lambda: self.L.tc_dwconv_bwd_weight(
+                    _ptr(dy), dy.stride(0), _ptr(x.data), x.ld, _ptr(w.grad), _ptr(b.grad) if b is not None else None, B, H, W, Cc, k,
+                    stride, Gn, w.gs, ws.data_ptr(), ws.numel(), self.dt, self.stream))
         self._rec(bwd)
         return out
 
@@ -1384,15 +1249,14 @@ class Graph:
                 assert all(d is None for d in dys)
                 return
             ldd = [d.stride(0) for d in dys]
-            if xs[0].requires_grad and ws[0].grad is not None and _DW_BWD_ONE and not (self.overlap_wgrad and self.use_streams):
+            if xs[0].requires_grad and ws[0].grad is not None and _DW_BWD_ONE:
                 g = [self.wgrad(x) for x in xs]                   # input and weight gradients of all segments in one launch
                 acc = g[0][1]
                 assert all(a == acc for _, a in g)
                 sg = segs([_ptr(x.data) for x in xs], wd, none, [_ptr(t) for t, _ in g], [_ptr(d) for d in dys],
                           [_ptr(w.grad) for w in ws], [_ptr(b.grad) if b is not None else None for b in bs],
                           [x.ld for x in xs], [t.stride(0) for t, _ in g], ldd)
-                if _DW_DEFER and not self.use_streams:         # the walkers' sums parked; one tc_dw_fold per backward leg (single-stream sweeps only:
-                    #                                            a fold issued on one branch stream must not read a sibling branch's unfinished sums)
+                if _DW_DEFER:                                     # the walkers' sums parked; one tc_dw_fold per backward leg
                     from ._lib import TcDwFold
                     sites, offs = (TcDwFold * n)(), (C.c_longlong * n)()
                     nf = int(self.L.tc_dwconv_multi_plan(sg, n, Gn, self.dt, sites, offs))
@@ -1406,7 +1270,7 @@ class Graph:
                             st.db = _ptr(bs[i].grad) if bs[i] is not None else None
                             self._dw_pending.append((st, part))
                         return
-                wk = _workspace(self.dev, self.stream)
+                wk = _workspace(self.dev)
                 self.L.tc_dwconv_multi(sg, n, 3, int(add_input), acc, Gn, gs, wk.data_ptr(), wk.numel(), self.dt, self.stream)
                 return
             if xs[0].requires_grad:
@@ -1417,13 +1281,11 @@ class Graph:
                                             [t.stride(0) for t, _ in g], zero), n, 1, int(add_input), acc, Gn, gs, None, 0, self.dt,
                                        self.stream)
             if ws[0].grad is not None:
-                def dwgrad():
-                    wk = _workspace(self.dev, self.stream)
-                    self.L.tc_dwconv_multi(segs([_ptr(x.data) for x in xs], none, none, none, [_ptr(d) for d in dys],
-                                                [_ptr(w.grad) for w in ws], [_ptr(b.grad) if b is not None else None for b in bs],
-                                                [x.ld for x in xs], zero, ldd), n, 2, 0, 0, Gn, gs, wk.data_ptr(), wk.numel(), self.dt,
-                                           self.stream)
-                self._weight_grad(dwgrad, reads=dys[0])
+                wk = _workspace(self.dev)
+                self.L.tc_dwconv_multi(segs([_ptr(x.data) for x in xs], none, none, none, [_ptr(d) for d in dys],
+                                            [_ptr(w.grad) for w in ws], [_ptr(b.grad) if b is not None else None for b in bs],
+                                            [x.ld for x in xs], zero, ldd), n, 2, 0, 0, Gn, gs, wk.data_ptr(), wk.numel(), self.dt,
+                                       self.stream)
         self._rec(bwd)
         return outs
 
@@ -1467,7 +1329,7 @@ class Graph:
         return out
 
     def ripm_supported(self, m: Var) -> bool:
-        return (_RIPM_FUSED and self.dt != TC_F32 and not self.use_streams and self.ngroups == 1 and m.ld % 8 == 0
+        return (_RIPM_FUSED and self.dt != TC_F32 and self.ngroups == 1 and m.ld % 8 == 0
                 and m.data.data_ptr() % 16 == 0 and bool(self.L.tc_ripm_supported(m.cols, self.dt)))
 
     def ripm_stage(self, m: Var, steps: List[dict], B: int, side: int, stack: Var) -> int:
@@ -1531,7 +1393,7 @@ class Graph:
         """out[b] = alpha * op(A[b]) op(B[b]); A/B/out are 2-D views whose data pointer is batch (0,0)."""
         assert not (tA and tB)
         # few output tiles with a long reduction (token-reduced context matrices): tc_gemm splits K itself and folds the
-        # partials in-kernel through the per-stream workspace
+        # partials in-kernel through the workspace
         self._gemm(_ptr(A.data), A.ld, _ptr(B.data), B.ld, _ptr(out.data), out.ld, M, N, K, tA, tB, alpha=alpha, nb1=nb1,
                    nb2=nb2, sA=sA, sB=sB, sC=sC)
 
@@ -1571,7 +1433,7 @@ class Graph:
         MSTr.py:1404 crpe_window): anything else takes the op-by-op form."""
         if heads != 8 or (windows is not None and [tuple(w_) for w_ in windows] != [(3, 2), (5, 3), (7, 3)]):
             return False
-        return (_MHCA_ATT_FUSED and self.dt != TC_F32 and not self.use_streams and n.ld % 8 == 0 and n.data.data_ptr() % 16 == 0
+        return (_MHCA_ATT_FUSED and self.dt != TC_F32 and n.ld % 8 == 0 and n.data.data_ptr() % 16 == 0
                 and (self.pgs % 8 == 0 or self.ngroups == 1) and bool(self.L.tc_mhca_att_supported(n.cols, N, self.dt)))
 
     def mhca_attention(self, n: Var, Wqkv: P, bqkv: P, cws: List[P], cbs: List[P], B: int, side: int, heads: int, scale: float,

@@ -17,7 +17,7 @@ import torch
 import torch.nn as nn
 
 from .engine import Graph, Var
-from .model import (DIMS, FUSED_MIXFFN, MSTransception, _decoders, _eff_block, _lin, _ln, _mixffn, _mixffn_plain, _mixffn_site, _mk_decoder_layer,
+from .model import (DIMS, MSTransception, _decoders, _eff_block, _lin, _ln, _mixffn_plain, _mixffn_site, _mk_decoder_layer,
                     _mk_eff_block, _mk_mixffn, _mk_mixffn_skip, _proj_ln, _sk_block)
 
 SIZE = 224
@@ -192,11 +192,8 @@ def _fuse_block(M, G: Graph, x: Var, name: str, B: int, g1: int, g2: int) -> Var
     if M.token_mlp_mode == "mix":
         for a0, a1, g, mlp in parts:
             _mixffn_plain(M, G, nx.rowslice(a0, a1), name + mlp, B, g, g, tx.rowslice(a0, a1), out=out.rowslice(a0, a1))
-    elif FUSED_MIXFFN and not G.use_streams:                            # both branches' MixFFN_skip as one site list
+    else:                                                               # both branches' MixFFN_skip as one site list
         G.mixffn([_mixffn_site(M, G, nx.rowslice(a0, a1), name + mlp, B, g, g, tx.rowslice(a0, a1), out.rowslice(a0, a1)) for a0, a1, g, mlp in parts])
-    else:
-        for a0, a1, g, mlp in parts:
-            _mixffn(M, G, nx.rowslice(a0, a1), name + mlp, B, g, g, tx.rowslice(a0, a1), out=out.rowslice(a0, a1))
     return out
 
 

@@ -757,16 +757,13 @@ def _lin(M: MSTransception, G: Graph, name: str, bias: bool = True):
     return W, b
 
 
-_PAIR_GROUPED = os.environ.get("TC_PAIR_GROUPED", "1") != "0"       # A/B switch of _lin_pair
-
-
 def _lin_pair(M: MSTransception, G: Graph, a: str, b: str):
     """(W, bias, stride) of two same-shaped Linear / 1x1 layers as TWO WEIGHT GROUPS of one launch (Graph.grouped(2, stride)) -- or None when
     their parameters do not sit at one constant, 16-byte-aligned distance in the flat arenas."""
     (oa, sa), (ob, sb) = M._index[a + ".weight"], M._index[b + ".weight"]
     (ba, sba), (bb, sbb) = M._index[a + ".bias"], M._index[b + ".bias"]
     stride = ob - oa
-    if sa != sb or sba != sbb or bb - ba != stride or stride <= 0 or stride % 8 or oa % 8 or ba % 8 or not _PAIR_GROUPED:
+    if sa != sb or sba != sbb or bb - ba != stride or stride <= 0 or stride % 8 or oa % 8 or ba % 8:
         return None
     W, bias = _lin(M, G, a)
     if G.record:
@@ -791,9 +788,6 @@ def _bn(M, G, x, name, act, residual=None, out=None):
                        residual, out)
 
 
-FUSED_MIXFFN = os.environ.get("TC_FUSED_MIXFFN", "1") != "0"
-
-
 def _mixffn_site(M, G, x, name, B, H, W, residual, out=None, pre_ln=None) -> dict:
     return dict(pre_ln=pre_ln, x=x, fc1=_lin(M, G, name + ".fc1"), dw=(M._P(G, name + ".dwconv.dwconv.weight"), M._P(G, name + ".dwconv.dwconv.bias")),
                 ln=(M._P(G, name + ".norm1.weight"), M._P(G, name + ".norm1.bias")), fc2=_lin(M, G, name + ".fc2"), geo=(B, H, W),
@@ -804,7 +798,7 @@ def _mixffn(M, G, x, name, B, H, W, residual, out=None, pre_ln=None):
     """MixFFN_skip, MSTr.py:889-902 (fc1 evaluated once): fc2(GELU(LN(dw3x3(h) + h))) + residual.
     pre_ln = (norm name, eps): the site's input is LayerNorm(x) -- the block's norm2 -- which the tiled kernels apply themselves."""
     pl = (M._P(G, pre_ln[0] + ".weight"), M._P(G, pre_ln[0] + ".bias"), pre_ln[1]) if pre_ln is not None else None
-    if FUSED_MIXFFN and not G.use_streams and x.data.is_contiguous():
+    if x.data.is_contiguous():
         return G.mixffn([_mixffn_site(M, G, x, name, B, H, W, residual, out, pl)])[0]     # 3 + 3 launches (engine.Graph.mixffn)
     if pl is not None:
         x = G.layernorm(x, *pl)
@@ -829,7 +823,7 @@ def _eff_attention(M, G, n1: Var, name: str, B: int, N: int, residual: Optional[
     kqv = G.new(rows, 3 * C, covered=True)         # k, q, v gradients (softmax / softmax / bmm backward) cover it
     k, q, v = kqv.colslice(0, C), kqv.colslice(C, 2 * C), kqv.colslice(2 * C, 3 * C)
     lk, lq, lv = _lin(M, G, name + ".keys"), _lin(M, G, name + ".queries"), _lin(M, G, name + ".values")
-    if MULTI_QKV and C % 64 == 0 and G.ngroups == 1:
+    if C % 64 == 0 and G.ngroups == 1:
         G.linear_multi(n1, [lk[0], lq[0], lv[0]], [lk[1], lq[1], lv[1]], kqv)       # the three 1x1 convs in one batched GEMM
     else:
         G.linear(n1, *lk, out=k)
@@ -894,13 +888,6 @@ def _resblock(M, G, x: Var, name: str, B: int, side: int, out: Var) -> Var:
     return _bn(M, G, f, name + ".conv2.bn", ACT_NONE, residual=x, out=out)
 
 
-MANY_MIXFFN = os.environ.get("TC_MANY_MIXFFN", "1") != "0"
-MULTI_QKV = os.environ.get("TC_MULTI_QKV", "1") != "0"
-MULTI_CRPE = os.environ.get("TC_MULTI_CRPE", "1") != "0"
-FUSED_FACTOR_ATT = os.environ.get("TC_FACTOR_ATT_FUSED", "1") != "0"
-SHUFFLE_IN_LN = os.environ.get("TC_SHUFFLE_IN_LN", "1") != "0"
-
-
 def _factor_att(M, G, n: Var, blk: str, enc: str, B: int, side: int, residual: Optional[Var] = None, ln=None):
     """FactorAtt_ConvRelPosEnc + ConvRelPosEnc, MSTr.py:852-886, 801-823 (Appendix C.1-2), + residual add.
     ln = (norm name, eps): also return LayerNorm(result) -- the block's norm2 -- from the same launch as `proj` where the library has it
@@ -908,11 +895,11 @@ def _factor_att(M, G, n: Var, blk: str, enc: str, B: int, side: int, residual: O
     C, N = n.cols, side * side
     Bt = B * G.ngroups                              # images of all stacked weight groups
     rows, h, Ch = Bt * N, HEADS, n.cols // HEADS
-    if FUSED_FACTOR_ATT and MULTI_CRPE and Ch % 8 == 0 and G.mhca_att_supported(n, N, h, list(CRPE_WINDOW)):     # qkv + crpe + attention core: one launch
+    if Ch % 8 == 0 and G.mhca_att_supported(n, N, h, list(CRPE_WINDOW)):     # qkv + crpe + attention core: one launch
         o = G.mhca_attention(n, *_lin(M, G, blk + ".factoratt_crpe.qkv"), [M._P(G, f"{enc}.crpe.conv_list.{i}.weight") for i in range(3)],
                              [M._P(G, f"{enc}.crpe.conv_list.{i}.bias") for i in range(3)], B, side, h, Ch ** -0.5, list(CRPE_WINDOW))
         return _proj_ln(M, G, o, blk + ".factoratt_crpe.proj", residual, ln)
-    qkv = G.linear(n, *_lin(M, G, blk + ".factoratt_crpe.qkv"), out=G.new(n.rows, 3 * C, covered=FUSED_FACTOR_ATT))
+    qkv = G.linear(n, *_lin(M, G, blk + ".factoratt_crpe.qkv"), out=G.new(n.rows, 3 * C, covered=True))
     q, k, v = qkv.colslice(0, C), qkv.colslice(C, 2 * C), qkv.colslice(2 * C, 3 * C)
     convv = G.new(rows, C)
     c0, xs, outs, wts, bss, kss = 0, [], [], [], [], []
@@ -921,14 +908,10 @@ def _factor_att(M, G, n: Var, blk: str, enc: str, B: int, side: int, residual: O
         xs.append(v.colslice(c0, c0 + w)); outs.append(convv.colslice(c0, c0 + w)); kss.append(ksz)
         wts.append(M._P(G, f"{enc}.crpe.conv_list.{i}.weight")); bss.append(M._P(G, f"{enc}.crpe.conv_list.{i}.bias"))
         c0 += w
-    if MULTI_CRPE:
-        G.dwconv_multi(xs, wts, bss, (B, side, side), kss, outs)           # the three window sizes in one launch
-    else:
-        for x_, w_, b_, k_, o_ in zip(xs, wts, bss, kss, outs):
-            G.dwconv(x_, w_, b_, B, side, side, k_, 1, False, out=o_)
-    if FUSED_FACTOR_ATT and Ch % 8 == 0 and 16 * N * Ch + 8 * Ch * Ch + 1024 <= 150 * 1024:     # a head's q, k, v, do tiles fit LDS in fp32
+    G.dwconv_multi(xs, wts, bss, (B, side, side), kss, outs)               # the three window sizes in one launch
+    if Ch % 8 == 0 and 16 * N * Ch + 8 * Ch * Ch + 1024 <= 150 * 1024:     # a head's q, k, v, do tiles fit LDS in fp32
         o = G.factor_att_core(q, k, v, convv, Bt, N, h, Ch ** -0.5)
-    else:                                           # unfused composition: larger inputs (384^2: 2304 tokens at stage 2), A/B tests
+    else:                                           # unfused composition: larger inputs (384^2: 2304 tokens at stage 2)
         ksm = G.softmax(k, Bt, 0)
         ctx = G.new(Bt * h * Ch, Ch)
         G.bmm(ksm, v, ctx, Ch, Ch, N, 1, 0, nb1=Bt, nb2=h, sA=(N * C, Ch), sB=(N * 3 * C, Ch), sC=(h * Ch * Ch, Ch * Ch))
@@ -990,16 +973,13 @@ def _mhca_stage(M, G, stack: Var, name: str, layers: int, B: int, side: int, out
     gs = M._path_stride(name, npath)
     enc = f"{name}.mhca_blks.0"
     stg = name[-1]
-    with G.parallel(2) as par:
-        with par.branch(0):
-            G.segment("mb" + stg)
-            with G.grouped(npath, gs):
-                t = stack
-                for l in range(layers):
-                    t = _mhca_block(M, G, t, f"{enc}.MHCA_layers.{l}", enc, B, side, cat.colslice(C, (npath + 1) * C) if l == layers - 1 else None)
-        with par.branch(1):
-            G.segment("res" + stg)
-            _resblock(M, G, stack.rowslice(0, rows), name + ".InvRes", B, side, cat.colslice(0, C))
+    G.segment("mb" + stg)
+    with G.grouped(npath, gs):
+        t = stack
+        for l in range(layers):
+            t = _mhca_block(M, G, t, f"{enc}.MHCA_layers.{l}", enc, B, side, cat.colslice(C, (npath + 1) * C) if l == layers - 1 else None)
+    G.segment("res" + stg)
+    _resblock(M, G, stack.rowslice(0, rows), name + ".InvRes", B, side, cat.colslice(0, C))
     G.segment("iff" + stg)
     if M.concat == "coord":
         return _coord_att(M, G, cat, name + ".aggregate", B, side, out)
@@ -1102,13 +1082,9 @@ def _channel_att(M, G, n: Var, X: Optional[Var], name: str, B: int, ntok: List[i
         Wb = _lin(M, G, f"{name}.{key}")
         for s in range(4):
             xs_, os_ = n.rowslice(R[s], R[s] + ntok[s]), buf.rowslice(offs[s], offs[s] + ntok[s])
-            if MANY_MIXFFN and not G.use_streams:
-                many.append((xs_, Wb[0], Wb[1], os_, None, (B, ntok[s] * Cd, N6 * Cd, 0)))
-            else:
-                G.linear(xs_, *Wb, out=os_, batch=(B, ntok[s] * Cd, N6 * Cd, 0))
+            many.append((xs_, Wb[0], Wb[1], os_, None, (B, ntok[s] * Cd, N6 * Cd, 0)))
         imgs[key] = buf.reshape(B * Cd, N6)
-    if many:
-        G.linear_many(many)                                     # 3 projections x 4 scales: one launch (and two for the gradients)
+    G.linear_many(many)                                         # 3 projections x 4 scales: one launch (and two for the gradients)
     ksm = G.softmax(imgs["k"], 1, 1)
     qsm = G.softmax(imgs["q"], B, 0)
     ctx = G.new(B * Cd, Cd)
@@ -1122,13 +1098,8 @@ def _channel_att(M, G, n: Var, X: Optional[Var], name: str, B: int, ntok: List[i
     for s in range(4):
         xs_, os_ = o_img.rowslice(offs[s], offs[s] + ntok[s]), tx1.rowslice(R[s], R[s] + ntok[s])
         rs_ = X.rowslice(R[s], R[s] + ntok[s]) if X is not None else None
-        bt = (B, N6 * Cd, ntok[s] * Cd, ntok[s] * Cd)
-        if MANY_MIXFFN and not G.use_streams:
-            many.append((xs_, Wp[0], Wp[1], os_, rs_, bt))
-        else:
-            G.linear(xs_, *Wp, out=os_, residual=rs_, batch=bt)
-    if many:
-        G.linear_many(many)
+        many.append((xs_, Wp[0], Wp[1], os_, rs_, (B, N6 * Cd, ntok[s] * Cd, ntok[s] * Cd)))
+    G.linear_many(many)
     return tx1
 
 
@@ -1141,11 +1112,11 @@ def _scale_reduce(M, G, n: Var, name: str, B: int, sides: List[int], ntok: List[
     Nk = Pn * 8 + ntok[3]
     red = G.new(B * Nk, Cd)                                     # image-major K/V source
     pitems = [(R[s] * Cd, sides[s] * sides[s] * Cd * MULT[s], B, sides[s], sides[s], Cd * MULT[s], SR_K[s]) for s in range(3)]
-    merged = MANY_MIXFFN and not G.use_streams and G.ngroups == 1     # the layout moves of the three scales share launches
+    merged = G.ngroups == 1     # the layout moves of the three scales share launches
     cols = G.patchify_many(n, pitems) if merged else [G.patchify(n, *it) for it in pitems]
     lins = [_lin(M, G, f"{name}.sr{s}") for s in range(3)]
     xo = None
-    if MANY_MIXFFN and not G.use_streams and G.ngroups == 1:
+    if merged:
         items = [(cols[s], lins[s][0], lins[s][1], G.new(cols[s].rows, lins[s][0].data.shape[0]), None) for s in range(3)]
         if extra is not None:
             items.append((extra[0], extra[1], extra[2], G.new(extra[0].rows, extra[1].data.shape[0]), None, None, extra[3]))
@@ -1205,25 +1176,8 @@ def _bridge_layer(M, G, X: Var, li: int, B: int, sides, ntok, R, N6) -> Var:
     tx2 = G.new(B * N6, 64)
     geo = [(B * sides[s] * sides[s], 64 * MULT[s]) for s in range(4)]
     view = lambda v, s: v.rowslice(R[s], R[s + 1]).reshape(*geo[s])
-    if FUSED_MIXFFN and MANY_MIXFFN and not G.use_streams:
-        # the four per-scale MixFFNs as ONE fused site list: 3 forward + 3 backward launches for all four scales
-        G.mixffn([_mixffn_site(M, G, view(tx, s), f"{name}.mixffn{s + 1}", B, sides[s], sides[s], view(tx1, s), view(tx2, s)) for s in range(4)])
-        return tx2
-    if MANY_MIXFFN and not G.use_streams:
-        # the four per-scale MixFFNs level by level: fc1 x4 in one launch, dw x4, LN x4, fc2 x4 in one launch (and the eight
-        # gradient GEMMs of each level in one launch): four independent chains of small kernels share the CUs
-        nm = [f"{name}.mixffn{s + 1}" for s in range(4)]
-        hs = G.linear_many([(view(tx, s), *_lin(M, G, nm[s] + ".fc1"), G.new(geo[s][0], 4 * geo[s][1]), None) for s in range(4)])
-        ds = G.dwconv_multi(hs, [M._P(G, nm[s] + ".dwconv.dwconv.weight") for s in range(4)],
-                            [M._P(G, nm[s] + ".dwconv.dwconv.bias") for s in range(4)], [(B, sides[s], sides[s]) for s in range(4)],
-                            [3] * 4, [None] * 4, add_input=True)
-        acts = [_ln(M, G, ds[s], nm[s] + ".norm1", act=ACT_GELU) for s in range(4)]
-        G.linear_many([(acts[s], *_lin(M, G, nm[s] + ".fc2"), view(tx2, s), view(tx1, s)) for s in range(4)])
-        return tx2
-    with G.parallel(4, shared=(tx, tx1)) as par:    # the four per-scale MixFFNs are independent
-        for s in range(4):
-            with par.branch(s):
-                _mixffn(M, G, view(tx, s), f"{name}.mixffn{s + 1}", B, sides[s], sides[s], residual=view(tx1, s), out=view(tx2, s))
+    # the four per-scale MixFFNs as ONE fused site list: 3 forward + 3 backward launches for all four scales
+    G.mixffn([_mixffn_site(M, G, view(tx, s), f"{name}.mixffn{s + 1}", B, sides[s], sides[s], view(tx1, s), view(tx2, s)) for s in range(4)])
     return tx2
 
 
@@ -1232,9 +1186,8 @@ def _patch_expand(M, G, t: Var, name: str, B: int, side: int, p: int) -> Var:
     if t.rows != B * side * side:
         raise AssertionError("input feature has wrong size")
     y = G.linear(t, *_lin(M, G, name + ".expand", bias=False))
-    if SHUFFLE_IN_LN:                            # the rearrange is an address computation inside the LayerNorm kernels
-        return G.layernorm_shuffled(y, M._P(G, name + ".norm.weight"), M._P(G, name + ".norm.bias"), B, side, side, p)
-    return _ln(M, G, G.pixel_shuffle(y, B, side, side, p), name + ".norm")
+    # the rearrange is an address computation inside the LayerNorm kernels
+    return G.layernorm_shuffled(y, M._P(G, name + ".norm.weight"), M._P(G, name + ".norm.bias"), B, side, side, p)
 
 
 def _decoder(M, G, x1: Var, skip: Var, name: str, B: int, side: int, last: bool) -> Var:
@@ -1254,11 +1207,11 @@ def _decoder(M, G, x1: Var, skip: Var, name: str, B: int, side: int, last: bool)
     Wc, bc = _lin(M, G, name + ".last_layer")
     gn, bn = M._P(G, up + ".norm.weight"), M._P(G, up + ".norm.bias")
     ye = G.linear(t, *_lin(M, G, up + ".expand", bias=False))       # FinalPatchExpand_X4.expand, MSTr.py:219-221
-    if SHUFFLE_IN_LN and G.ln_cls_supported(ye, 4, gn, bn, Wc, bc, B, side, side):
+    if G.ln_cls_supported(ye, 4, gn, bn, Wc, bc, B, side, side):
         # rearrange + norm of FinalPatchExpand_X4 and last_layer in one launch each way (csrc/lncls.hip): the normalised 224^2 x 64 map is never stored
         lg = G.ln_cls(ye, gn, bn, Wc, bc, B, side, side, 4, pad_rows=tok)
     else:
-        y = G.layernorm_shuffled(ye, gn, bn, B, side, side, 4) if SHUFFLE_IN_LN else _ln(M, G, G.pixel_shuffle(ye, B, side, side, 4), up + ".norm")
+        y = G.layernorm_shuffled(ye, gn, bn, B, side, side, 4)
         lg = G.linear(y, Wc, bc)                                # [B*16*side^2, classes]
     if tok:
         return lg                                               # token-major for the captured step's loss kernels
