@@ -642,6 +642,40 @@ int tc_factor_att_bwd(const void* q, const void* k, const void* v, int ld, const
 int tc_argmax_counts(const void* logits, const long long* labels, unsigned char* pred, float* counts, int B, int ncls, int HW,
                      int dtype, void* stream);
 
+/* Evaluation metrics on the device (csrc/metrics.hip): the integer side of calculate_metric_percase (utils.py:50-60, called per class at
+ * utils.py:96-98: medpy's dc and hd95 with defaults, i.e. unit voxel spacing, connectivity 1) for a predicted label volume against a
+ * ground-truth one, both uint8 [D,H,W] in HBM.  Definition, as oracle.transception_oracle.eval_hd95 states it:
+ *   - surface voxel of a mask = mask voxel with at least one of its 6 face neighbours outside the mask, the outside of the array counting
+ *     as background (scipy binary_erosion, border_value 0), so every mask voxel of a [1,H,W] volume is on its surface;
+ *   - for every surface voxel of A the Euclidean distance to the nearest surface voxel of B, and the other way round, both lists pooled;
+ *   - HD95 = numpy.percentile(pooled, 95), linear interpolation between the two neighbouring order statistics;
+ *   - utils.py:53-60: both masks non-empty -> (dice, hd95); only the prediction non-empty -> (1, 0); else (0, 0)  (the host applies it).
+ * Squared distances are integers, so all of it is exact int32 work with integer atomics: bit-identical from run to run.
+ * Limits (TC_ERR_ARG beyond them, as for null pointers; nothing is launched): D, H, W in 1..2048, D*H*W < 2^31, ncls in 1..16,
+ * class k in 1..15 (and k < ncls where ncls is passed).  zfaces = 1 is a 3-D volume; zfaces = 0 treats every z-slice as a 2-D image of
+ * its own (no z neighbours, no z pass): what an [H,W] pair means to hd95, passed with D = 1.
+ *
+ * tc_metric_surfaces: surf[v] = lab[v] if v is a surface voxel of class lab[v] (1 <= lab[v] < ncls), else 0, for both volumes (uint8
+ *   [D,H,W] each, OVERWRITTEN), and counts[3k..3k+2] += (|P==k & G==k|, |P==k|, |G==k|) for k < ncls: int64, ACCUMULATED -- the caller
+ *   zeroes them (the same rule as tc_argmax_counts).
+ * tc_metric_edt: d2[v] = squared Euclidean distance from v to the nearest voxel with surf == k, int32 [D,H,W], OVERWRITTEN; exact
+ *   (separable: nearest source within the row, then min_j f[j] + (i-j)^2 along y and z, in place).  TC_METRIC_NO_SOURCE everywhere when
+ *   no voxel has surf == k (with zfaces = 0: in every slice without one).
+ * tc_metric_hist: hist[k][d2_gt[v]] += 1 for every v with surf_pred[v] == k and hist[k][d2_pred[v]] += 1 for every v with
+ *   surf_gt[v] == k; hist is uint32 [ncls][nbins], ACCUMULATED -- the caller zeroes it; nbins >= tc_metric_hist_bins(D,H,W) =
+ *   (D-1)^2 + (H-1)^2 + (W-1)^2 + 1 (0 for a shape outside the limits).  Distances to an empty surface are not counted.
+ * tc_metric_select: out[3k..3k+2] = (n, d2_lo, d2_hi), int64, OVERWRITTEN for every k < ncls: the pooled count of hist[k] and the squared
+ *   distances at sorted positions floor(0.95 (n-1)) and min(that + 1, n-1); (0, 0, 0) for an empty histogram.  The host forms
+ *   sqrt(d2_lo) + (sqrt(d2_hi) - sqrt(d2_lo)) * (0.95 (n-1) - floor(0.95 (n-1))) in fp64. */
+#define TC_METRIC_NO_SOURCE (1 << 28)
+long long tc_metric_hist_bins(int D, int H, int W);
+int tc_metric_surfaces(const unsigned char* pred, const unsigned char* gt, unsigned char* surf_pred, unsigned char* surf_gt,
+                       long long* counts, int D, int H, int W, int ncls, int zfaces, void* stream);
+int tc_metric_edt(const unsigned char* surf, int k, int* d2, int D, int H, int W, int zfaces, void* stream);
+int tc_metric_hist(const unsigned char* surf_pred, const unsigned char* surf_gt, const int* d2_pred, const int* d2_gt, int k,
+                   unsigned int* hist, long long nbins, int ncls, int D, int H, int W, void* stream);
+int tc_metric_select(const unsigned int* hist, long long nbins, int ncls, long long* out, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Input pipeline (datasets/dataset_synapse.py:101-112, trainer.py:89-93): a batch of raw slices
  * [B,H,W] (image fp32 in [0,1], label uint8 0..8) already in HBM -> network input.

@@ -103,6 +103,7 @@ class TcSliceAug(C.Structure):
 
 TC_AUG_WARP, TC_AUG_LINEAR, TC_AUG_BLUR, TC_AUG_PIECEWISE = 1, 2, 4, 8
 TC_AUG_SKIP, TC_AUG_FROM_RAW = 1 << 20, 1 << 21
+TC_METRIC_NO_SOURCE = 1 << 28          # include/transception_hip.h: tc_metric_edt's value where no voxel has surf == k
 
 # name -> argtypes (every function returns int status unless listed in _RET)
 SIGNATURES = {
@@ -202,6 +203,11 @@ SIGNATURES = {
     "tc_factor_att_fwd": [vp, vp, vp, i32, vp, i32, vp, i32, vp, i32, i32, i32, i32, f32, i32, vp],
     "tc_factor_att_bwd": [vp, vp, vp, i32, vp, i32, vp, i32, vp, vp, vp, vp, i32, i32, i32, i32, vp, i32, i32, i32, i32, i32, f32, i32, vp],
     "tc_argmax_counts": [vp, vp, vp, vp, i32, i32, i32, i32, vp],
+    "tc_metric_hist_bins": [i32, i32, i32],
+    "tc_metric_surfaces": [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp],
+    "tc_metric_edt": [vp, i32, vp, i32, i32, i32, i32, vp],
+    "tc_metric_hist": [vp, vp, vp, vp, i32, vp, i64, i32, i32, i32, i32, vp],
+    "tc_metric_select": [vp, i64, i32, vp, vp],
     "tc_seg_loss_bwd": [vp, vp, vp, vp, i32, i32, i32, f32, f32, f32, f32, vp, i32, vp],
     "tc_seg_loss_fwd_tok": [vp, i32, vp, vp, vp, i32, i32, i32, i32, vp],
     "tc_seg_loss_bwd_tok": [vp, vp, i32, vp, vp, vp, i32, i32, i32, i32, f32, f32, f32, f32, vp, i32, vp],
@@ -232,8 +238,8 @@ SIGNATURES = {
     "tc_mhca_att_bwd": [vp, i32, vp, i32, vp, i32, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, i32, f32, i32, vp],
     "tc_mhca_att_fwd": [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp, i32, vp, i32, vp, i32, vp, i32, i32, i32, i32, i32, f32, i32, vp],
 }
-_RET = {"tc_ln_cls_scratch_floats": i64, "tc_ffn_fused_bwd_scratch_floats": i64, "tc_effatt_scratch_floats": i64, "tc_bn_scratch_floats": i64, "tc_softmax_scratch_floats": i64, "tc_layernorm_bwd_scratch_floats": i64, "tc_dwconv_bwd_plan": i64, "tc_dwconv_multi_plan": i64, "tc_ffn_mid_plan": i64, "tc_factor_att_stats_floats": i64}
-_RAW = {"tc_abi_version", "tc_ln_cls_supported", "tc_ln_cls_scratch_floats", "tc_linear_ln_supported", "tc_ripm_supported", "tc_ripm_tiles", "tc_mhca_att_supported", "tc_dw_ln_supported", "tc_mhca_att_bwd_supported", "tc_effatt_supported", "tc_effatt_scratch_floats", "tc_ffn_chunk", "tc_ffn_fused_supported", "tc_ffn_fused_bwd_supported", "tc_ffn_fused_bwd_scratch_floats", "tc_bn_scratch_floats", "tc_softmax_scratch_floats", "tc_layernorm_bwd_scratch_floats", "tc_layernorm_bwd_nblk", "tc_dwconv_bwd_plan", "tc_dwconv_multi_plan", "tc_ffn_mid_plan", "tc_factor_att_stats_floats"}     # not status-returning
+_RET = {"tc_ln_cls_scratch_floats": i64, "tc_ffn_fused_bwd_scratch_floats": i64, "tc_effatt_scratch_floats": i64, "tc_bn_scratch_floats": i64, "tc_softmax_scratch_floats": i64, "tc_layernorm_bwd_scratch_floats": i64, "tc_dwconv_bwd_plan": i64, "tc_dwconv_multi_plan": i64, "tc_ffn_mid_plan": i64, "tc_factor_att_stats_floats": i64, "tc_metric_hist_bins": i64}
+_RAW = {"tc_abi_version", "tc_ln_cls_supported", "tc_ln_cls_scratch_floats", "tc_linear_ln_supported", "tc_ripm_supported", "tc_ripm_tiles", "tc_mhca_att_supported", "tc_dw_ln_supported", "tc_mhca_att_bwd_supported", "tc_effatt_supported", "tc_effatt_scratch_floats", "tc_ffn_chunk", "tc_ffn_fused_supported", "tc_ffn_fused_bwd_supported", "tc_ffn_fused_bwd_scratch_floats", "tc_bn_scratch_floats", "tc_softmax_scratch_floats", "tc_layernorm_bwd_scratch_floats", "tc_layernorm_bwd_nblk", "tc_dwconv_bwd_plan", "tc_dwconv_multi_plan", "tc_ffn_mid_plan", "tc_factor_att_stats_floats", "tc_metric_hist_bins"}     # not status-returning
 
 
 class TcError(RuntimeError):

@@ -1,0 +1,253 @@
+// Evaluation metrics on the device: the integer side of calculate_metric_percase (utils.py:50-60, called per class at utils.py:96-98) --
+// per-class Dice counts and the exact HD95 order statistics of a predicted label volume against a ground-truth one, both uint8 [D,H,W].
+//
+//   surface voxel of a mask  = mask voxel with at least one of its 6 face neighbours outside the mask, the outside of the array counting as
+//                              background (scipy binary_erosion, connectivity 1, border_value 0);
+//   distance                 = Euclidean, unit spacing, from every surface voxel of one mask to the nearest surface voxel of the other, both
+//                              directions pooled;
+//   HD95                     = numpy.percentile(pooled, 95).
+//
+// With unit spacing every squared distance is an integer, so everything here is int32 / integer atomics and the result does not depend on
+// arrival order: (1) one pass writes a surface map per label volume (a voxel has one label, so surf[v] = lab[v] on the surface of class
+// lab[v], else 0, holds every class) and the Dice counts; (2) the squared Euclidean distance transform to {surf == k} is separable: the
+// distance to the nearest source inside the row, then out[i] = min_j f[j] + (i-j)^2 along y and along z; (3) a histogram of the squared
+// distances met on the other mask's surface; (4) its two order statistics around position 0.95 (n-1).  The host takes two square roots.
+#include "tc_common.h"
+
+#define MT_MAXCLS 16
+#define MT_MAXDIM 2048                    // longest line: a [L][8] int32 tile is 64 KB of the 160 KB LDS, and 3 * 2047^2 + 2^28 stays far inside int32
+#define MT_INF TC_METRIC_NO_SOURCE
+
+// ---- (1) surfaces and counts -------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ unsigned char mt_surface(const unsigned char* __restrict__ lab, int v, int z, int y, int x, int D, int H, int W,
+                                                    int ncls, int zfaces) {
+    const unsigned char c = lab[v];
+    if (c == 0 || c >= ncls) return 0;
+    bool edge = x == 0 || x == W - 1 || y == 0 || y == H - 1 || (zfaces && (z == 0 || z == D - 1));
+    if (!edge) {                                                                   // all six neighbours are inside the array
+        edge = lab[v - 1] != c || lab[v + 1] != c || lab[v - W] != c || lab[v + W] != c;
+        if (zfaces) edge = edge || lab[v - H * W] != c || lab[v + H * W] != c;
+        return edge ? c : 0;
+    }
+    bool out = (x == 0 || lab[v - 1] != c) || (x == W - 1 || lab[v + 1] != c) || (y == 0 || lab[v - W] != c) || (y == H - 1 || lab[v + W] != c);
+    if (zfaces) out = out || (z == 0 || lab[v - H * W] != c) || (z == D - 1 || lab[v + H * W] != c);
+    return out ? c : 0;
+}
+
+// counts[3k..3k+2] += (|P==k & G==k|, |P==k|, |G==k|): per class one ballot + popcount per wave and voxel batch (wave-uniform partial sums),
+// then one LDS add per wave and one global atomic per workgroup and counter.
+__global__ __launch_bounds__(256) void metric_surfaces_kernel(const unsigned char* __restrict__ P, const unsigned char* __restrict__ G,
+                                                              unsigned char* __restrict__ sP, unsigned char* __restrict__ sG,
+                                                              unsigned long long* __restrict__ counts, int D, int H, int W, int ncls, int zfaces) {
+    __shared__ int lc[3 * MT_MAXCLS];
+    if (threadIdx.x < 3 * MT_MAXCLS) lc[threadIdx.x] = 0;
+    __syncthreads();
+    const int n = D * H * W, HW = H * W, lane = threadIdx.x & 63;
+    int ci[MT_MAXCLS], cp[MT_MAXCLS], cg[MT_MAXCLS];
+#pragma unroll
+    for (int k = 0; k < MT_MAXCLS; ++k) ci[k] = cp[k] = cg[k] = 0;
+    // every lane of a wave runs the same number of iterations (the ballots need the whole wave); `ok` masks the tail
+    for (long long base = (long long)blockIdx.x * 256 + (threadIdx.x & ~63); base < n; base += (long long)gridDim.x * 256) {
+        const long long vv = base + lane;
+        const bool ok = vv < n;
+        const int v = ok ? (int)vv : 0;
+        const int z = v / HW, r = v - z * HW, y = r / W, x = r - y * W;
+        const int p = ok ? P[v] : 255, g = ok ? G[v] : 255;
+        if (ok) {
+            sP[v] = mt_surface(P, v, z, y, x, D, H, W, ncls, zfaces);
+            sG[v] = mt_surface(G, v, z, y, x, D, H, W, ncls, zfaces);
+        }
+#pragma unroll
+        for (int k = 0; k < MT_MAXCLS; ++k) {
+            if (k < ncls) {
+                const unsigned long long mp = __ballot(p == k), mg = __ballot(g == k);
+                cp[k] += __popcll(mp); cg[k] += __popcll(mg); ci[k] += __popcll(mp & mg);
+            }
+        }
+    }
+    if (lane == 0) {
+#pragma unroll
+        for (int k = 0; k < MT_MAXCLS; ++k) {
+            if (k < ncls) {
+                if (ci[k]) atomicAdd(&lc[3 * k], ci[k]);
+                if (cp[k]) atomicAdd(&lc[3 * k + 1], cp[k]);
+                if (cg[k]) atomicAdd(&lc[3 * k + 2], cg[k]);
+            }
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x < 3 * ncls && lc[threadIdx.x]) atomicAdd(&counts[threadIdx.x], (unsigned long long)lc[threadIdx.x]);
+}
+
+// ---- (2) exact squared Euclidean distance transform ---------------------------------------------------------------------------------
+// x: one wave per row.  The row's sources become one 64-bit ballot per 64 voxels; a voxel finds the nearest set bit on either side with
+// clz / ffs, walking whole words where its own has none.
+__global__ __launch_bounds__(256) void metric_edt_x_kernel(const unsigned char* __restrict__ surf, int k, int* __restrict__ d2, int rows, int W) {
+    __shared__ unsigned long long masks[4][MT_MAXDIM / 64];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + wave;
+    const bool live = row < rows;
+    const int nch = (W + 63) >> 6;
+    const unsigned char* s = surf + (long long)(live ? row : 0) * W;
+    unsigned long long any = 0;
+    for (int c = 0; c < nch; ++c) {
+        const int x = c * 64 + lane;
+        const unsigned long long m = __ballot(live && x < W && s[x] == k);
+        if (lane == 0) masks[wave][c] = m;
+        any |= m;
+    }
+    __syncthreads();
+    if (!live) return;
+    int* o = d2 + (long long)row * W;
+    for (int c0 = 0; c0 < nch; ++c0) {
+        const int x = c0 * 64 + lane;
+        if (x >= W) break;
+        int best = MT_INF;
+        if (any) {
+            int c = c0;
+            unsigned long long m = masks[wave][c] & (~0ull >> (63 - lane));          // sources at or left of x
+            while (m == 0 && c > 0) m = masks[wave][--c];
+            if (m) { const int d = x - (c * 64 + 63 - __clzll((long long)m)); best = d * d; }
+            c = c0;
+            m = masks[wave][c] & (~0ull << lane);                                     // sources at or right of x
+            while (m == 0 && c < nch - 1) m = masks[wave][++c];
+            if (m) { const int d = c * 64 + __ffsll((unsigned long long)m) - 1 - x; best = min(best, d * d); }
+        }
+        o[x] = best;
+    }
+}
+
+// y and z: the array is [outer][L][inner] with the pass along L (y: outer = D, inner = W; z: outer = 1, inner = H*W).  A workgroup stages
+// TX neighbouring lines in LDS ([L][TX], lanes along the contiguous axis so global accesses stay coalesced and a half-wave reads one
+// conflict-free LDS row) and, for every output i, scans j outwards from i until (i-j)^2 can no longer beat the best found.  In place: a
+// workgroup reads its whole tile before it writes, and no other workgroup touches those lines.  A line without any finite value is left
+// as it is (min_j of 2^28 + (i-j)^2 is 2^28 at j = i), so only lines that the earlier passes reached are scanned.
+template <int TX>
+__global__ __launch_bounds__(256) void metric_edt_line_kernel(int* __restrict__ d2, int L, long long inner) {
+    extern __shared__ int mt_tile[];
+    constexpr int NY = 256 / TX;
+    const int tx = threadIdx.x % TX, ty = threadIdx.x / TX;
+    const long long col = (long long)blockIdx.x * TX + tx;
+    const bool ok = col < inner;
+    int* base = d2 + (long long)blockIdx.y * L * inner + (ok ? col : 0);
+    int* col_finite = mt_tile + L * TX;                                             // a line without a source stays as it is: nothing to scan for
+    if (threadIdx.x < TX) col_finite[threadIdx.x] = 0;
+    __syncthreads();
+    int finite = 0;
+    for (int i = ty; i < L; i += NY) {
+        const int v = ok ? base[i * inner] : MT_INF;
+        mt_tile[i * TX + tx] = v;
+        finite |= v < MT_INF;
+    }
+    if (finite) col_finite[tx] = 1;
+    if (!__syncthreads_or(finite)) return;
+    if (!col_finite[tx]) return;                                                    // (no barrier follows)
+    for (int i = ty; i < L; i += NY) {
+        int best = mt_tile[i * TX + tx];
+        const int far = max(i, L - 1 - i);
+        for (int d = 1; d <= far && d * d < best; ++d) {
+            const int dd = d * d;
+            if (i - d >= 0) best = min(best, mt_tile[(i - d) * TX + tx] + dd);
+            if (i + d < L) best = min(best, mt_tile[(i + d) * TX + tx] + dd);
+        }
+        if (ok) base[i * inner] = best;
+    }
+}
+
+static int mt_line_pass(int* d2, int outer, int L, long long inner, hipStream_t s) {
+    if (L <= 1) return TC_OK;
+    const int tx = L <= 512 ? 32 : (L <= 1024 ? 16 : 8);
+    const size_t smem = (size_t)(L + 1) * tx * sizeof(int);                          // the tile and one flag per line: <= 64 KB + 128 B
+    const dim3 grid((unsigned)((inner + tx - 1) / tx), (unsigned)outer);
+    const void* fn = tx == 32 ? (const void*)metric_edt_line_kernel<32> : tx == 16 ? (const void*)metric_edt_line_kernel<16> : (const void*)metric_edt_line_kernel<8>;
+    if (smem > 64 * 1024) (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+    if (tx == 32) hipLaunchKernelGGL(metric_edt_line_kernel<32>, grid, dim3(256), smem, s, d2, L, inner);
+    else if (tx == 16) hipLaunchKernelGGL(metric_edt_line_kernel<16>, grid, dim3(256), smem, s, d2, L, inner);
+    else hipLaunchKernelGGL(metric_edt_line_kernel<8>, grid, dim3(256), smem, s, d2, L, inner);
+    return tc_launch_status();
+}
+
+// ---- (3) histogram of squared distances ----------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void metric_hist_kernel(const unsigned char* __restrict__ sP, const unsigned char* __restrict__ sG,
+                                                          const int* __restrict__ d2P, const int* __restrict__ d2G, int k,
+                                                          unsigned int* __restrict__ hist, long long nbins, int n) {
+    for (long long v = (long long)blockIdx.x * 256 + threadIdx.x; v < n; v += (long long)gridDim.x * 256) {
+        if (sP[v] == k) { const int d = d2G[v]; if (d < nbins) atomicAdd(&hist[d], 1u); }       // d >= nbins only when the other surface is empty
+        if (sG[v] == k) { const int d = d2P[v]; if (d < nbins) atomicAdd(&hist[d], 1u); }
+    }
+}
+
+// ---- (4) order statistics --------------------------------------------------------------------------------------------------------------
+// One workgroup per class: every thread sums one contiguous run of bins, thread 0 walks the 256 partial sums to the run that holds each
+// wanted position and then that run.
+__global__ __launch_bounds__(256) void metric_select_kernel(const unsigned int* __restrict__ hist, long long nbins, long long* __restrict__ out) {
+    __shared__ unsigned long long part[256];
+    const unsigned int* h = hist + (long long)blockIdx.x * nbins;
+    const long long run = (nbins + 255) / 256, b0 = threadIdx.x * run, b1 = b0 + run < nbins ? b0 + run : nbins;
+    unsigned long long sum = 0;
+    for (long long b = b0; b < b1; ++b) sum += h[b];
+    part[threadIdx.x] = sum;
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    unsigned long long n = 0;
+    for (int t = 0; t < 256; ++t) n += part[t];
+    long long* o = out + 3 * blockIdx.x;
+    o[0] = (long long)n; o[1] = 0; o[2] = 0;
+    if (n == 0) return;
+    // the host forms the same IEEE fp64 product 0.95 * (n-1) (evaluate.hd95_from_order_stats), so its floor and fraction belong to these positions
+    const unsigned long long lo = (unsigned long long)floor(0.95 * (double)(n - 1)), hi = lo + 1 < n ? lo + 1 : n - 1;
+    const unsigned long long want[2] = {lo, hi};
+    for (int w = 0; w < 2; ++w) {
+        unsigned long long before = 0;
+        int t = 0;
+        while (before + part[t] <= want[w]) before += part[t++];                      // terminates: want < n = sum of part
+        long long b = t * run;
+        while (before + h[b] <= want[w]) before += h[b++];                            // and the run's bins sum to part[t]
+        o[1 + w] = b;
+    }
+}
+
+// ---- entries ------------------------------------------------------------------------------------------------------------------------------
+static bool mt_shape_ok(int D, int H, int W) {
+    return D > 0 && H > 0 && W > 0 && D <= MT_MAXDIM && H <= MT_MAXDIM && W <= MT_MAXDIM && (long long)D * H * W < 0x7fffffffLL;
+}
+
+extern "C" long long tc_metric_hist_bins(int D, int H, int W) {
+    if (!mt_shape_ok(D, H, W)) return 0;
+    return (long long)(D - 1) * (D - 1) + (long long)(H - 1) * (H - 1) + (long long)(W - 1) * (W - 1) + 1;
+}
+
+extern "C" int tc_metric_surfaces(const unsigned char* pred, const unsigned char* gt, unsigned char* surf_pred, unsigned char* surf_gt,
+                                  long long* counts, int D, int H, int W, int ncls, int zfaces, void* stream) {
+    if (!pred || !gt || !surf_pred || !surf_gt || !counts || !mt_shape_ok(D, H, W) || ncls <= 0 || ncls > MT_MAXCLS) return TC_ERR_ARG;
+    hipLaunchKernelGGL(metric_surfaces_kernel, dim3(tc_blocks((long long)D * H * W, 256, 2048)), dim3(256), 0, (hipStream_t)stream,
+                       pred, gt, surf_pred, surf_gt, (unsigned long long*)counts, D, H, W, ncls, zfaces ? 1 : 0);
+    return tc_launch_status();
+}
+
+extern "C" int tc_metric_edt(const unsigned char* surf, int k, int* d2, int D, int H, int W, int zfaces, void* stream) {
+    if (!surf || !d2 || !mt_shape_ok(D, H, W) || k <= 0 || k >= MT_MAXCLS) return TC_ERR_ARG;
+    hipStream_t s = (hipStream_t)stream;
+    const int rows = D * H;
+    hipLaunchKernelGGL(metric_edt_x_kernel, dim3((rows + 3) / 4), dim3(256), 0, s, surf, k, d2, rows, W);
+    int rc = tc_launch_status();
+    if (rc == TC_OK) rc = mt_line_pass(d2, D, H, W, s);
+    if (rc == TC_OK && zfaces) rc = mt_line_pass(d2, 1, D, (long long)H * W, s);
+    return rc;
+}
+
+extern "C" int tc_metric_hist(const unsigned char* surf_pred, const unsigned char* surf_gt, const int* d2_pred, const int* d2_gt, int k,
+                              unsigned int* hist, long long nbins, int ncls, int D, int H, int W, void* stream) {
+    if (!surf_pred || !surf_gt || !d2_pred || !d2_gt || !hist || !mt_shape_ok(D, H, W) || ncls <= 0 || ncls > MT_MAXCLS || k <= 0 || k >= ncls ||
+        nbins < tc_metric_hist_bins(D, H, W))
+        return TC_ERR_ARG;
+    hipLaunchKernelGGL(metric_hist_kernel, dim3(tc_blocks((long long)D * H * W, 256, 2048)), dim3(256), 0, (hipStream_t)stream,
+                       surf_pred, surf_gt, d2_pred, d2_gt, k, hist + (long long)k * nbins, nbins, D * H * W);
+    return tc_launch_status();
+}
+
+extern "C" int tc_metric_select(const unsigned int* hist, long long nbins, int ncls, long long* out, void* stream) {
+    if (!hist || !out || nbins <= 0 || ncls <= 0 || ncls > MT_MAXCLS) return TC_ERR_ARG;
+    hipLaunchKernelGGL(metric_select_kernel, dim3(ncls), dim3(256), 0, (hipStream_t)stream, hist, nbins, out);
+    return tc_launch_status();
+}

@@ -5,20 +5,31 @@ The reference runs one slice at a time (batch 1, host sync per slice, `utils.py:
 normalised and pushed through the eval-mode forward in batches, `argmax(softmax(logits))` and the per-class voxel counts of
 the Dice score are one HIP kernel (`tc_argmax_counts`), and only the uint8 label map returns to the host.
 
-Host-side pieces that stay on the CPU exactly as in the reference: the order-3 `scipy.ndimage.zoom` of a slice to the network
-size and the order-0 zoom of the prediction back (`utils.py:69-70,83-84`), and HD95: `medpy.metric.binary.hd95` (`utils.py:55`;
-medpy is not installable here) restated from its published algorithm on scipy.ndimage -- surface voxels = mask minus its
-erosion (connectivity 1), distances by the Euclidean distance transform of the other mask's surface, 95th percentile of both
-directions pooled.  Parity with medpy itself is unpinned; tests pin it to a brute-force evaluation of that definition.
+The order-3 zoom of a slice to the network size and the order-0 zoom of the prediction back (`utils.py:69-70,83-84`) run on the
+device too (`host_zoom=True` keeps scipy per slice, as the reference does).
+
+The metric (`calculate_metric_percase`, `utils.py:50-60`) has two forms.  The default is the host one: HD95 is
+`medpy.metric.binary.hd95` (`utils.py:55`; medpy is not installable here) restated from its published algorithm on scipy.ndimage --
+surface voxels = mask minus its erosion (connectivity 1), distances by the Euclidean distance transform of the other mask's
+surface, 95th percentile of both directions pooled.  Parity with medpy itself is unpinned; tests pin it to a brute-force
+evaluation of that definition.  With `device_metrics=True` the prediction never leaves the GPU: `metrics_device` computes the
+Dice counts and the same HD95 (unit spacing, connectivity 1) exactly, in integers, with the kernels of csrc/metrics.hip -- surface
+maps, a separable squared Euclidean distance transform, a histogram of squared distances and its two order statistics -- and
+one small copy of (counts, n, d2_lo, d2_hi) per volume returns to the host, which takes the square roots.  Anisotropic
+`voxelspacing` exists on the host path only.
 """
 from __future__ import annotations
 
 from typing import List, Optional, Tuple
 
+import math
+
 import numpy as np
 import torch
 
 from ._lib import TC_F32, lib
+
+NO_CPU = "transception_amd.evaluate runs on MI355X only (no CPU fallback)"
 
 
 def argmax_counts(logits: torch.Tensor, labels: Optional[torch.Tensor] = None,
@@ -26,7 +37,7 @@ def argmax_counts(logits: torch.Tensor, labels: Optional[torch.Tensor] = None,
     """pred[b,h,w] = argmax_k logits[b,k,h,w] (uint8).  With `labels` (int64 [B,H,W]) the per-class counts
     (|pred==k & gt==k|, |pred==k|, |gt==k|) are ADDED to `counts` (float32 [ncls,3], created zeroed when None)."""
     if not logits.is_cuda:
-        raise RuntimeError("transception_amd.evaluate runs on MI355X only (no CPU fallback)")
+        raise RuntimeError(NO_CPU)
     B, C, H, W = logits.shape
     lg = logits.contiguous().float()
     pred = torch.empty((B, H, W), dtype=torch.uint8, device=lg.device)
@@ -86,6 +97,114 @@ def calculate_metric_percase(pred: np.ndarray, gt: np.ndarray) -> Tuple[float, f
     return 0.0, 0.0
 
 
+def _shape3(shape) -> Tuple[int, int, int]:
+    """[D,H,W], or [H,W] as one slice."""
+    if len(shape) not in (2, 3):
+        raise ValueError(f"label volumes are [D,H,W] or [H,W], got {tuple(shape)}")
+    return (1,) * (3 - len(shape)) + tuple(int(v) for v in shape)
+
+
+def metrics_hist_bins(shape) -> int:
+    """Bins of one class's histogram of squared distances: the largest squared distance inside the array, plus one."""
+    D, H, W = _shape3(shape)
+    return (D - 1) ** 2 + (H - 1) ** 2 + (W - 1) ** 2 + 1
+
+
+def metrics_scratch_bytes(shape, classes: int) -> int:
+    """What `metrics_device` allocates for one volume: two uint8 surface maps, two int32 squared-distance maps (one class at a time:
+    to the prediction's surface and to the ground truth's), the uint32 histograms [classes][bins] and the int64 result [2][classes][3]."""
+    D, H, W = _shape3(shape)
+    n = D * H * W
+    return 2 * n + 2 * 4 * n + 4 * classes * metrics_hist_bins(shape) + 8 * 2 * classes * 3
+
+
+def hd95_from_order_stats(n: int, d2_lo: int, d2_hi: int) -> float:
+    """numpy.percentile(sqrt(d2), 95) of a pooled multiset of n squared distances from the two order statistics tc_metric_select returns:
+    d2_lo at sorted position floor(0.95 (n-1)) and d2_hi at the next one (clamped), interpolated linearly in fp64."""
+    pos = 0.95 * (n - 1)
+    lo, hi = math.sqrt(d2_lo), math.sqrt(d2_hi)
+    return lo + (hi - lo) * (pos - math.floor(pos))
+
+
+def _label_pair(pred: torch.Tensor, label: torch.Tensor, classes: int):
+    if not (pred.is_cuda and label.is_cuda):
+        raise RuntimeError(NO_CPU)
+    if pred.dtype != torch.uint8 or label.dtype != torch.uint8 or pred.shape != label.shape:
+        raise ValueError("metrics on the device take two uint8 label volumes of one shape")
+    if not 2 <= classes <= 16:
+        raise ValueError("classes must be in 2..16")
+    return pred.contiguous(), label.contiguous(), _shape3(pred.shape), int(pred.dim() == 3)
+
+
+def surfaces_counts(pred: torch.Tensor, label: torch.Tensor, classes: int):
+    """(surf_pred, surf_label, counts): per volume the uint8 map that holds label k on the surface voxels of class k and 0 elsewhere,
+    and the int64 [classes,3] Dice counts (|P==k & G==k|, |P==k|, |G==k|), one launch (tc_metric_surfaces).  Nothing is synchronised."""
+    pred, label, (D, H, W), zfaces = _label_pair(pred, label, classes)
+    sp, sg = torch.empty_like(pred), torch.empty_like(label)
+    counts = torch.zeros((classes, 3), dtype=torch.int64, device=pred.device)
+    stream = torch.cuda.current_stream(pred.device).cuda_stream
+    lib().tc_metric_surfaces(pred.data_ptr(), label.data_ptr(), sp.data_ptr(), sg.data_ptr(), counts.data_ptr(), D, H, W, classes, zfaces, stream)
+    return sp, sg, counts
+
+
+def edt_squared(surf: torch.Tensor, k: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """int32 map of the squared Euclidean distance to the nearest voxel with surf == k (TC_METRIC_NO_SOURCE everywhere if there is none)."""
+    if not surf.is_cuda:
+        raise RuntimeError(NO_CPU)
+    D, H, W = _shape3(surf.shape)
+    if out is None:
+        out = torch.empty(surf.shape, dtype=torch.int32, device=surf.device)
+    lib().tc_metric_edt(surf.data_ptr(), k, out.data_ptr(), D, H, W, int(surf.dim() == 3), torch.cuda.current_stream(surf.device).cuda_stream)
+    return out
+
+
+def metrics_order_stats(pred: torch.Tensor, label: torch.Tensor, classes: int) -> torch.Tensor:
+    """int64 [2,classes,3] on the device: [0] the Dice counts, [1] (n, d2_lo, d2_hi) per class (tc_metric_select).  Allocates
+    `metrics_scratch_bytes(pred.shape, classes)`; the two distance maps are reused class by class.  Nothing is synchronised."""
+    sp, sg, counts = surfaces_counts(pred, label, classes)
+    D, H, W = _shape3(pred.shape)
+    dev = pred.device
+    L, stream = lib(), torch.cuda.current_stream(dev).cuda_stream
+    nbins = metrics_hist_bins(pred.shape)
+    hist = torch.zeros((classes, nbins), dtype=torch.int32, device=dev)               # uint32 to the library
+    dp, dg = torch.empty(pred.shape, dtype=torch.int32, device=dev), torch.empty(pred.shape, dtype=torch.int32, device=dev)
+    res = torch.empty((2, classes, 3), dtype=torch.int64, device=dev)
+    res[0] = counts
+    for k in range(1, classes):
+        edt_squared(sp, k, dp)
+        edt_squared(sg, k, dg)
+        L.tc_metric_hist(sp.data_ptr(), sg.data_ptr(), dp.data_ptr(), dg.data_ptr(), k, hist.data_ptr(), nbins, classes, D, H, W, stream)
+    L.tc_metric_select(hist.data_ptr(), nbins, classes, res[1].data_ptr(), stream)
+    return res
+
+
+def metrics_device(pred: torch.Tensor, label: torch.Tensor, classes: int = 9) -> List[Tuple[float, float]]:
+    """`calculate_metric_percase` (utils.py:50-60) for classes 1..classes-1 of two uint8 CUDA label volumes [D,H,W] ([H,W]: true 2-D, no z
+    faces), unit spacing, connectivity 1: [(dice, hd95)].  Exact integer work on the device (csrc/metrics.hip), one copy of 6 * classes
+    integers back; scratch: `metrics_scratch_bytes` (10 bytes a voxel plus the histograms).  The library takes D, H, W up to 2048 and
+    fewer than 2^31 voxels; a larger volume raises `TcError`."""
+    counts, sel = metrics_order_stats(pred, label, classes).cpu().tolist()
+    out = []
+    for (inter, p, g), (n, lo, hi) in zip(counts[1:], sel[1:]):
+        if p > 0 and g > 0:
+            out.append((float(2.0 * inter / (p + g)), hd95_from_order_stats(n, lo, hi)))
+        elif p > 0:
+            out.append((1.0, 0.0))
+        else:
+            out.append((0.0, 0.0))
+    return out
+
+
+def hd95_device(result: torch.Tensor, reference: torch.Tensor) -> float:
+    """`hd95(result, reference)` with its defaults for two boolean / uint8 CUDA masks, on the device."""
+    if not (result.is_cuda and reference.is_cuda):
+        raise RuntimeError(NO_CPU)
+    counts, sel = metrics_order_stats((result != 0).to(torch.uint8), (reference != 0).to(torch.uint8), 2).cpu().tolist()
+    if counts[1][1] == 0 or counts[1][2] == 0:
+        raise RuntimeError("surface distances need non-empty masks")
+    return hd95_from_order_stats(*sel[1])
+
+
 @torch.no_grad()
 def predict_slices(model, slices: torch.Tensor, batch: int = 16) -> torch.Tensor:
     """slices: float [N,H,W] in [0,1] at the network size (a multiple of 32); returns uint8 [N,H,W] labels.
@@ -135,11 +254,15 @@ def zoom_labels(pred: torch.Tensor, size: Tuple[int, int]) -> torch.Tensor:
 
 @torch.no_grad()
 def evaluate_volume(model, image: np.ndarray, label: np.ndarray, classes: int = 9, patch_size=(224, 224),
-                    batch: int = 16, with_hd95: bool = False, host_zoom: bool = False):
+                    batch: int = 16, with_hd95: bool = False, host_zoom: bool = False, device_metrics: bool = False):
     """`test_single_volume` for one [D,H,W] volume (utils.py:63-98): per-class Dice for classes 1..classes-1, or with
     `with_hd95` the reference's metric_list of (dice, hd95) pairs.  The volume goes to the GPU once; the order-3 zoom to the network
-    size, inference, argmax and the order-0 zoom back all run there (host_zoom=True: scipy per slice, as the reference does)."""
+    size, inference, argmax and the order-0 zoom back all run there (host_zoom=True: scipy per slice, as the reference does).
+    `device_metrics=True`: the prediction stays on the GPU, the label volume is uploaded once and `metrics_device` (with_hd95) or the
+    counts of its first kernel (Dice only) replace the host metric; same returned structure."""
     dev = next(model.parameters()).device
+    if device_metrics and dev.type != "cuda":
+        raise RuntimeError(NO_CPU)
     D, X, Y = image.shape
     resize = (X, Y) != tuple(patch_size)
     if host_zoom:
@@ -152,7 +275,15 @@ def evaluate_volume(model, image: np.ndarray, label: np.ndarray, classes: int = 
         vol = torch.from_numpy(np.ascontiguousarray(image, np.float32)).to(dev)
         sl = zoom_volume_to_network(vol, tuple(patch_size)) if resize else vol
         pred_d = predict_slices(model, sl, batch)
-        pred = (zoom_labels(pred_d, (X, Y)) if resize else pred_d).cpu().numpy()
+        pred = zoom_labels(pred_d, (X, Y)) if resize else pred_d
+        if not device_metrics:
+            pred = pred.cpu().numpy()
+    if device_metrics:
+        pred_t = torch.from_numpy(pred).to(dev) if host_zoom else pred
+        label_t = torch.from_numpy(np.ascontiguousarray(label).astype(np.uint8)).to(dev)
+        if with_hd95:
+            return metrics_device(pred_t, label_t, classes)
+        return dice_from_counts(surfaces_counts(pred_t, label_t, classes)[2].cpu().numpy())
     if with_hd95:
         return [calculate_metric_percase(pred == k, label == k) for k in range(1, classes)]
     counts = np.zeros((classes, 3), dtype=np.float64)
@@ -162,11 +293,14 @@ def evaluate_volume(model, image: np.ndarray, label: np.ndarray, classes: int = 
     return dice_from_counts(counts)
 
 
-def inference(model, volumes, classes: int = 9, img_size: int = 224, batch: int = 16, log=None) -> Tuple[float, float]:
-    """trainer.py:25-47: mean Dice and mean HD95 over `volumes` = iterable of (image [D,H,W] in [0,1], label [D,H,W], case name)."""
+def inference(model, volumes, classes: int = 9, img_size: int = 224, batch: int = 16, log=None,
+              device_metrics: bool = False) -> Tuple[float, float]:
+    """trainer.py:25-47: mean Dice and mean HD95 over `volumes` = iterable of (image [D,H,W] in [0,1], label [D,H,W], case name).
+    `device_metrics`: as in `evaluate_volume`."""
     total, n = 0.0, 0
     for i, (image, label, name) in enumerate(volumes):
-        m = np.array(evaluate_volume(model, np.asarray(image), np.asarray(label), classes, (img_size, img_size), batch, with_hd95=True))
+        m = np.array(evaluate_volume(model, np.asarray(image), np.asarray(label), classes, (img_size, img_size), batch, with_hd95=True,
+                                     device_metrics=device_metrics))
         total = total + m
         n += 1
         if log:
