@@ -676,6 +676,29 @@ int tc_metric_hist(const unsigned char* surf_pred, const unsigned char* surf_gt,
                    unsigned int* hist, long long nbins, int ncls, int D, int H, int W, void* stream);
 int tc_metric_select(const unsigned int* hist, long long nbins, int ncls, long long* out, void* stream);
 
+/* The same metric with anisotropic voxel spacing (sz, sy, sx), each finite and > 0, in the units of the result (medpy's voxelspacing, in
+ * array axis order): distance^2 = (sz dz)^2 + (sy dy)^2 + (sx dx)^2 is no integer, so the maps are fp64 and the order statistics come
+ * from a radix select over bit patterns, not from a histogram indexed by the distance.  Surfaces and counts do not depend on spacing:
+ * tc_metric_surfaces serves both forms.  Same limits (D, H, W in 1..2048, fewer than 2^31 voxels, k in 1..15 and k < ncls where ncls is
+ * passed), same meaning of zfaces (0: sz is not used), same error rule; a spacing that is not finite and > 0 is TC_ERR_ARG.
+ *
+ * tc_metric_edt_f64: d2[v] = min over voxels u with surf == k of (sz dz)^2 + (sy dy)^2 + (sx dx)^2, double [D,H,W], OVERWRITTEN
+ *   (separable: (sx dx)^2 to the nearest source within the row, then min_j f[j] + (s (i-j))^2 along y and z, in place; the sum is
+ *   formed in the order x, y, z, each term rounded once or fused into the add).  +inf everywhere when no voxel has surf == k (with
+ *   zfaces = 0: in every slice without one).
+ * tc_metric_select_f64: for ONE class k, out[3k..3k+2] = (n, d2_lo, d2_hi), OVERWRITTEN (the other classes' records are not touched):
+ *   n (long long) counts the pooled multiset { d2_gt[v] : surf_pred[v] == k } + { d2_pred[v] : surf_gt[v] == k } without its +inf
+ *   members (distances to an empty surface), and the next two 8-byte slots hold, AS DOUBLES, its elements at sorted positions
+ *   floor(0.95 (n-1)) and min(that + 1, n-1); (0, 0.0, 0.0) for an empty multiset.  Exact: non-negative doubles order like their bit
+ *   patterns, and eight passes of 8-bit integer histograms (most significant digit first) pin both elements; integer atomics only, so
+ *   the result is bit-identical from run to run.  work: TC_METRIC_SELECT_WORK_BYTES of device memory, 8-byte aligned, OVERWRITTEN
+ *   (zeroed by the entry; one buffer serves every class on one stream).  The host forms the percentile as for tc_metric_select. */
+#define TC_METRIC_SELECT_WORK_BYTES 16448
+int tc_metric_edt_f64(const unsigned char* surf, int k, double* d2, int D, int H, int W, int zfaces, double sz, double sy, double sx,
+                      void* stream);
+int tc_metric_select_f64(const unsigned char* surf_pred, const unsigned char* surf_gt, const double* d2_pred, const double* d2_gt, int k,
+                         int ncls, int D, int H, int W, void* work, long long* out, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Input pipeline (datasets/dataset_synapse.py:101-112, trainer.py:89-93): a batch of raw slices
  * [B,H,W] (image fp32 in [0,1], label uint8 0..8) already in HBM -> network input.

@@ -16,7 +16,7 @@ ACT_NONE, ACT_HSWISH, ACT_COORD, ACT_SIGMOID, ACT_GELU, ACT_SCALE, ACT_RELU = 0,
 ABI_VERSION = 15
 ATTN_DKV_SPLITS = 8                # include/transception_hip.h: partial dK|dV buffers in tc_attn_bwd_seg's fp32 scratch
 
-vp, i32, i64, f32 = C.c_void_p, C.c_int, C.c_longlong, C.c_float
+vp, i32, i64, f32, f64 = C.c_void_p, C.c_int, C.c_longlong, C.c_float, C.c_double
 
 
 class TcGemm(C.Structure):
@@ -104,6 +104,7 @@ class TcSliceAug(C.Structure):
 TC_AUG_WARP, TC_AUG_LINEAR, TC_AUG_BLUR, TC_AUG_PIECEWISE = 1, 2, 4, 8
 TC_AUG_SKIP, TC_AUG_FROM_RAW = 1 << 20, 1 << 21
 TC_METRIC_NO_SOURCE = 1 << 28          # include/transception_hip.h: tc_metric_edt's value where no voxel has surf == k
+TC_METRIC_SELECT_WORK_BYTES = 16448    # include/transception_hip.h: tc_metric_select_f64's work buffer
 
 # name -> argtypes (every function returns int status unless listed in _RET)
 SIGNATURES = {
@@ -208,6 +209,8 @@ SIGNATURES = {
     "tc_metric_edt": [vp, i32, vp, i32, i32, i32, i32, vp],
     "tc_metric_hist": [vp, vp, vp, vp, i32, vp, i64, i32, i32, i32, i32, vp],
     "tc_metric_select": [vp, i64, i32, vp, vp],
+    "tc_metric_edt_f64": [vp, i32, vp, i32, i32, i32, i32, f64, f64, f64, vp],
+    "tc_metric_select_f64": [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp],
     "tc_seg_loss_bwd": [vp, vp, vp, vp, i32, i32, i32, f32, f32, f32, f32, vp, i32, vp],
     "tc_seg_loss_fwd_tok": [vp, i32, vp, vp, vp, i32, i32, i32, i32, vp],
     "tc_seg_loss_bwd_tok": [vp, vp, i32, vp, vp, vp, i32, i32, i32, i32, f32, f32, f32, f32, vp, i32, vp],

@@ -207,6 +207,178 @@ __global__ __launch_bounds__(256) void metric_select_kernel(const unsigned int* 
     }
 }
 
+// ---- (5) anisotropic voxel spacing: the same transform and order statistics in fp64 ---------------------------------------------------
+// With a spacing (sz, sy, sx) a squared distance (sz dz)^2 + (sy dy)^2 + (sx dx)^2 is no integer any more, so there is no histogram to index
+// with it.  The transform keeps its shape in doubles; the two order statistics come from a most-significant-digit radix select over the bit
+// patterns (non-negative doubles order like their bits read as uint64): integer histograms of one 8-bit digit per pass, eight passes.
+#define MT_F64_INF_BITS 0x7ff0000000000000ull
+#define MT_SEL_PASSES 8
+#define MT_SEL_HIST_WORDS (MT_SEL_PASSES * 2 * 256)       // uint32 [pass][wanted position][digit], then one MtSelState
+struct MtSelState { unsigned long long prefix[2], rank[2], n; };   // per wanted position: the digits fixed so far and the position among the values that share them
+static_assert(MT_SEL_HIST_WORDS * 4 + sizeof(MtSelState) <= TC_METRIC_SELECT_WORK_BYTES, "the header's work size");
+
+// x: metric_edt_x_kernel with the nearest source's distance scaled: d2 = (sx dx)^2, +inf in a row without a source.
+__global__ __launch_bounds__(256) void metric_edt_x_f64_kernel(const unsigned char* __restrict__ surf, int k, double* __restrict__ d2, int rows, int W, double sx) {
+    __shared__ unsigned long long masks[4][MT_MAXDIM / 64];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + wave;
+    const bool live = row < rows;
+    const int nch = (W + 63) >> 6;
+    const unsigned char* s = surf + (long long)(live ? row : 0) * W;
+    unsigned long long any = 0;
+    for (int c = 0; c < nch; ++c) {
+        const int x = c * 64 + lane;
+        const unsigned long long m = __ballot(live && x < W && s[x] == k);
+        if (lane == 0) masks[wave][c] = m;
+        any |= m;
+    }
+    __syncthreads();
+    if (!live) return;
+    double* o = d2 + (long long)row * W;
+    for (int c0 = 0; c0 < nch; ++c0) {
+        const int x = c0 * 64 + lane;
+        if (x >= W) break;
+        double best = __builtin_huge_val();
+        if (any) {
+            int near = MT_MAXDIM, c = c0;
+            unsigned long long m = masks[wave][c] & (~0ull >> (63 - lane));          // sources at or left of x
+            while (m == 0 && c > 0) m = masks[wave][--c];
+            if (m) near = x - (c * 64 + 63 - __clzll((long long)m));
+            c = c0;
+            m = masks[wave][c] & (~0ull << lane);                                     // sources at or right of x
+            while (m == 0 && c < nch - 1) m = masks[wave][++c];
+            if (m) near = min(near, c * 64 + __ffsll((unsigned long long)m) - 1 - x);
+            const double t = sx * near;
+            best = t * t;
+        }
+        o[x] = best;
+    }
+}
+
+// y and z: metric_edt_line_kernel on doubles, out[i] = min_j f[j] + (s (i-j))^2.  The tile is [L][TX] doubles with lanes along the contiguous
+// axis: a half-wave reads 32 / TX whole neighbouring rows, 256 contiguous bytes, which is one conflict-free bank row of an 8-byte LDS read
+// (every lane of a wave is at the same step d of its scan).  TX = 32, 16, 8 for L <= 256, 512, 2048: 64 KB of tile up to L = 1024, so two
+// workgroups share a compute unit, and 128 KB of the 160 KB for the longest lines.
+template <int TX>
+__global__ __launch_bounds__(256) void metric_edt_line_f64_kernel(double* __restrict__ d2, int L, long long inner, double s) {
+    extern __shared__ double mt_tile_f64[];
+    constexpr int NY = 256 / TX;
+    const int tx = threadIdx.x % TX, ty = threadIdx.x / TX;
+    const long long col = (long long)blockIdx.x * TX + tx;
+    const bool ok = col < inner;
+    double* base = d2 + (long long)blockIdx.y * L * inner + (ok ? col : 0);
+    int* col_finite = (int*)(mt_tile_f64 + L * TX);                                 // a line without a source stays as it is: nothing to scan for
+    if (threadIdx.x < TX) col_finite[threadIdx.x] = 0;
+    __syncthreads();
+    const double inf = __builtin_huge_val();
+    int finite = 0;
+    for (int i = ty; i < L; i += NY) {
+        const double v = ok ? base[i * inner] : inf;
+        mt_tile_f64[i * TX + tx] = v;
+        finite |= v < inf;
+    }
+    if (finite) col_finite[tx] = 1;
+    if (!__syncthreads_or(finite)) return;
+    if (!col_finite[tx]) return;                                                    // (no barrier follows)
+    for (int i = ty; i < L; i += NY) {
+        double best = mt_tile_f64[i * TX + tx];
+        const int far = max(i, L - 1 - i);
+        for (int d = 1; d <= far; ++d) {
+            const double t = s * d, dd = t * t;
+            if (!(dd < best)) break;
+            if (i - d >= 0) best = fmin(best, mt_tile_f64[(i - d) * TX + tx] + dd);
+            if (i + d < L) best = fmin(best, mt_tile_f64[(i + d) * TX + tx] + dd);
+        }
+        if (ok) base[i * inner] = best;
+    }
+}
+
+static int mt_line_pass_f64(double* d2, int outer, int L, long long inner, double sp, hipStream_t s) {
+    if (L <= 1) return TC_OK;
+    const int tx = L <= 256 ? 32 : (L <= 512 ? 16 : 8);
+    const size_t smem = (size_t)L * tx * sizeof(double) + tx * sizeof(int);          // the tile and one flag per line: <= 128 KB + 32 B
+    const dim3 grid((unsigned)((inner + tx - 1) / tx), (unsigned)outer);
+    const void* fn = tx == 32 ? (const void*)metric_edt_line_f64_kernel<32> : tx == 16 ? (const void*)metric_edt_line_f64_kernel<16> : (const void*)metric_edt_line_f64_kernel<8>;
+    if (smem > 64 * 1024 && hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess) return TC_ERR_LAUNCH;
+    if (tx == 32) hipLaunchKernelGGL(metric_edt_line_f64_kernel<32>, grid, dim3(256), smem, s, d2, L, inner, sp);
+    else if (tx == 16) hipLaunchKernelGGL(metric_edt_line_f64_kernel<16>, grid, dim3(256), smem, s, d2, L, inner, sp);
+    else hipLaunchKernelGGL(metric_edt_line_f64_kernel<8>, grid, dim3(256), smem, s, d2, L, inner, sp);
+    return tc_launch_status();
+}
+
+// One pass of the radix select.  The pooled multiset of class k is d2_gt on the prediction's surface and d2_pred on the ground truth's
+// (+inf, the distance to an empty surface, is not counted).  Of the values whose leading 8 * pass bits equal the prefix fixed for a wanted
+// position, the next 8-bit digit is counted: in LDS first, then one global atomic per workgroup and used bin.  While both positions share
+// their prefix (always in pass 0) only row 0 is filled.
+__global__ __launch_bounds__(256) void metric_select_count_kernel(const unsigned char* __restrict__ sP, const unsigned char* __restrict__ sG,
+                                                                  const double* __restrict__ d2P, const double* __restrict__ d2G, int k,
+                                                                  unsigned int* __restrict__ work, int pass, int n) {
+    __shared__ unsigned int lh[2][256];
+    lh[0][threadIdx.x] = 0; lh[1][threadIdx.x] = 0;
+    const MtSelState* st = (const MtSelState*)(work + MT_SEL_HIST_WORDS);
+    const unsigned long long p0 = pass ? st->prefix[0] : 0, p1 = pass ? st->prefix[1] : 0;
+    const int shift = 56 - 8 * pass;
+    __syncthreads();
+    auto count = [&](double x) {
+        const unsigned long long b = (unsigned long long)__double_as_longlong(x);
+        if (b >= MT_F64_INF_BITS) return;
+        const unsigned long long lead = pass ? b >> (shift + 8) : 0;
+        const int digit = (int)(b >> shift) & 255;
+        if (lead == p0) atomicAdd(&lh[0][digit], 1u);
+        else if (lead == p1) atomicAdd(&lh[1][digit], 1u);
+    };
+    for (long long v = (long long)blockIdx.x * 256 + threadIdx.x; v < n; v += (long long)gridDim.x * 256) {
+        if (sP[v] == k) count(d2G[v]);
+        if (sG[v] == k) count(d2P[v]);
+    }
+    __syncthreads();
+    unsigned int* hist = work + pass * 512;
+    if (lh[0][threadIdx.x]) atomicAdd(&hist[threadIdx.x], lh[0][threadIdx.x]);
+    if (lh[1][threadIdx.x]) atomicAdd(&hist[256 + threadIdx.x], lh[1][threadIdx.x]);
+}
+
+// One workgroup: an inclusive scan over the 256 bins of each wanted position, and the thread whose bin holds the position appends its
+// digit to the prefix and keeps the position inside the bin.  Pass 0 also fixes n and the two positions; the last pass writes the result.
+__global__ __launch_bounds__(256) void metric_select_scan_kernel(unsigned int* __restrict__ work, int pass, long long* __restrict__ out) {
+    __shared__ unsigned long long inc[2][256];
+    MtSelState* st = (MtSelState*)(work + MT_SEL_HIST_WORDS);
+    const unsigned int* hist = work + pass * 512;
+    const int t = threadIdx.x;
+    const unsigned long long p[2] = {pass ? st->prefix[0] : 0, pass ? st->prefix[1] : 0};
+    unsigned long long rank[2] = {pass ? st->rank[0] : 0, pass ? st->rank[1] : 0}, n = pass ? st->n : 0;
+    const unsigned long long h[2] = {hist[t], p[0] != p[1] ? hist[256 + t] : hist[t]};
+    inc[0][t] = h[0]; inc[1][t] = h[1];
+    __syncthreads();
+    for (int off = 1; off < 256; off <<= 1) {
+        const unsigned long long a = t >= off ? inc[0][t - off] : 0, b = t >= off ? inc[1][t - off] : 0;
+        __syncthreads();
+        inc[0][t] += a; inc[1][t] += b;
+        __syncthreads();
+    }
+    if (pass == 0) {
+        n = inc[0][255];
+        if (n) {
+            // the host forms the same IEEE fp64 product 0.95 * (n-1) (evaluate.hd95_from_order_stats), so its floor and fraction belong to these positions
+            rank[0] = (unsigned long long)floor(0.95 * (double)(n - 1));
+            rank[1] = rank[0] + 1 < n ? rank[0] + 1 : n - 1;
+        }
+        if (t == 0) st->n = n;
+    }
+    if (n == 0) {                                                                    // (uniform) an empty multiset: (0, 0.0, 0.0)
+        if (t == 0 && pass == MT_SEL_PASSES - 1) { out[0] = 0; out[1] = 0; out[2] = 0; }
+        return;
+    }
+    for (int w = 0; w < 2; ++w) {
+        const unsigned long long before = inc[w][t] - h[w];
+        if (h[w] && before <= rank[w] && rank[w] < inc[w][t]) {                      // exactly one thread: rank < the bins' total
+            const unsigned long long q = (p[w] << 8) | (unsigned long long)t;
+            st->prefix[w] = q; st->rank[w] = rank[w] - before;
+            if (pass == MT_SEL_PASSES - 1) out[1 + w] = (long long)q;                // all 64 bits: the double itself
+        }
+    }
+    if (t == 0 && pass == MT_SEL_PASSES - 1) out[0] = (long long)n;
+}
+
 // ---- entries ------------------------------------------------------------------------------------------------------------------------------
 static bool mt_shape_ok(int D, int H, int W) {
     return D > 0 && H > 0 && W > 0 && D <= MT_MAXDIM && H <= MT_MAXDIM && W <= MT_MAXDIM && (long long)D * H * W < 0x7fffffffLL;
@@ -250,4 +422,35 @@ extern "C" int tc_metric_select(const unsigned int* hist, long long nbins, int n
     if (!hist || !out || nbins <= 0 || ncls <= 0 || ncls > MT_MAXCLS) return TC_ERR_ARG;
     hipLaunchKernelGGL(metric_select_kernel, dim3(ncls), dim3(256), 0, (hipStream_t)stream, hist, nbins, out);
     return tc_launch_status();
+}
+
+static bool mt_spacing_ok(double v) { return v > 0.0 && v < __builtin_huge_val(); }       // finite and > 0 (false for a NaN)
+
+extern "C" int tc_metric_edt_f64(const unsigned char* surf, int k, double* d2, int D, int H, int W, int zfaces, double sz, double sy, double sx,
+                                 void* stream) {
+    if (!surf || !d2 || !mt_shape_ok(D, H, W) || k <= 0 || k >= MT_MAXCLS || !mt_spacing_ok(sz) || !mt_spacing_ok(sy) || !mt_spacing_ok(sx))
+        return TC_ERR_ARG;
+    hipStream_t s = (hipStream_t)stream;
+    const int rows = D * H;
+    hipLaunchKernelGGL(metric_edt_x_f64_kernel, dim3((rows + 3) / 4), dim3(256), 0, s, surf, k, d2, rows, W, sx);
+    int rc = tc_launch_status();
+    if (rc == TC_OK) rc = mt_line_pass_f64(d2, D, H, W, sy, s);
+    if (rc == TC_OK && zfaces) rc = mt_line_pass_f64(d2, 1, D, (long long)H * W, sz, s);
+    return rc;
+}
+
+extern "C" int tc_metric_select_f64(const unsigned char* surf_pred, const unsigned char* surf_gt, const double* d2_pred, const double* d2_gt, int k,
+                                    int ncls, int D, int H, int W, void* work, long long* out, void* stream) {
+    if (!surf_pred || !surf_gt || !d2_pred || !d2_gt || !work || !out || !mt_shape_ok(D, H, W) || ncls <= 0 || ncls > MT_MAXCLS || k <= 0 || k >= ncls)
+        return TC_ERR_ARG;
+    hipStream_t s = (hipStream_t)stream;
+    if (hipMemsetAsync(work, 0, TC_METRIC_SELECT_WORK_BYTES, s) != hipSuccess) return TC_ERR_LAUNCH;
+    const int n = D * H * W, blocks = tc_blocks(n, 256, 2048);
+    for (int pass = 0; pass < MT_SEL_PASSES; ++pass) {
+        hipLaunchKernelGGL(metric_select_count_kernel, dim3(blocks), dim3(256), 0, s, surf_pred, surf_gt, d2_pred, d2_gt, k, (unsigned int*)work, pass, n);
+        hipLaunchKernelGGL(metric_select_scan_kernel, dim3(1), dim3(256), 0, s, (unsigned int*)work, pass, out + 3 * k);
+        const int rc = tc_launch_status();
+        if (rc != TC_OK) return rc;
+    }
+    return TC_OK;
 }

@@ -13,10 +13,13 @@ The metric (`calculate_metric_percase`, `utils.py:50-60`) has two forms.  The de
 surface voxels = mask minus its erosion (connectivity 1), distances by the Euclidean distance transform of the other mask's
 surface, 95th percentile of both directions pooled.  Parity with medpy itself is unpinned; tests pin it to a brute-force
 evaluation of that definition.  With `device_metrics=True` the prediction never leaves the GPU: `metrics_device` computes the
-Dice counts and the same HD95 (unit spacing, connectivity 1) exactly, in integers, with the kernels of csrc/metrics.hip -- surface
-maps, a separable squared Euclidean distance transform, a histogram of squared distances and its two order statistics -- and
-one small copy of (counts, n, d2_lo, d2_hi) per volume returns to the host, which takes the square roots.  Anisotropic
-`voxelspacing` exists on the host path only.
+Dice counts and the same HD95 (connectivity 1) with the kernels of csrc/metrics.hip -- surface maps, a separable squared Euclidean
+distance transform, the two order statistics of the squared distances met on the other surface -- and one small copy of
+(counts, n, d2_lo, d2_hi) per volume returns to the host, which takes the square roots.  Without `voxelspacing` (unit spacing)
+that is exact integer work: int32 maps and a histogram indexed by the squared distance.  With `voxelspacing` (medpy's argument:
+one positive float per array axis, or a scalar for all) the maps are float64 and the order statistics come from a radix select
+over the doubles' bit patterns; the sums of squares differ from scipy's by rounding only.  Both metric paths take it, through
+`calculate_metric_percase`, `evaluate_volume`, `inference` and `TrainConfig.voxelspacing`.
 """
 from __future__ import annotations
 
@@ -27,7 +30,7 @@ import math
 import numpy as np
 import torch
 
-from ._lib import TC_F32, lib
+from ._lib import TC_F32, TC_METRIC_SELECT_WORK_BYTES, lib
 
 NO_CPU = "transception_amd.evaluate runs on MI355X only (no CPU fallback)"
 
@@ -86,12 +89,12 @@ def hd95(result: np.ndarray, reference: np.ndarray, voxelspacing=None, connectiv
     return float(np.percentile(np.hstack((a, b)), 95))
 
 
-def calculate_metric_percase(pred: np.ndarray, gt: np.ndarray) -> Tuple[float, float]:
-    """(dice, hd95) of one class of one volume with the reference's conventions (utils.py:50-60)."""
+def calculate_metric_percase(pred: np.ndarray, gt: np.ndarray, voxelspacing=None) -> Tuple[float, float]:
+    """(dice, hd95) of one class of one volume with the reference's conventions (utils.py:50-60); `voxelspacing` as `hd95` takes it."""
     pred, gt = pred > 0, gt > 0
     ps, gs = int(pred.sum()), int(gt.sum())
     if ps > 0 and gs > 0:
-        return float(2.0 * np.logical_and(pred, gt).sum() / (ps + gs)), hd95(pred, gt)
+        return float(2.0 * np.logical_and(pred, gt).sum() / (ps + gs)), hd95(pred, gt, voxelspacing)
     if ps > 0:
         return 1.0, 0.0
     return 0.0, 0.0
@@ -110,11 +113,27 @@ def metrics_hist_bins(shape) -> int:
     return (D - 1) ** 2 + (H - 1) ** 2 + (W - 1) ** 2 + 1
 
 
-def metrics_scratch_bytes(shape, classes: int) -> int:
-    """What `metrics_device` allocates for one volume: two uint8 surface maps, two int32 squared-distance maps (one class at a time:
-    to the prediction's surface and to the ground truth's), the uint32 histograms [classes][bins] and the int64 result [2][classes][3]."""
+def _spacing3(voxelspacing, ndim: int) -> Tuple[float, float, float]:
+    """(sz, sy, sx) from medpy's `voxelspacing`: `ndim` floats in array axis order or one scalar for every axis, each finite and > 0
+    (sz = 1 for [H,W]: unused)."""
+    sp = np.asarray(voxelspacing, dtype=np.float64)
+    if sp.ndim == 0:
+        sp = np.full(ndim, float(sp))
+    if sp.shape != (ndim,):
+        raise ValueError(f"voxelspacing needs {ndim} components (one per array axis) or a scalar, got {voxelspacing!r}")
+    if not (np.isfinite(sp).all() and (sp > 0).all()):
+        raise ValueError(f"voxelspacing components must be finite and > 0, got {voxelspacing!r}")
+    return (1.0,) * (3 - ndim) + tuple(float(v) for v in sp)
+
+
+def metrics_scratch_bytes(shape, classes: int, voxelspacing=None) -> int:
+    """What `metrics_device` allocates for one volume: two uint8 surface maps, two squared-distance maps (one class at a time: to the
+    prediction's surface and to the ground truth's) and the int64 result [2][classes][3]; beside them, without spacing, int32 maps and
+    the uint32 histograms [classes][bins]; with spacing, float64 maps and the radix select's work buffer."""
     D, H, W = _shape3(shape)
     n = D * H * W
+    if voxelspacing is not None:
+        return 2 * n + 2 * 8 * n + TC_METRIC_SELECT_WORK_BYTES + 8 * 2 * classes * 3
     return 2 * n + 2 * 4 * n + 4 * classes * metrics_hist_bins(shape) + 8 * 2 * classes * 3
 
 
@@ -147,24 +166,48 @@ def surfaces_counts(pred: torch.Tensor, label: torch.Tensor, classes: int):
     return sp, sg, counts
 
 
-def edt_squared(surf: torch.Tensor, k: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """int32 map of the squared Euclidean distance to the nearest voxel with surf == k (TC_METRIC_NO_SOURCE everywhere if there is none)."""
+def edt_squared(surf: torch.Tensor, k: int, out: Optional[torch.Tensor] = None, voxelspacing=None) -> torch.Tensor:
+    """int32 map of the squared Euclidean distance to the nearest voxel with surf == k (TC_METRIC_NO_SOURCE everywhere if there is none).
+    With `voxelspacing`: the float64 map of min (sz dz)^2 + (sy dy)^2 + (sx dx)^2 (tc_metric_edt_f64; +inf everywhere if there is none)."""
     if not surf.is_cuda:
         raise RuntimeError(NO_CPU)
     D, H, W = _shape3(surf.shape)
+    if voxelspacing is not None:
+        sz, sy, sx = _spacing3(voxelspacing, surf.dim())
+        if out is None:
+            out = torch.empty(surf.shape, dtype=torch.float64, device=surf.device)
+        elif out.dtype != torch.float64 or out.shape != surf.shape or not out.is_contiguous():
+            raise ValueError("with voxelspacing `out` is a contiguous float64 map of surf's shape")
+        lib().tc_metric_edt_f64(surf.contiguous().data_ptr(), k, out.data_ptr(), D, H, W, int(surf.dim() == 3), sz, sy, sx,
+                                torch.cuda.current_stream(surf.device).cuda_stream)
+        return out
     if out is None:
         out = torch.empty(surf.shape, dtype=torch.int32, device=surf.device)
     lib().tc_metric_edt(surf.data_ptr(), k, out.data_ptr(), D, H, W, int(surf.dim() == 3), torch.cuda.current_stream(surf.device).cuda_stream)
     return out
 
 
-def metrics_order_stats(pred: torch.Tensor, label: torch.Tensor, classes: int) -> torch.Tensor:
+def metrics_order_stats(pred: torch.Tensor, label: torch.Tensor, classes: int, voxelspacing=None) -> torch.Tensor:
     """int64 [2,classes,3] on the device: [0] the Dice counts, [1] (n, d2_lo, d2_hi) per class (tc_metric_select).  Allocates
-    `metrics_scratch_bytes(pred.shape, classes)`; the two distance maps are reused class by class.  Nothing is synchronised."""
+    `metrics_scratch_bytes(pred.shape, classes, voxelspacing)`; the two distance maps are reused class by class.  Nothing is synchronised.
+    With `voxelspacing` d2_lo and d2_hi are doubles (tc_metric_select_f64): read them with `result[1, :, 1:].view(torch.float64)`."""
+    if voxelspacing is not None:
+        spacing = _spacing3(voxelspacing, pred.dim())
     sp, sg, counts = surfaces_counts(pred, label, classes)
     D, H, W = _shape3(pred.shape)
     dev = pred.device
     L, stream = lib(), torch.cuda.current_stream(dev).cuda_stream
+    if voxelspacing is not None:
+        work = torch.empty(TC_METRIC_SELECT_WORK_BYTES, dtype=torch.uint8, device=dev)
+        dp, dg = torch.empty(pred.shape, dtype=torch.float64, device=dev), torch.empty(pred.shape, dtype=torch.float64, device=dev)
+        res = torch.zeros((2, classes, 3), dtype=torch.int64, device=dev)             # class 0 is never selected: (0, 0.0, 0.0)
+        res[0] = counts
+        for k in range(1, classes):
+            edt_squared(sp, k, dp, spacing[3 - pred.dim():])
+            edt_squared(sg, k, dg, spacing[3 - pred.dim():])
+            L.tc_metric_select_f64(sp.data_ptr(), sg.data_ptr(), dp.data_ptr(), dg.data_ptr(), k, classes, D, H, W, work.data_ptr(),
+                                   res[1].data_ptr(), stream)
+        return res
     nbins = metrics_hist_bins(pred.shape)
     hist = torch.zeros((classes, nbins), dtype=torch.int32, device=dev)               # uint32 to the library
     dp, dg = torch.empty(pred.shape, dtype=torch.int32, device=dev), torch.empty(pred.shape, dtype=torch.int32, device=dev)
@@ -178,12 +221,22 @@ def metrics_order_stats(pred: torch.Tensor, label: torch.Tensor, classes: int) -
     return res
 
 
-def metrics_device(pred: torch.Tensor, label: torch.Tensor, classes: int = 9) -> List[Tuple[float, float]]:
+def _order_stats_to_host(res: torch.Tensor, spaced: bool):
+    """(counts, [(n, d2_lo, d2_hi)]) as Python numbers from `metrics_order_stats`' tensor: one copy."""
+    res = res.cpu()
+    counts, sel = res[0].tolist(), res[1].tolist()
+    if spaced:
+        sel = [(n, lo, hi) for (n, _, _), (lo, hi) in zip(sel, res[1, :, 1:].contiguous().view(torch.float64).tolist())]
+    return counts, sel
+
+
+def metrics_device(pred: torch.Tensor, label: torch.Tensor, classes: int = 9, voxelspacing=None) -> List[Tuple[float, float]]:
     """`calculate_metric_percase` (utils.py:50-60) for classes 1..classes-1 of two uint8 CUDA label volumes [D,H,W] ([H,W]: true 2-D, no z
-    faces), unit spacing, connectivity 1: [(dice, hd95)].  Exact integer work on the device (csrc/metrics.hip), one copy of 6 * classes
-    integers back; scratch: `metrics_scratch_bytes` (10 bytes a voxel plus the histograms).  The library takes D, H, W up to 2048 and
-    fewer than 2^31 voxels; a larger volume raises `TcError`."""
-    counts, sel = metrics_order_stats(pred, label, classes).cpu().tolist()
+    faces), connectivity 1: [(dice, hd95)].  Unit spacing: exact integer work on the device (csrc/metrics.hip), one copy of 6 * classes
+    integers back; scratch: `metrics_scratch_bytes` (10 bytes a voxel plus the histograms).  `voxelspacing` (`pred.dim()` positive floats in
+    array axis order, or a scalar): the fp64 kernels, 18 bytes a voxel.  The library takes D, H, W up to 2048 and fewer than 2^31 voxels;
+    a larger volume raises `TcError`."""
+    counts, sel = _order_stats_to_host(metrics_order_stats(pred, label, classes, voxelspacing), voxelspacing is not None)
     out = []
     for (inter, p, g), (n, lo, hi) in zip(counts[1:], sel[1:]):
         if p > 0 and g > 0:
@@ -195,11 +248,12 @@ def metrics_device(pred: torch.Tensor, label: torch.Tensor, classes: int = 9) ->
     return out
 
 
-def hd95_device(result: torch.Tensor, reference: torch.Tensor) -> float:
-    """`hd95(result, reference)` with its defaults for two boolean / uint8 CUDA masks, on the device."""
+def hd95_device(result: torch.Tensor, reference: torch.Tensor, voxelspacing=None) -> float:
+    """`hd95(result, reference, voxelspacing)` (connectivity 1) for two boolean / uint8 CUDA masks, on the device."""
     if not (result.is_cuda and reference.is_cuda):
         raise RuntimeError(NO_CPU)
-    counts, sel = metrics_order_stats((result != 0).to(torch.uint8), (reference != 0).to(torch.uint8), 2).cpu().tolist()
+    counts, sel = _order_stats_to_host(metrics_order_stats((result != 0).to(torch.uint8), (reference != 0).to(torch.uint8), 2, voxelspacing),
+                                       voxelspacing is not None)
     if counts[1][1] == 0 or counts[1][2] == 0:
         raise RuntimeError("surface distances need non-empty masks")
     return hd95_from_order_stats(*sel[1])
@@ -254,12 +308,13 @@ def zoom_labels(pred: torch.Tensor, size: Tuple[int, int]) -> torch.Tensor:
 
 @torch.no_grad()
 def evaluate_volume(model, image: np.ndarray, label: np.ndarray, classes: int = 9, patch_size=(224, 224),
-                    batch: int = 16, with_hd95: bool = False, host_zoom: bool = False, device_metrics: bool = False):
+                    batch: int = 16, with_hd95: bool = False, host_zoom: bool = False, device_metrics: bool = False, voxelspacing=None):
     """`test_single_volume` for one [D,H,W] volume (utils.py:63-98): per-class Dice for classes 1..classes-1, or with
     `with_hd95` the reference's metric_list of (dice, hd95) pairs.  The volume goes to the GPU once; the order-3 zoom to the network
     size, inference, argmax and the order-0 zoom back all run there (host_zoom=True: scipy per slice, as the reference does).
     `device_metrics=True`: the prediction stays on the GPU, the label volume is uploaded once and `metrics_device` (with_hd95) or the
-    counts of its first kernel (Dice only) replace the host metric; same returned structure."""
+    counts of its first kernel (Dice only) replace the host metric; same returned structure.  `voxelspacing`: the (z, y, x) size of a voxel
+    of `label`, for the HD95 of either metric path (Dice does not depend on it)."""
     dev = next(model.parameters()).device
     if device_metrics and dev.type != "cuda":
         raise RuntimeError(NO_CPU)
@@ -282,10 +337,10 @@ def evaluate_volume(model, image: np.ndarray, label: np.ndarray, classes: int = 
         pred_t = torch.from_numpy(pred).to(dev) if host_zoom else pred
         label_t = torch.from_numpy(np.ascontiguousarray(label).astype(np.uint8)).to(dev)
         if with_hd95:
-            return metrics_device(pred_t, label_t, classes)
+            return metrics_device(pred_t, label_t, classes, voxelspacing)
         return dice_from_counts(surfaces_counts(pred_t, label_t, classes)[2].cpu().numpy())
     if with_hd95:
-        return [calculate_metric_percase(pred == k, label == k) for k in range(1, classes)]
+        return [calculate_metric_percase(pred == k, label == k, voxelspacing) for k in range(1, classes)]
     counts = np.zeros((classes, 3), dtype=np.float64)
     for k in range(classes):
         p, g = pred == k, label == k
@@ -294,13 +349,13 @@ def evaluate_volume(model, image: np.ndarray, label: np.ndarray, classes: int = 
 
 
 def inference(model, volumes, classes: int = 9, img_size: int = 224, batch: int = 16, log=None,
-              device_metrics: bool = False) -> Tuple[float, float]:
+              device_metrics: bool = False, voxelspacing=None) -> Tuple[float, float]:
     """trainer.py:25-47: mean Dice and mean HD95 over `volumes` = iterable of (image [D,H,W] in [0,1], label [D,H,W], case name).
-    `device_metrics`: as in `evaluate_volume`."""
+    `device_metrics`, `voxelspacing` (one spacing for every volume): as in `evaluate_volume`."""
     total, n = 0.0, 0
     for i, (image, label, name) in enumerate(volumes):
         m = np.array(evaluate_volume(model, np.asarray(image), np.asarray(label), classes, (img_size, img_size), batch, with_hd95=True,
-                                     device_metrics=device_metrics))
+                                     device_metrics=device_metrics, voxelspacing=voxelspacing))
         total = total + m
         n += 1
         if log:

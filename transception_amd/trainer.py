@@ -44,6 +44,7 @@ class TrainConfig:
     augment: bool = True
     graphed: bool = True               # replay the captured step (hipGraph); False launches every kernel from Python
     device_metrics: bool = False       # Dice / HD95 of the evaluation on the GPU (evaluate.metrics_device) instead of scipy on the host
+    voxelspacing: Optional[tuple] = None   # (z, y, x) voxel size for the HD95 of the evaluation, on either metric path; None: in voxels
     log_every: int = 1                 # iterations between log lines (each one reads three scalars back from the GPU)
 
 
@@ -146,7 +147,8 @@ def trainer_synapse(cfg: TrainConfig, model, snapshot_path: str, volumes: Option
                     if vols:
                         if rank == 0:
                             log(f"Running Inference after epoch {epoch_num}")
-                        mean_dice, mean_hd95 = inference(model, vols, cfg.num_classes, cfg.img_size, log=log, device_metrics=cfg.device_metrics)
+                        mean_dice, mean_hd95 = inference(model, vols, cfg.num_classes, cfg.img_size, log=log, device_metrics=cfg.device_metrics,
+                                                        voxelspacing=cfg.voxelspacing)
                         res[0], res[1], res[2] = mean_dice * len(vols), mean_hd95 * len(vols), len(vols)
                         model.train()
                     if distributed:
