@@ -762,6 +762,28 @@ int tc_sgd_step(float* p, const float* grad, float* buf, long long n, float lr, 
 int tc_sgd_step_multi(float* p, const float* grad, float* buf, const long long* segs_dev, int nseg, long long max_len,
                       float lr, const float* lr_dev, float momentum, float wd, float gscale, int first, const float* clip_sumsq,
                       float clip_norm, void* lp, int lp_dtype, void* stream);
+/* ---- Dynamic loss scaling for float16 storage, entirely on the device (nothing here synchronises, allocates or reads back).
+ * A LOSS-SCALE STATE is four 32-bit words in device memory, owned by the caller:
+ *     [0] fp32   scale                      (the loss gradient is multiplied by it: hand &state[0] to tc_seg_loss_bwd* as gscale_dev)
+ *     [1] fp32   1 / scale                  (rewritten whenever the scale is)
+ *     [2] int32  growth tracker: clean steps since the scale last changed
+ *     [3] int32  updates skipped so far
+ *
+ * tc_sgd_step_multi_scaled = tc_sgd_step_multi on gradients that carry the state's scale: gscale is multiplied by state[1], and the
+ * clip coefficient is min(1, clip_norm * state[0] / (sqrt(*clip_sumsq) + 1e-6)), so clip_norm bounds the norm of the TRUE gradient.
+ * clip_sumsq is mandatory (TC_ERR_ARG without it; clip_norm = inf for no clipping): a non-finite *clip_sumsq leaves p, buf and lp as
+ * they were, exactly as in tc_sgd_step_multi.  With scale a power of two the result is bit-equal to tc_sgd_step_multi called with
+ * gscale / scale and clip_norm * scale. */
+int tc_sgd_step_multi_scaled(float* p, const float* grad, float* buf, const long long* segs_dev, int nseg, long long max_len,
+                             float lr, const float* lr_dev, float momentum, float wd, float gscale, int first,
+                             const float* clip_sumsq, float clip_norm, void* lp, int lp_dtype, const float* scale_state, void* stream);
+/* The scale's own step, launched after the update kernel of the same training step; *sumsq is what tc_grad_sumsq left.
+ *     *sumsq not finite (inf or NaN):  scale = max(scale * backoff, min_scale) ; tracker = 0 ; skipped += 1
+ *     *sumsq finite:                   tracker += 1 ; when it reaches interval:  scale = min(scale * growth, max_scale) ; tracker = 0
+ * and state[1] = 1 / scale.  This is torch.amp.GradScaler.update's rule with the two clamps added.
+ * growth >= 1, 0 < backoff < 1, interval >= 1, 0 < min_scale <= max_scale, all finite (TC_ERR_ARG otherwise). */
+int tc_loss_scale_update(float* state, const float* sumsq, float growth, float backoff, int interval, float min_scale,
+                         float max_scale, void* stream);
 /* *out += sum_i g[i]^2 over a flat fp32 buffer (n a multiple of 4, 16-byte aligned): the squared total gradient norm. */
 int tc_grad_sumsq(const float* g, long long n, float* out, void* stream);
 /* p[0..n) = v (fp32): resets device accumulators inside a captured step */

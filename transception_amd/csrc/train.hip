@@ -184,13 +184,20 @@ __global__ __launch_bounds__(256) void sumsq_kernel(const float* __restrict__ g,
 
 __global__ void sgd_multi_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf, const long long* __restrict__ segs,
                                  float lr, float mom, float wd, float gscale, int first, const float* __restrict__ lr_dev,
-                                 const float* __restrict__ clip_sumsq, float clip_norm, void* __restrict__ lp, int lp_dtype) {
+                                 const float* __restrict__ clip_sumsq, float clip_norm, void* __restrict__ lp, int lp_dtype,
+                                 const float* __restrict__ scale_state) {
     if (lr_dev) lr = *lr_dev;
     if (clip_sumsq) {
+        // a non-finite gradient (float16 overflow under a loss scale): skip the update -- weights, momentum and the 16-bit copy stay as
+        // they were.  Otherwise clip_grad_norm_'s coefficient, clamped to 1 (clip_norm = inf: no clipping)
         const float ss = *clip_sumsq;
-        if (!(ss < __builtin_inff())) return;                     // a non-finite gradient (float16 overflow under a static loss scale): skip the
-        gscale *= fminf(clip_norm / (sqrtf(ss) + 1e-6f), 1.0f);   // update -- weights, momentum and the 16-bit copy stay as they were.  Otherwise
-    }                                                             // clip_grad_norm_'s coefficient, clamped to 1 (clip_norm = inf: no clipping)
+        if (!(ss < __builtin_inff())) return;
+        if (scale_state) {                    // dynamic loss scale (tc_sgd_step_multi_scaled): the arena holds gradients `scale` times too
+            gscale *= scale_state[1];         // large, so 1 / scale takes it out again and the threshold is raised by `scale`: what is clipped
+            clip_norm *= scale_state[0];      // is the norm of the TRUE gradient
+        }
+        gscale *= fminf(clip_norm / (sqrtf(ss) + 1e-6f), 1.0f);
+    }
     const long long off = segs[2 * blockIdx.y], n = segs[2 * blockIdx.y + 1];
     if (!((off | n) & 3) && !(((uintptr_t)p | (uintptr_t)g | (uintptr_t)buf) & 15) && !((uintptr_t)lp & 7)) {
         // four elements per thread in 16-byte pieces (the arena's segments start and end on multiples of 8 elements): the scalar form
@@ -264,6 +271,28 @@ __global__ __launch_bounds__(256) void argmax_counts_kernel(const T* __restrict_
     for (int k = 0; k < 3 * MAXCLS; ++k) if (k < 3 * ncls) { const float a = wave_sum(cnt[k]); if (lane == 0) red[wave][k] = a; }
     __syncthreads();
     if (threadIdx.x < 3 * ncls) atomicAdd(counts + threadIdx.x, red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x]);
+}
+
+// torch.amp.GradScaler.update's rule on the four words of a loss-scale state (include/transception_hip.h), with two clamps added.
+// One thread: four loads, a handful of flops, four ordinary stores.
+__global__ void loss_scale_update_kernel(float* __restrict__ state, const float* __restrict__ sumsq, float growth, float backoff, int interval,
+                                         float min_scale, float max_scale) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    int* istate = reinterpret_cast<int*>(state);
+    float scale = state[0];
+    int tracker = istate[2], skipped = istate[3];
+    if (!(*sumsq < __builtin_inff())) {                           // inf or NaN: the update kernel skipped this step
+        scale = fmaxf(scale * backoff, min_scale);
+        tracker = 0;
+        ++skipped;
+    } else if (++tracker >= interval) {                           // (== for a tracker that counts up from 0; >= so that a loaded tracker beyond
+        scale = fminf(scale * growth, max_scale);                 //  the interval grows at once instead of counting round the integers)
+        tracker = 0;
+    }
+    state[0] = scale;
+    state[1] = 1.f / scale;
+    istate[2] = tracker;
+    istate[3] = skipped;
 }
 
 __global__ void zero_floats_kernel(float* __restrict__ p, int n) {
@@ -370,7 +399,28 @@ extern "C" int tc_sgd_step_multi(float* p, const float* grad, float* buf, const 
         (lp && lp_dtype != TC_BF16 && lp_dtype != TC_F16))
         return TC_ERR_ARG;
     hipLaunchKernelGGL(sgd_multi_kernel, dim3(tc_blocks(max_len, 256 * 8, 256), nseg), dim3(256), 0, (hipStream_t)stream, p, grad, buf, segs_dev,
-                       lr, momentum, wd, gscale, first, lr_dev, clip_sumsq, clip_norm, lp, lp ? lp_dtype : -1);
+                       lr, momentum, wd, gscale, first, lr_dev, clip_sumsq, clip_norm, lp, lp ? lp_dtype : -1, (const float*)nullptr);
+    return tc_launch_status();
+}
+
+extern "C" int tc_sgd_step_multi_scaled(float* p, const float* grad, float* buf, const long long* segs_dev, int nseg, long long max_len, float lr,
+                                        const float* lr_dev, float momentum, float wd, float gscale, int first, const float* clip_sumsq,
+                                        float clip_norm, void* lp, int lp_dtype, const float* scale_state, void* stream) {
+    if (!p || !grad || !buf || !segs_dev || nseg <= 0 || nseg > 65535 || max_len <= 0 || !clip_sumsq || !scale_state || !(clip_norm > 0.f) ||
+        (lp && lp_dtype != TC_BF16 && lp_dtype != TC_F16))
+        return TC_ERR_ARG;
+    hipLaunchKernelGGL(sgd_multi_kernel, dim3(tc_blocks(max_len, 256 * 8, 256), nseg), dim3(256), 0, (hipStream_t)stream, p, grad, buf, segs_dev,
+                       lr, momentum, wd, gscale, first, lr_dev, clip_sumsq, clip_norm, lp, lp ? lp_dtype : -1, scale_state);
+    return tc_launch_status();
+}
+
+extern "C" int tc_loss_scale_update(float* state, const float* sumsq, float growth, float backoff, int interval, float min_scale,
+                                    float max_scale, void* stream) {
+    if (!state || !sumsq || !(growth >= 1.f) || !(growth < __builtin_inff()) || !(backoff > 0.f) || !(backoff < 1.f) || interval < 1 ||
+        !(min_scale > 0.f) || !(max_scale >= min_scale) || !(max_scale < __builtin_inff()))
+        return TC_ERR_ARG;
+    hipLaunchKernelGGL(loss_scale_update_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, state, sumsq, growth, backoff, interval, min_scale,
+                       max_scale);
     return tc_launch_status();
 }
 

@@ -467,8 +467,9 @@ class MSTransception(nn.Module):
     # ------------------------------------------------------------------ flat parameter / gradient arenas
     def set_compute_dtype(self, dtype: torch.dtype):
         """Storage type of activations and of the working copy of the weights: float32 (the parity path), bfloat16, or float16 (IEEE
-        half, BASELINE config 5; train it with a loss scale -- train.SegLoss(loss_scale=...) -- because activation gradients of
-        order 1e-6 underflow in half precision).  Master weights, gradients, statistics and accumulators stay fp32 in every mode."""
+        half, BASELINE config 5; train it with a loss scale -- train.SegLoss(loss_scale=...), a number or a self-adjusting
+        train.DynamicLossScale(); trainer.TrainConfig(loss_scale="dynamic") -- because activation gradients of order 1e-6 underflow in
+        half precision).  Master weights, gradients, statistics and accumulators stay fp32 in every mode."""
         assert dtype in (torch.float32, torch.bfloat16, torch.float16)
         if dtype != self.compute_dtype:
             self._flat_lp = None

@@ -13,7 +13,7 @@ from __future__ import annotations
 
 import math
 import os
-from typing import Optional
+from typing import Optional, Union
 
 import torch
 import torch.distributed as dist
@@ -63,6 +63,99 @@ def loss_from_sums(sums: torch.Tensor, n_pix: float, w_ce: float, w_dice: float)
     return w_ce * ce + w_dice * dice, ce, dice
 
 
+class DynamicLossScale:
+    """A loss scale for float16 storage that lives in device memory and tunes itself from inside the (captured) step.
+
+    The rule is torch.amp.GradScaler.update's, with two clamps added: a step whose squared gradient norm is not finite is skipped
+    (FusedSGD) and multiplies the scale by `backoff_factor`, never below `min_scale`; `growth_interval` clean steps in a row multiply
+    it by `growth_factor`, never above `max_scale`.  Unlike GradScaler nothing is read back on the host: the state is four 32-bit
+    words on the device (include/transception_hip.h: scale, 1 / scale, growth tracker, skipped count), the loss backward multiplies by
+    word 0, tc_sgd_step_multi_scaled divides by it through word 1, and tc_loss_scale_update -- one single-thread launch after the
+    update -- applies the rule.  A GraphedStep therefore carries the scale, the skip and the adjustment in its replayed graph.
+
+    Several GPUs: the squared norm is taken AFTER the gradient all-reduce, so every rank sees the same value -- inf or NaN included
+    when only one rank overflowed, since a sum with a non-finite term is not finite.  Every rank makes the same decision from the
+    same number and keeps the same scale: no collective of its own is needed.
+
+    Pass it as SegLoss(loss_scale=DynamicLossScale()); train_step / GraphedStep hand it to the optimiser.  The device state is created
+    on the first device it meets.  value(), skipped() and state_dict() read it back: each is a host sync, for log lines and
+    checkpoints, not for the step."""
+
+    def __init__(self, init_scale: float = 65536.0, growth_factor: float = 2.0, backoff_factor: float = 0.5, growth_interval: int = 2000,
+                 min_scale: float = 1.0, max_scale: float = 2.0 ** 24):
+        vals = dict(init_scale=init_scale, growth_factor=growth_factor, backoff_factor=backoff_factor, min_scale=min_scale, max_scale=max_scale)
+        for k, v in vals.items():
+            if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v):
+                raise ValueError(f"{k} must be a finite number, got {v!r}")
+        if isinstance(growth_interval, bool) or not isinstance(growth_interval, int) or not 1 <= growth_interval < 2 ** 31:
+            raise ValueError(f"growth_interval must be an integer >= 1, got {growth_interval!r}")
+        if not growth_factor >= 1.0:
+            raise ValueError(f"growth_factor must be >= 1, got {growth_factor!r}")
+        if not 0.0 < backoff_factor < 1.0:
+            raise ValueError(f"backoff_factor must lie in (0, 1), got {backoff_factor!r}")
+        if not 0.0 < min_scale <= init_scale <= max_scale:
+            raise ValueError(f"need 0 < min_scale <= init_scale <= max_scale, got {min_scale!r}, {init_scale!r}, {max_scale!r}")
+        self.growth_factor, self.backoff_factor, self.growth_interval = float(growth_factor), float(backoff_factor), growth_interval
+        self.min_scale, self.max_scale = float(min_scale), float(max_scale)
+        self._host = (float(init_scale), 0, 0)           # (scale, tracker, skipped) until the device state exists
+        self._state: Optional[torch.Tensor] = None       # fp32[4]; words 2 and 3 are int32
+
+    def _words(self, scale: float, tracker: int, skipped: int) -> torch.Tensor:
+        w = torch.zeros(4, dtype=torch.float32)
+        w[0], w[1] = scale, 1.0 / scale
+        w.view(torch.int32)[2], w.view(torch.int32)[3] = tracker, skipped
+        return w
+
+    def state(self, device) -> torch.Tensor:
+        """The four-word device state (created on first use).  Its address is baked into captured launches: it is never replaced."""
+        if self._state is None:
+            self._state = self._words(*self._host).to(device)
+        elif (d := torch.device(device)).type != self._state.device.type or d.index not in (None, self._state.device.index):
+            raise RuntimeError(f"this DynamicLossScale lives on {self._state.device}, not {device}: use one per device")
+        return self._state
+
+    def update(self, sumsq: torch.Tensor):
+        """The rule's step from the squared gradient norm of the step just taken (FusedSGD.step calls it): one launch, no sync."""
+        st = self.state(sumsq.device)
+        lib().tc_loss_scale_update(st.data_ptr(), sumsq.data_ptr(), self.growth_factor, self.backoff_factor, self.growth_interval,
+                                   self.min_scale, self.max_scale, torch.cuda.current_stream(sumsq.device).cuda_stream)
+
+    def state_dict(self) -> dict:
+        """{"scale", "growth_tracker", "skipped"}.  Reads the device state back once it exists: a host sync."""
+        if self._state is not None:
+            w = self._state.cpu()
+            self._host = (float(w[0]), int(w.view(torch.int32)[2]), int(w.view(torch.int32)[3]))
+        return {"scale": self._host[0], "growth_tracker": self._host[1], "skipped": self._host[2]}
+
+    def load_state_dict(self, sd: dict):
+        """Writes an existing device state IN PLACE: a captured step has its address in its launches and sees the new value on the
+        next replay (a fresh tensor would leave the graph reading the old one)."""
+        scale, tracker, skipped = float(sd["scale"]), int(sd.get("growth_tracker", 0)), int(sd.get("skipped", 0))
+        if not (math.isfinite(scale) and scale > 0.0) or tracker < 0 or skipped < 0:
+            raise ValueError(f"bad loss-scale state {sd!r}")
+        self._host = (scale, tracker, skipped)
+        if self._state is not None:
+            self._state.copy_(self._words(*self._host))
+
+    def value(self) -> float:
+        """The current scale.  A host sync."""
+        return self.state_dict()["scale"]
+
+    def skipped(self) -> int:
+        """Updates skipped so far, counted on the device by every step (not only those a log line looked at).  A host sync."""
+        return self.state_dict()["skipped"]
+
+
+def _wire_loss_scale(loss_fn, opt, device) -> None:
+    """The optimiser takes out the scale the loss puts in: a static one as grad_scale, a DynamicLossScale through its device state."""
+    ls = getattr(loss_fn, "loss_scale", 1.0)
+    if isinstance(ls, DynamicLossScale):
+        ls.state(device)                                  # exists before anything is captured
+        opt.loss_scaler, opt.grad_scale = ls, 1.0
+    else:
+        opt.loss_scaler, opt.grad_scale = None, 1.0 / ls
+
+
 class _SegLossFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, logits, labels, ncls, w_ce, w_dice, group, loss_scale=1.0):
@@ -78,7 +171,7 @@ class _SegLossFn(torch.autograd.Function):
         sums, n_pix, world = seg_sums_allreduce(sums, float(B * H * W), group)
         loss, ce, dice = loss_from_sums(sums, n_pix, w_ce, w_dice)
         ctx.save_for_backward(prob, labels, sums)
-        ctx.meta = (ncls, w_ce, w_dice, n_pix, world, logits.dtype, float(loss_scale))
+        ctx.meta = (ncls, w_ce, w_dice, n_pix, world, logits.dtype, loss_scale if isinstance(loss_scale, DynamicLossScale) else float(loss_scale))
         return loss.float(), ce.float(), dice.float()
 
     @staticmethod
@@ -92,6 +185,9 @@ class _SegLossFn(torch.autograd.Function):
         # gradients of the *global* loss w.r.t. local logits; the later gradient all-reduce SUMS ranks, so the usual
         # DDP mean is folded in by the caller (gscale).  gloss is 1 for a plain loss.backward().
         gl = gloss.detach().float().contiguous()             # upstream d(loss) stays on the device: no host sync
+        if isinstance(loss_scale, DynamicLossScale):         # ... times the device scale: a one-element product, still no host sync
+            gl = (gl * loss_scale.state(prob.device)[0]).reshape(1)
+            loss_scale = 1.0
         L.tc_seg_loss_bwd(prob.data_ptr(), labels.data_ptr(), sums.data_ptr(), d.data_ptr(), B, ncls, H * W, float(w_ce), float(w_dice),
                           float(n_pix), loss_scale, gl.data_ptr(), _dt(d), stream)
         return d, None, None, None, None, None, None
@@ -100,11 +196,14 @@ class _SegLossFn(torch.autograd.Function):
 class SegLoss(torch.nn.Module):
     """0.4*CE + 0.6*Dice over the (global) batch; returns (loss, ce, dice)."""
 
-    def __init__(self, n_classes: int = 9, w_ce: float = 0.4, w_dice: float = 0.6, group=None, loss_scale: float = 1.0):
-        """loss_scale: the gradient that leaves this loss is multiplied by it (the reported loss is not) -- static loss scaling for
-        float16 storage; FusedSGD.step divides it out again (train_step wires the two together)."""
+    def __init__(self, n_classes: int = 9, w_ce: float = 0.4, w_dice: float = 0.6, group=None,
+                 loss_scale: Union[float, DynamicLossScale] = 1.0):
+        """loss_scale: the gradient that leaves this loss is multiplied by it (the reported loss is not) -- loss scaling for float16
+        storage; FusedSGD.step divides it out again (train_step wires the two together).  A float is a static scale; a
+        DynamicLossScale is read from device memory by the backward kernel and adjusts itself after every update."""
         super().__init__()
-        self.n_classes, self.w_ce, self.w_dice, self.group, self.loss_scale = n_classes, w_ce, w_dice, group, float(loss_scale)
+        self.n_classes, self.w_ce, self.w_dice, self.group = n_classes, w_ce, w_dice, group
+        self.loss_scale = loss_scale if isinstance(loss_scale, DynamicLossScale) else float(loss_scale)
 
     def forward(self, logits: torch.Tensor, labels: torch.Tensor):
         return _SegLossFn.apply(logits, labels.long(), self.n_classes, self.w_ce, self.w_dice, self.group, self.loss_scale)
@@ -132,11 +231,12 @@ class FusedSGD:
         self._sumsq: Optional[torch.Tensor] = None       # squared gradient norm (clip_norm)
         self.grad_scale = 1.0                            # gradients in the arena are this many times too small (1 / loss scale)
         self.guard_overflow: Optional[bool] = None       # skip the update when the gradient norm is not finite; None: on for float16 storage
+        self.loss_scaler: Optional[DynamicLossScale] = None   # gradients carry its device scale instead (the guard is then always on)
 
         self.skipped_steps = 0                           # updates found skipped by last_step_skipped() (read back at the caller's log cadence)
 
     def last_step_skipped(self) -> bool:
-        """True when the last update was skipped because the gradient norm was not finite (float16 overflow under a static loss scale:
+        """True when the last update was skipped because the gradient norm was not finite (float16 overflow under a loss scale:
         sgd_multi_kernel returns without touching the weights).  Reads one float back (a host sync): call it where the loop already
         reads its loss scalars; a run whose every step overflows would otherwise look like a plateau."""
         if self._sumsq is None:
@@ -182,7 +282,8 @@ class FusedSGD:
             self._segs_dev = torch.tensor([v for s in segs for v in s], dtype=torch.int64, device=flat.device)
             self._nseg, self._maxlen = len(segs), max(n for _, n in segs)
         sumsq = None
-        guard = self.guard_overflow if self.guard_overflow is not None else M.compute_dtype == torch.float16
+        scaler = self.loss_scaler
+        guard = scaler is not None or (self.guard_overflow if self.guard_overflow is not None else M.compute_dtype == torch.float16)
         if self.clip_norm or guard:
             # clip_grad_norm_(max_norm, 2): one reduction kernel for the squared norm (grad-less parameters hold zeros, so the arena's
             # norm is the model's), the coefficient min(1, max_norm / (norm + 1e-6)) is applied inside the update kernel
@@ -193,10 +294,19 @@ class FusedSGD:
             sumsq = self._sumsq.data_ptr()
         # the 16-bit working copy of the weights is refreshed by the same kernel (the forward then skips its cast pass over the arena)
         lp = M._flat_lp if (M.compute_dtype != torch.float32 and M._flat_lp is not None and M._flat_lp.dtype == M.compute_dtype) else None
-        L.tc_sgd_step_multi(flat.data_ptr(), g.data_ptr(), self.buf.data_ptr(), self._segs_dev.data_ptr(), self._nseg, self._maxlen,
-                            float(self.lr), self.lr_dev.data_ptr(), float(self.momentum), float(self.wd), float(grad_scale),
-                            int(self.steps == 0), sumsq, float((self.clip_norm or math.inf) / grad_scale),
-                            lp.data_ptr() if lp is not None else None, M._tc_dtype() if lp is not None else 0, stream)
+        # `first` is baked into a captured kernel's arguments, and a skipped first step is harmless all the same: the momentum buffer
+        # starts as zeros, so the later form mom * 0 + d equals the first-step form d
+        args = (flat.data_ptr(), g.data_ptr(), self.buf.data_ptr(), self._segs_dev.data_ptr(), self._nseg, self._maxlen,
+                float(self.lr), self.lr_dev.data_ptr(), float(self.momentum), float(self.wd), float(grad_scale),
+                int(self.steps == 0), sumsq, float((self.clip_norm or math.inf) / grad_scale),
+                lp.data_ptr() if lp is not None else None, M._tc_dtype() if lp is not None else 0)
+        if scaler is None:
+            L.tc_sgd_step_multi(*args, stream)
+        else:
+            # the arena's gradients carry the device scale (grad_scale is 1 here): the kernel divides it out and clips the true norm,
+            # then the scale takes its own step from the same squared norm
+            L.tc_sgd_step_multi_scaled(*args, scaler.state(flat.device).data_ptr(), stream)
+            scaler.update(self._sumsq)
         M._lp_fresh = lp is not None
         self.steps += 1
 
@@ -399,7 +509,7 @@ def allreduce_gradients(model, group=None, part: Optional[str] = None, async_op:
 def train_step(model, loss_fn: SegLoss, opt: FusedSGD, images: torch.Tensor, labels: torch.Tensor, group=None):
     """One step with trainer.py semantics; returns (loss, ce, dice) tensors (no host sync)."""
     opt.zero_grad()
-    opt.grad_scale = 1.0 / getattr(loss_fn, "loss_scale", 1.0)
+    _wire_loss_scale(loss_fn, opt, images.device)
     logits = model(images)
     loss, ce, dice = loss_fn(logits, labels)
     loss.backward()
@@ -471,7 +581,7 @@ class GraphedStep:
         self._pre = pre
         self.x, self.y = images.clone(), labels.clone().long().contiguous()
         self._dtype = model.compute_dtype                # the captured launches hold pointers into this storage type's working copy
-        opt.grad_scale = 1.0 / getattr(loss_fn, "loss_scale", 1.0)
+        _wire_loss_scale(loss_fn, opt, images.device)
         self.distributed = comm_on(group)
         self.split = self.distributed or force_split
         side = torch.cuda.Stream()
@@ -560,8 +670,11 @@ class GraphedStep:
         # the gradient of the token-major logits, in the logits' own layout (their rows are padded to 16 bytes when the fused LayerNorm +
         # classifier produced them: Graph.ln_cls)
         d = torch.empty((B * H * W, lg.stride(0)), dtype=self.model.compute_dtype, device=lg.device)[:, :C]
+        # a DynamicLossScale is read from its device state (word 0) by the kernel: the scale of every replay is the one the last left
+        dyn = isinstance(lf.loss_scale, DynamicLossScale)
         L.tc_seg_loss_bwd_tok(None, lg.data_ptr(), lg.stride(0), self.y.data_ptr(), self._sums.data_ptr(), d.data_ptr(), d.stride(0), B, C, H * W,
-                              float(lf.w_ce), float(lf.w_dice), float(self._npix), float(lf.loss_scale), None, _dt(d), stream)
+                              float(lf.w_ce), float(lf.w_dice), float(self._npix), 1.0 if dyn else float(lf.loss_scale),
+                              lf.loss_scale.state(lg.device).data_ptr() if dyn else None, _dt(d), stream)
         M._backward(self._G, self._out_var, d, until="encoder_done")     # loss gradient, decoders, bridge
 
     def _bwd_leg(self, until: Optional[str]):

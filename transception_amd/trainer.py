@@ -15,16 +15,17 @@ Not kept: TensorBoard writers and the matplotlib/CSV result plots (:216-237).
 from __future__ import annotations
 
 import logging
+import math
 import os
 from dataclasses import dataclass
-from typing import Callable, List, Optional
+from typing import Callable, List, Optional, Union
 
 import torch
 import torch.distributed as dist
 
 from .data import DeviceLoader, SynapseSlices
 from .evaluate import inference
-from .train import FusedSGD, GraphedStep, SegLoss, cosine_lr, train_step
+from .train import DynamicLossScale, FusedSGD, GraphedStep, SegLoss, cosine_lr, train_step
 
 
 @dataclass
@@ -46,6 +47,22 @@ class TrainConfig:
     device_metrics: bool = False       # Dice / HD95 of the evaluation on the GPU (evaluate.metrics_device) instead of scipy on the host
     voxelspacing: Optional[tuple] = None   # (z, y, x) voxel size for the HD95 of the evaluation, on either metric path; None: in voxels
     log_every: int = 1                 # iterations between log lines (each one reads three scalars back from the GPU)
+    loss_scale: Union[None, float, str] = None   # float16 storage: None = no scale (1), a number = static scale, "dynamic" = a default
+                                       # train.DynamicLossScale (device-resident, adjusts itself inside the captured step)
+
+    def __post_init__(self):
+        make_loss_scale(self.loss_scale)
+
+
+def make_loss_scale(spec) -> Union[float, DynamicLossScale]:
+    """TrainConfig.loss_scale -> what SegLoss takes.  Anything but None, a positive finite number or "dynamic" is a ValueError."""
+    if spec is None:
+        return 1.0
+    if spec == "dynamic":
+        return DynamicLossScale()
+    if isinstance(spec, (int, float)) and not isinstance(spec, bool) and math.isfinite(spec) and spec > 0:
+        return float(spec)
+    raise ValueError(f'loss_scale must be None, a positive finite number or "dynamic", got {spec!r}')
 
 
 def scaled_base_lr(base_lr: float, batch_size: int) -> float:
@@ -82,7 +99,9 @@ def trainer_synapse(cfg: TrainConfig, model, snapshot_path: str, volumes: Option
     log("The length of train set is: {}".format(len(ds)))
     log("{} iterations per epoch. {} max iterations ".format(per_epoch, max_iterations))
     model.train()
-    loss_fn = SegLoss(cfg.num_classes, group=group)
+    loss_scale = make_loss_scale(cfg.loss_scale)
+    scaler = loss_scale if isinstance(loss_scale, DynamicLossScale) else None
+    loss_fn = SegLoss(cfg.num_classes, group=group, loss_scale=loss_scale)
     opt = FusedSGD(model, lr=cfg.base_lr, momentum=0.9, weight_decay=1e-4, clip_norm=5.0 if cfg.grad_clipping else None)
 
     def lr_at(it: int) -> float:
@@ -104,6 +123,8 @@ def trainer_synapse(cfg: TrainConfig, model, snapshot_path: str, volumes: Option
 
     saves = set(checkpoint_epochs(cfg.max_epochs, cfg.eval_interval))
     hist = {"loss": [], "lr": [], "dice": [], "hd95": [], "checkpoints": []}
+    if scaler is not None:
+        hist["loss_scale"] = []                                   # the scale after the step of each log line
     step = None
     iter_num = 0
     for x, y in loader:
@@ -123,7 +144,13 @@ def trainer_synapse(cfg: TrainConfig, model, snapshot_path: str, volumes: Option
             hist["loss"].append(lv)
             hist["lr"].append(lr_at(iter_num))
             log('iteration %d : lr: %f, loss : %f, loss_ce: %f, loss_dice: %f' % (iter_num, lr_at(iter_num), lv, cv, dv))
-            if opt.last_step_skipped():                           # float16: a non-finite gradient norm skips the update (no weights were touched)
+            if scaler is not None:                                # read with the loss scalars above: no sync point of its own
+                ls = scaler.state_dict()
+                hist["loss_scale"].append(ls["scale"])
+                if opt.last_step_skipped():                       # the scale has halved already; the count is the device's, every step in it
+                    log('iteration %d : update SKIPPED, gradient norm not finite (%d skipped so far; dynamic loss scale now %g)'
+                        % (iter_num, ls["skipped"], ls["scale"]))
+            elif opt.last_step_skipped():                         # float16: a non-finite gradient norm skips the update (no weights were touched)
                 log('iteration %d : update SKIPPED, gradient norm not finite (%d skipped so far; lower the loss scale if this persists)'
                     % (iter_num, opt.skipped_steps))
         if iter_num % per_epoch == 0:
