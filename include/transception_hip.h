@@ -597,6 +597,32 @@ int tc_seg_loss_bwd_tok(const float* prob, const void* logits, int ldl, const lo
                         int dtype, void* stream);
 /* prob may be NULL in both: the forward then only accumulates the sums, the backward recomputes the softmax from `logits` (row pitch ldl)
  * with the forward's operations in the forward's order -- 29 MB of fp32 probabilities less to write and read at B = 16, 224 x 224. */
+/* The class-weighted loss with ignore_index: the arguments the reference's loss classes take beyond their defaults -- the `weight` and
+ * `ignore_index` of the CrossEntropyLoss it constructs (trainer.py:123, applied at trainer.py:141) and the per-class `weight` of
+ * DiceLoss.forward (utils.py:34-47: weight at :38-39, `loss += dice * weight[i]` at :46, `/ n_classes` at :47):
+ *   CE   = sum_i w_ce[y_i] nll_i / sum_i w_ce[y_i]                                       over the pixels whose label is not ignore_index
+ *   Dice = sum_k w_dice[k] (1 - (2 I_k + 1e-5) / (Z_k + Y_k + 1e-5)) / ncls              an ignored pixel enters none of I, Y, Z
+ * weights: float[2 * ncls] on the device, CE weights then Dice weights; NULL = all ones.  ignore_index: a label value outside [0, ncls)
+ * (an index inside it is TC_ERR_ARG), or TC_IGNORE_NONE for none.  ncls <= 16.
+ * ONE pair of entries serves both layouts: ld = 0 is NCHW logits / dlogits [B, ncls, HW] (tc_seg_loss_fwd / _bwd; prob is then required),
+ * ld >= ncls is token-major rows [B * HW, ld] (tc_seg_loss_fwd_tok / _bwd_tok, with the same 16-byte-piece path for aligned padded 16-bit
+ * rows, pad elements of dlogits written as zeros, and the same prob == NULL recompute from `logits` of row pitch ldl).
+ * The sums vector keeps its layout and meaning except sums[0] = sum_i w_ce[y_i] nll_i: I, Y, Z are unweighted, so ranks all-reduce the same
+ * 1 + 3 ncls floats, and the CE denominator is formed from them as sum_k w_ce[k] Y_k -- no pixel count is passed.  The fp32 Y_k are whole
+ * numbers: the denominator is exact only while the GLOBAL number of counted pixels stays below 2^24.
+ * Zero denominator (every pixel ignored, or only zero-weight classes present): CE and its gradient are 0, NOT the NaN of torch -- a NaN
+ * would read as an overflow to the loss-scale guard of tc_sgd_step_multi and skip the update silently.
+ * Backward: dlogits of an ignored pixel is WRITTEN as exact zeros in every class; per pixel the CE factor is (w_ce / denominator) * w_ce[y_i]
+ * in that order, so that with all-ones weights and no ignore_index dlogits and prob are bit-equal to the plain entries' (the atomically
+ * accumulated sums agree to rounding).  gscale / gscale_dev as in tc_seg_loss_bwd.  A label outside [0, ncls) that is not ignore_index is
+ * not supported (as in the plain entries). */
+#define TC_IGNORE_NONE (-2147483647 - 1)
+int tc_seg_loss_fwd_w(const void* logits, int ld, const long long* labels, const float* weights, int ignore_index, float* prob, float* sums,
+                      int B, int ncls, int HW, int dtype, void* stream);
+int tc_seg_loss_value_w(const float* sums, const float* weights, int ncls, double w_ce, double w_dice, float* out3, void* stream);
+int tc_seg_loss_bwd_w(const float* prob, const void* logits, int ldl, const long long* labels, const float* weights, int ignore_index,
+                      const float* sums, void* dlogits, int ld, int B, int ncls, int HW, float w_ce, float w_dice, float gscale,
+                      const float* gscale_dev, int dtype, void* stream);
 /* Fused core of FactorAtt_ConvRelPosEnc (MSTr.py:864-877), one workgroup per (image, head):
  *   o = scale * q (softmax_N(k)^T v) + q (.) convv        q, k, v: column slices (row stride ld) of the [Bt*N, 3C] qkv buffer,
  * head h owning channels [h*Ch, (h+1)*Ch); convv = crpe(v) (row stride ldc).  stats: tc_factor_att_stats_floats() floats saved for

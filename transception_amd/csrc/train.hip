@@ -1,5 +1,6 @@
 // Reductions and training-step kernels: bias-gradient column sums, the fused CE + Dice segmentation loss
-// (trainer.py:141-143, utils.py:24-47) and the fused SGD-momentum update (trainer.py:125).
+// (trainer.py:141-143, utils.py:24-47), its class-weighted / ignore_index form (nn.CrossEntropyLoss(weight, ignore_index), trainer.py:141;
+// DiceLoss.forward(weight=...), utils.py:34-47) and the fused SGD-momentum update (trainer.py:125).
 #include "tc_common.h"
 
 namespace {
@@ -41,10 +42,22 @@ template <typename T> __device__ __forceinline__ void tok_row_store(T* dp, int n
 
 // ld = 0: logits / dlogits are [B, ncls, HW] (the module's NCHW output); ld > 0: token-major [B * HW, ld] rows as the last Linear leaves
 // them (the captured training step hands them over without the transpose and the fp32 copy); prob is [B, ncls, HW] either way
-template <typename T>
+//
+// WEIGHTED (the class-weighted / ignoring loss, tc_seg_loss_*_w) is a compile-time variant of the same bodies: every line it adds sits under
+// `if constexpr (WEIGHTED)`, so the plain instantiations keep their instruction sequence and their bits.  weights: float[2 * ncls], CE weights
+// then Dice weights, NULL = all ones, staged in LDS once per workgroup; ignore: the label value whose pixels are left out of every sum and get an
+// exactly zero gradient (TC_IGNORE_NONE: no such label).  The forward needs the CE weights only -- I, Y, Z stay unweighted, so the sums vector
+// and its all-reduce are what they were, and the CE denominator sum_k w_ce[k] Y_k is formed from the (global) sums where it is needed.
+template <typename T, bool WEIGHTED>
 __global__ __launch_bounds__(256) void seg_loss_fwd_kernel(const T* __restrict__ logits, const long long* __restrict__ labels,
-                                                           float* __restrict__ prob, float* __restrict__ sums, int B, int ncls, int HW, int ld) {
+                                                           float* __restrict__ prob, float* __restrict__ sums, int B, int ncls, int HW, int ld,
+                                                           const float* __restrict__ weights, int ignore) {
     __shared__ float red[4][1 + 3 * MAXCLS];
+    __shared__ float wce[WEIGHTED ? MAXCLS : 1];
+    if constexpr (WEIGHTED) {
+        if (threadIdx.x < ncls) wce[threadIdx.x] = weights ? weights[threadIdx.x] : 1.f;
+        __syncthreads();
+    }
     const bool vec16 = ld > 0 && !(ld & 7) && ld >= ((ncls + 7) & ~7) && !((uintptr_t)logits & 15);
     float ce = 0.f, I[MAXCLS], Y[MAXCLS], Z[MAXCLS];
 #pragma unroll
@@ -70,6 +83,19 @@ __global__ __launch_bounds__(256) void seg_loss_fwd_kernel(const T* __restrict__
         const float inv = 1.f / s;
         const int lab = (int)labels[i];
         float* pp = prob + (long long)b * ncls * HW + p;
+        if constexpr (WEIGHTED) {
+            const bool counted = lab != ignore;                    // one test per pixel; an ignored pixel still writes its probabilities
+#pragma unroll
+            for (int k = 0; k < MAXCLS; ++k) if (k < ncls) {
+                const float pk = v[k] * inv;
+                if (prob) pp[(long long)k * HW] = pk;
+                if (counted) {
+                    Z[k] += pk * pk;
+                    if (k == lab) { I[k] += pk; Y[k] += 1.f; ce -= wce[k] * logf(fmaxf(pk, 1e-38f)); }
+                }
+            }
+            continue;
+        }
 #pragma unroll
         for (int k = 0; k < MAXCLS; ++k) if (k < ncls) {
             const float pk = v[k] * inv;
@@ -91,24 +117,43 @@ __global__ __launch_bounds__(256) void seg_loss_fwd_kernel(const T* __restrict__
         atomicAdd(sums + threadIdx.x, red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x]);
 }
 
-template <typename T>
+// WEIGHTED: n_pix is not used.  The prologue forms n_eff = sum_k w_ce[k] Y_k from the sums (Y_k is the number of counted pixels of class k:
+// whole numbers, exact in fp32 below 2^24 counted pixels in all) and folds w_dice[k] into ca / cb; per pixel the CE factor is
+// (w_ce / n_eff) * w_ce[lab] in that order, which with all-ones weights is w_ce / n_pix to the bit.  n_eff = 0 (every pixel ignored, or only
+// zero-weight classes present): the CE term has no gradient.  An ignored pixel's gradient is WRITTEN as zeros (dlogits is uninitialised memory).
+template <typename T, bool WEIGHTED>
 __global__ __launch_bounds__(256) void seg_loss_bwd_kernel(const float* __restrict__ prob, const long long* __restrict__ labels,
                                                            const float* __restrict__ sums, T* __restrict__ dlogits, int B, int ncls,
                                                            int HW, float w_ce, float w_dice, float n_pix, float gscale, const float* __restrict__ gscale_dev, int ld,
-                                                           const T* __restrict__ logits, int ldl) {
+                                                           const T* __restrict__ logits, int ldl, const float* __restrict__ weights, int ignore) {
     if (gscale_dev) gscale *= *gscale_dev;
     const bool vin = !prob && !(ldl & 7) && ldl >= ((ncls + 7) & ~7) && !((uintptr_t)logits & 15);
     const bool vout = ld > 0 && !(ld & 7) && ld >= ((ncls + 7) & ~7) && !((uintptr_t)dlogits & 15);
     __shared__ float ca[MAXCLS], cb[MAXCLS];          // dDice/dp_c = ca[c]*onehot_c + cb[c]*p_c
+    __shared__ float wce[WEIGHTED ? MAXCLS : 1], wy[WEIGHTED ? MAXCLS : 1];
     if (threadIdx.x < ncls) {
         const float I = sums[1 + 3 * threadIdx.x], Y = sums[2 + 3 * threadIdx.x], Z = sums[3 + 3 * threadIdx.x];
         const float den = Z + Y + 1e-5f, num = 2.f * I + 1e-5f;
         ca[threadIdx.x] = -w_dice / (float)ncls * 2.f / den;
         cb[threadIdx.x] = w_dice / (float)ncls * 2.f * num / (den * den);
+        if constexpr (WEIGHTED) {
+            const float wc = weights ? weights[threadIdx.x] : 1.f, wd = weights ? weights[ncls + threadIdx.x] : 1.f;
+            ca[threadIdx.x] *= wd;
+            cb[threadIdx.x] *= wd;
+            wce[threadIdx.x] = wc;
+            wy[threadIdx.x] = wc * Y;
+        }
     }
     __syncthreads();
     const long long n = (long long)B * HW;
-    const float cew = w_ce / n_pix;
+    float cew;
+    if constexpr (WEIGHTED) {
+        float n_eff = 0.f;
+        for (int k = 0; k < ncls; ++k) n_eff += wy[k];              // class order, the same in every thread and every workgroup
+        cew = n_eff > 0.f ? w_ce / n_eff : 0.f;
+    } else {
+        cew = w_ce / n_pix;
+    }
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
         const int b = (ld && !prob) ? 0 : (int)((unsigned)i / (unsigned)HW), p = (int)i - b * HW;
         const float* pp = prob + (long long)b * ncls * HW + p;
@@ -141,6 +186,23 @@ __global__ __launch_bounds__(256) void seg_loss_bwd_kernel(const float* __restri
         }
         T* dp = ld ? dlogits + i * ld : dlogits + (long long)b * ncls * HW + p;
         const long long ks = ld ? 1 : HW;
+        if constexpr (WEIGHTED) {
+            // (a label outside [0, ncls) that is not `ignore` matches no class, as in the plain kernel; it takes weight 1 rather than reading past wce)
+            const bool counted = lab != ignore;
+            const float cw = cew * ((unsigned)lab < (unsigned)ncls ? wce[lab] : 1.f);
+            if (sizeof(T) == 2 && vout) {
+                float o[MAXCLS];
+#pragma unroll
+                for (int k = 0; k < MAXCLS; ++k)
+                    o[k] = (k < ncls && counted) ? gscale * (cw * (pk[k] - (k == lab ? 1.f : 0.f)) + pk[k] * (g[k] - dot)) : 0.f;
+                tok_row_store<T>(dp, ncls, o);
+            } else {
+#pragma unroll
+                for (int k = 0; k < MAXCLS; ++k) if (k < ncls)
+                    stf<T>(dp + k * ks, counted ? gscale * (cw * (pk[k] - (k == lab ? 1.f : 0.f)) + pk[k] * (g[k] - dot)) : 0.f);
+            }
+            continue;
+        }
         if (sizeof(T) == 2 && vout) {                           // padded rows: the pad elements are written as zeros
             float o[MAXCLS];
 #pragma unroll
@@ -317,8 +379,8 @@ extern "C" int tc_seg_loss_fwd(const void* logits, const long long* labels, floa
                                int dtype, void* stream) {
     if (!logits || !labels || !prob || !sums || B <= 0 || ncls <= 0 || ncls > MAXCLS || HW <= 0 || (long long)B * HW >= 0x7fffffffLL) return TC_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
-    TC_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((seg_loss_fwd_kernel<T>), dim3(tc_blocks((long long)B * HW, 256, 1024)), dim3(256), 0, s,
-                                                (const T*)logits, labels, prob, sums, B, ncls, HW, 0));
+    TC_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((seg_loss_fwd_kernel<T, false>), dim3(tc_blocks((long long)B * HW, 256, 1024)), dim3(256), 0, s,
+                                                (const T*)logits, labels, prob, sums, B, ncls, HW, 0, (const float*)nullptr, 0));
     return tc_launch_status();
 }
 
@@ -326,8 +388,8 @@ extern "C" int tc_seg_loss_fwd_tok(const void* logits, int ld, const long long* 
                                    int dtype, void* stream) {
     if (!logits || !labels || !sums || B <= 0 || ncls <= 0 || ncls > MAXCLS || HW <= 0 || ld < ncls || (long long)B * HW >= 0x7fffffffLL) return TC_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
-    TC_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((seg_loss_fwd_kernel<T>), dim3(tc_blocks((long long)B * HW, 256, 1024)), dim3(256), 0, s,
-                                                (const T*)logits, labels, prob, sums, B, ncls, HW, ld));
+    TC_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((seg_loss_fwd_kernel<T, false>), dim3(tc_blocks((long long)B * HW, 256, 1024)), dim3(256), 0, s,
+                                                (const T*)logits, labels, prob, sums, B, ncls, HW, ld, (const float*)nullptr, 0));
     return tc_launch_status();
 }
 
@@ -354,6 +416,59 @@ extern "C" int tc_seg_loss_value(const float* sums, int ncls, double n_pix, doub
     return tc_launch_status();
 }
 
+// The same from the sums of the class-weighted / ignoring forward: sums[0] = sum_i w_ce[y_i] nll_i over the counted pixels, so
+// CE = sums[0] / sum_k w_ce[k] Y_k (nn.CrossEntropyLoss(weight, ignore_index), mean reduction) -- 0, not NaN, when that denominator is 0 --
+// and Dice = sum_k w_dice[k] (1 - (2 I_k + eps) / (Z_k + Y_k + eps)) / ncls (DiceLoss.forward(weight=...), utils.py:42-46).
+__global__ void seg_loss_value_w_kernel(const float* __restrict__ sums, const float* __restrict__ weights, int ncls, double w_ce, double w_dice,
+                                        float* __restrict__ out3) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    double acc = 0.0, n_eff = 0.0;
+    for (int c = 0; c < ncls; ++c) {
+        const double inter = sums[1 + 3 * c], ysum = sums[2 + 3 * c], zsum = sums[3 + 3 * c];
+        const double wc = weights ? (double)weights[c] : 1.0, wd = weights ? (double)weights[ncls + c] : 1.0;
+        n_eff += wc * ysum;
+        acc += wd * (1.0 - (2.0 * inter + 1e-5) / (zsum + ysum + 1e-5));
+    }
+    const double ce = n_eff > 0.0 ? (double)sums[0] / n_eff : 0.0;
+    const double dice = acc / (double)ncls;
+    out3[0] = (float)(w_ce * ce + w_dice * dice);
+    out3[1] = (float)ce;
+    out3[2] = (float)dice;
+}
+
+extern "C" int tc_seg_loss_value_w(const float* sums, const float* weights, int ncls, double w_ce, double w_dice, float* out3, void* stream) {
+    if (!sums || !out3 || ncls <= 0 || ncls > MAXCLS) return TC_ERR_ARG;
+    hipLaunchKernelGGL(seg_loss_value_w_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, sums, weights, ncls, w_ce, w_dice, out3);
+    return tc_launch_status();
+}
+
+// ld = 0: NCHW logits (prob is then required, as in tc_seg_loss_fwd); ld >= ncls: token-major rows (tc_seg_loss_fwd_tok)
+extern "C" int tc_seg_loss_fwd_w(const void* logits, int ld, const long long* labels, const float* weights, int ignore_index, float* prob,
+                                 float* sums, int B, int ncls, int HW, int dtype, void* stream) {
+    if (!logits || !labels || !sums || B <= 0 || ncls <= 0 || ncls > MAXCLS || HW <= 0 || (ld != 0 && ld < ncls) || (ld == 0 && !prob) ||
+        (ignore_index >= 0 && ignore_index < ncls) || (long long)B * HW >= 0x7fffffffLL)
+        return TC_ERR_ARG;
+    hipStream_t s = (hipStream_t)stream;
+    TC_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((seg_loss_fwd_kernel<T, true>), dim3(tc_blocks((long long)B * HW, 256, 1024)), dim3(256), 0, s,
+                                                (const T*)logits, labels, prob, sums, B, ncls, HW, ld, weights, ignore_index));
+    return tc_launch_status();
+}
+
+// ld = 0: NCHW dlogits from the probability map (tc_seg_loss_bwd); ld >= ncls: token-major rows, prob or -- prob == NULL -- the softmax
+// recomputed from the token-major logits of row pitch ldl (tc_seg_loss_bwd_tok)
+extern "C" int tc_seg_loss_bwd_w(const float* prob, const void* logits, int ldl, const long long* labels, const float* weights, int ignore_index,
+                                 const float* sums, void* dlogits, int ld, int B, int ncls, int HW, float w_ce, float w_dice, float gscale,
+                                 const float* gscale_dev, int dtype, void* stream) {
+    if ((!prob && (!logits || ldl < ncls || ld == 0)) || !labels || !sums || !dlogits || B <= 0 || ncls <= 0 || ncls > MAXCLS || HW <= 0 ||
+        (ld != 0 && ld < ncls) || (ignore_index >= 0 && ignore_index < ncls) || (long long)B * HW >= 0x7fffffffLL)
+        return TC_ERR_ARG;
+    hipStream_t s = (hipStream_t)stream;
+    TC_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((seg_loss_bwd_kernel<T, true>), dim3(tc_blocks((long long)B * HW, 256, 2048)), dim3(256), 0, s,
+                                                prob, labels, sums, (T*)dlogits, B, ncls, HW, w_ce, w_dice, 0.f, gscale, gscale_dev, ld,
+                                                (const T*)logits, ldl, weights, ignore_index));
+    return tc_launch_status();
+}
+
 extern "C" int tc_argmax_counts(const void* logits, const long long* labels, unsigned char* pred, float* counts, int B, int ncls, int HW,
                                 int dtype, void* stream) {
     if (!logits || !pred || (labels && !counts) || B <= 0 || ncls <= 0 || ncls > MAXCLS || HW <= 0) return TC_ERR_ARG;
@@ -367,8 +482,9 @@ extern "C" int tc_seg_loss_bwd(const float* prob, const long long* labels, const
                                float w_ce, float w_dice, float n_pix_global, float gscale, const float* gscale_dev, int dtype, void* stream) {
     if (!prob || !labels || !sums || !dlogits || B <= 0 || ncls <= 0 || ncls > MAXCLS || HW <= 0 || (long long)B * HW >= 0x7fffffffLL) return TC_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
-    TC_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((seg_loss_bwd_kernel<T>), dim3(tc_blocks((long long)B * HW, 256, 2048)), dim3(256), 0, s,
-                                                prob, labels, sums, (T*)dlogits, B, ncls, HW, w_ce, w_dice, n_pix_global, gscale, gscale_dev, 0, (const T*)nullptr, 0));
+    TC_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((seg_loss_bwd_kernel<T, false>), dim3(tc_blocks((long long)B * HW, 256, 2048)), dim3(256), 0, s,
+                                                prob, labels, sums, (T*)dlogits, B, ncls, HW, w_ce, w_dice, n_pix_global, gscale, gscale_dev, 0, (const T*)nullptr, 0,
+                                                (const float*)nullptr, 0));
     return tc_launch_status();
 }
 
@@ -379,8 +495,9 @@ extern "C" int tc_seg_loss_bwd_tok(const float* prob, const void* logits, int ld
         (long long)B * HW >= 0x7fffffffLL)
         return TC_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
-    TC_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((seg_loss_bwd_kernel<T>), dim3(tc_blocks((long long)B * HW, 256, 2048)), dim3(256), 0, s,
-                                                prob, labels, sums, (T*)dlogits, B, ncls, HW, w_ce, w_dice, n_pix_global, gscale, gscale_dev, ld, (const T*)logits, ldl));
+    TC_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((seg_loss_bwd_kernel<T, false>), dim3(tc_blocks((long long)B * HW, 256, 2048)), dim3(256), 0, s,
+                                                prob, labels, sums, (T*)dlogits, B, ncls, HW, w_ce, w_dice, n_pix_global, gscale, gscale_dev, ld, (const T*)logits, ldl,
+                                                (const float*)nullptr, 0));
     return tc_launch_status();
 }
 

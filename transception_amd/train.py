@@ -48,19 +48,71 @@ def seg_sums_allreduce(sums: torch.Tensor, n_pix: float, group=None):
     return sums, n_pix * world, world
 
 
-def loss_from_sums(sums: torch.Tensor, n_pix: float, w_ce: float, w_dice: float):
+def loss_from_sums(sums: torch.Tensor, n_pix: float, w_ce: float, w_dice: float, weights: Optional[torch.Tensor] = None):
     """0.4*CE + 0.6*Dice from the (global) sums: trainer.py:141-143, utils.py:34-47 (smooth 1e-5, mean over classes).
-    Device sums: one tc_seg_loss_value launch.  Host sums (the gloo tests): the same expression in torch, double."""
+    Device sums: one tc_seg_loss_value launch.  Host sums (the gloo tests): the same expression in torch, double.
+
+    weights (the class-weighted / ignoring loss, SegLoss._route): [2 * classes] floats, CE weights then Dice weights, on the device
+    of `sums`.  sums[0] is then sum_i w[y_i] nll_i and the CE denominator is sum_k w_ce[k] Y_k, taken from the sums themselves
+    (n_pix is not used); a zero denominator gives CE = 0, not NaN.  Dice = sum_k w_dice[k] (1 - ...) / classes (utils.py:42-46)."""
+    ncls = (sums.numel() - 1) // 3
     if sums.is_cuda:
         out3 = torch.empty(3, dtype=torch.float32, device=sums.device)
-        lib().tc_seg_loss_value(sums.data_ptr(), (sums.numel() - 1) // 3, float(n_pix), float(w_ce), float(w_dice), out3.data_ptr(),
-                                torch.cuda.current_stream(sums.device).cuda_stream)
+        stream = torch.cuda.current_stream(sums.device).cuda_stream
+        if weights is None:
+            lib().tc_seg_loss_value(sums.data_ptr(), ncls, float(n_pix), float(w_ce), float(w_dice), out3.data_ptr(), stream)
+        else:
+            lib().tc_seg_loss_value_w(sums.data_ptr(), weights.data_ptr(), ncls, float(w_ce), float(w_dice), out3.data_ptr(), stream)
         return out3[0], out3[1], out3[2]
     s = sums.double()
-    ce = s[0] / n_pix
     inter, ysum, zsum = s[1::3], s[2::3], s[3::3]
-    dice = (1.0 - (2.0 * inter + 1e-5) / (zsum + ysum + 1e-5)).mean()
+    per_class = 1.0 - (2.0 * inter + 1e-5) / (zsum + ysum + 1e-5)
+    if weights is None:
+        ce = s[0] / n_pix
+        dice = per_class.mean()
+    else:
+        w = weights.double()
+        den = (w[:ncls] * ysum).sum()
+        ce = s[0] / den if float(den) > 0.0 else torch.zeros((), dtype=torch.float64)
+        dice = (w[ncls:] * per_class).sum() / ncls
     return w_ce * ce + w_dice * dice, ce, dice
+
+
+IGNORE_NONE = -2 ** 31           # include/transception_hip.h TC_IGNORE_NONE: "no ignore_index" for the tc_seg_loss_*_w entries
+
+
+def check_class_weights(name: str, w, ncls: int, need_positive: bool) -> Optional[tuple]:
+    """A per-class weight vector as a tuple of floats (None stays None): `ncls` finite numbers >= 0, not bools; with
+    need_positive at least one of them > 0.  Anything else is a ValueError."""
+    if w is None:
+        return None
+    if isinstance(w, torch.Tensor):
+        w = w.detach().cpu().tolist()
+    try:
+        vals = list(w)
+    except TypeError:
+        raise ValueError(f"{name} must be a sequence of {ncls} numbers, got {w!r}") from None
+    if len(vals) != ncls:
+        raise ValueError(f"{name} must have {ncls} entries (one per class), got {len(vals)}")
+    for v in vals:
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or v < 0:
+            raise ValueError(f"{name} must hold finite numbers >= 0, got {v!r}")
+    if need_positive and not any(v > 0 for v in vals):
+        raise ValueError(f"{name} must not be all zero")
+    return tuple(float(v) for v in vals)
+
+
+def check_ignore_index(ii, ncls: int) -> Optional[int]:
+    """None, or an int outside [0, ncls) that a 32-bit label compare can hold (the kernels' "off" value excluded)."""
+    if ii is None:
+        return None
+    if isinstance(ii, bool) or not isinstance(ii, int):
+        raise ValueError(f"ignore_index must be an int or None, got {ii!r}")
+    if 0 <= ii < ncls:
+        raise ValueError(f"ignore_index {ii} is a class index: it must lie outside [0, {ncls})")
+    if not IGNORE_NONE < ii < 2 ** 31:
+        raise ValueError(f"ignore_index {ii} does not fit the kernels' 32-bit label compare")
+    return ii
 
 
 class DynamicLossScale:
@@ -158,7 +210,9 @@ def _wire_loss_scale(loss_fn, opt, device) -> None:
 
 class _SegLossFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, logits, labels, ncls, w_ce, w_dice, group, loss_scale=1.0):
+    def forward(ctx, logits, labels, ncls, w_ce, w_dice, group, loss_scale=1.0, route=None):
+        """route: None (the plain loss), or SegLoss._route's (weights tensor or None, ignore_index as the kernels take it) -- the
+        class-weighted / ignoring entries, NCHW through ld = 0."""
         L = lib()
         logits = logits.contiguous()
         B, C, H, W = logits.shape
@@ -167,11 +221,16 @@ class _SegLossFn(torch.autograd.Function):
         prob = torch.empty((B, C, H, W), dtype=torch.float32, device=logits.device)
         sums = torch.zeros(1 + 3 * ncls, dtype=torch.float32, device=logits.device)
         labels = labels.contiguous()
-        L.tc_seg_loss_fwd(logits.data_ptr(), labels.data_ptr(), prob.data_ptr(), sums.data_ptr(), B, ncls, H * W, _dt(logits), stream)
+        if route is None:
+            L.tc_seg_loss_fwd(logits.data_ptr(), labels.data_ptr(), prob.data_ptr(), sums.data_ptr(), B, ncls, H * W, _dt(logits), stream)
+        else:
+            L.tc_seg_loss_fwd_w(logits.data_ptr(), 0, labels.data_ptr(), route[0].data_ptr(), route[1], prob.data_ptr(), sums.data_ptr(),
+                                B, ncls, H * W, _dt(logits), stream)
         sums, n_pix, world = seg_sums_allreduce(sums, float(B * H * W), group)
-        loss, ce, dice = loss_from_sums(sums, n_pix, w_ce, w_dice)
+        loss, ce, dice = loss_from_sums(sums, n_pix, w_ce, w_dice, None if route is None else route[0])
         ctx.save_for_backward(prob, labels, sums)
         ctx.meta = (ncls, w_ce, w_dice, n_pix, world, logits.dtype, loss_scale if isinstance(loss_scale, DynamicLossScale) else float(loss_scale))
+        ctx.route = route
         return loss.float(), ce.float(), dice.float()
 
     @staticmethod
@@ -188,25 +247,76 @@ class _SegLossFn(torch.autograd.Function):
         if isinstance(loss_scale, DynamicLossScale):         # ... times the device scale: a one-element product, still no host sync
             gl = (gl * loss_scale.state(prob.device)[0]).reshape(1)
             loss_scale = 1.0
-        L.tc_seg_loss_bwd(prob.data_ptr(), labels.data_ptr(), sums.data_ptr(), d.data_ptr(), B, ncls, H * W, float(w_ce), float(w_dice),
-                          float(n_pix), loss_scale, gl.data_ptr(), _dt(d), stream)
-        return d, None, None, None, None, None, None
+        if ctx.route is None:
+            L.tc_seg_loss_bwd(prob.data_ptr(), labels.data_ptr(), sums.data_ptr(), d.data_ptr(), B, ncls, H * W, float(w_ce), float(w_dice),
+                              float(n_pix), loss_scale, gl.data_ptr(), _dt(d), stream)
+        else:
+            L.tc_seg_loss_bwd_w(prob.data_ptr(), None, 0, labels.data_ptr(), ctx.route[0].data_ptr(), ctx.route[1], sums.data_ptr(),
+                                d.data_ptr(), 0, B, ncls, H * W, float(w_ce), float(w_dice), loss_scale, gl.data_ptr(), _dt(d), stream)
+        return d, None, None, None, None, None, None, None
 
 
 class SegLoss(torch.nn.Module):
-    """0.4*CE + 0.6*Dice over the (global) batch; returns (loss, ce, dice)."""
+    """0.4*CE + 0.6*Dice over the (global) batch; returns (loss, ce, dice).
+
+    ce_weight / dice_weight / ignore_index (all None: the plain loss, through the same calls as ever):
+      CE   = torch.nn.CrossEntropyLoss(weight=ce_weight, ignore_index=ignore_index), mean reduction (trainer.py:141):
+             sum_i w[y_i] nll_i / sum_i w[y_i] over the pixels whose label is not ignore_index -- but 0 with a zero gradient, not NaN,
+             when that denominator is 0 (every pixel ignored, or only zero-weight classes present): a NaN there would read as an
+             overflow to the loss-scale guard and skip the update silently;
+      Dice = the reference's DiceLoss.forward(weight=dice_weight, softmax=True) (utils.py:34-47):
+             sum_k dice_weight[k] (1 - (2 I_k + 1e-5) / (Z_k + Y_k + 1e-5)) / n_classes, an ignored pixel entering none of I, Y, Z.
+    The gradient at an ignored pixel is exactly zero in every class.  The weights live in one small device tensor per device
+    (weights(device): CE weights, then Dice weights), created on first use and never replaced: captured launches hold its address, so
+    new values are written IN PLACE (weights(device).copy_(...)) and are seen by the next replay.  The CE denominator is taken from the fp32 per-class pixel counts of the
+    sums vector, which are exact while the global number of counted pixels is below 2^24."""
 
     def __init__(self, n_classes: int = 9, w_ce: float = 0.4, w_dice: float = 0.6, group=None,
-                 loss_scale: Union[float, DynamicLossScale] = 1.0):
+                 loss_scale: Union[float, DynamicLossScale] = 1.0, ce_weight=None, dice_weight=None, ignore_index: Optional[int] = None):
         """loss_scale: the gradient that leaves this loss is multiplied by it (the reported loss is not) -- loss scaling for float16
         storage; FusedSGD.step divides it out again (train_step wires the two together).  A float is a static scale; a
-        DynamicLossScale is read from device memory by the backward kernel and adjusts itself after every update."""
+        DynamicLossScale is read from device memory by the backward kernel and adjusts itself after every update.
+        ce_weight: n_classes finite numbers >= 0, not all zero; dice_weight: n_classes finite numbers >= 0; ignore_index: an int
+        outside [0, n_classes), e.g. 255 or -100.  Bad values raise ValueError."""
         super().__init__()
         self.n_classes, self.w_ce, self.w_dice, self.group = n_classes, w_ce, w_dice, group
         self.loss_scale = loss_scale if isinstance(loss_scale, DynamicLossScale) else float(loss_scale)
+        self.ce_weight = check_class_weights("ce_weight", ce_weight, n_classes, need_positive=True)
+        self.dice_weight = check_class_weights("dice_weight", dice_weight, n_classes, need_positive=False)
+        self.ignore_index = check_ignore_index(ignore_index, n_classes)
+        if self.weighted and n_classes > 16:
+            raise ValueError(f"the class-weighted loss kernels take at most 16 classes, got {n_classes}")
+        self._weights = {}                               # device -> fp32 [2 * n_classes]
+
+    @property
+    def weighted(self) -> bool:
+        """True when the class-weighted / ignoring kernels are used (any of the three arguments set)."""
+        return self.ce_weight is not None or self.dice_weight is not None or self.ignore_index is not None
+
+    def _host_weights(self) -> torch.Tensor:
+        ones = (1.0,) * self.n_classes
+        return torch.tensor((self.ce_weight or ones) + (self.dice_weight or ones), dtype=torch.float32)
+
+    def weights(self, device) -> torch.Tensor:
+        """The [2 * n_classes] weight tensor of `device` (CE weights, then Dice weights; ones where none were given)."""
+        d = torch.device(device)
+        if d.type == "cuda" and d.index is None:
+            d = torch.device("cuda", torch.cuda.current_device())
+        if d not in self._weights:
+            self._weights[d] = self._host_weights().to(d)
+        return self._weights[d]
+
+    def _route(self, device):
+        """None for the plain loss; else (weights tensor, ignore_index or the kernels' "off" value) for the tc_seg_loss_*_w entries."""
+        if not self.weighted:
+            return None
+        return self.weights(device), IGNORE_NONE if self.ignore_index is None else self.ignore_index
 
     def forward(self, logits: torch.Tensor, labels: torch.Tensor):
-        return _SegLossFn.apply(logits, labels.long(), self.n_classes, self.w_ce, self.w_dice, self.group, self.loss_scale)
+        route = self._route(logits.device)
+        if route is None:
+            return _SegLossFn.apply(logits, labels.long(), self.n_classes, self.w_ce, self.w_dice, self.group, self.loss_scale)
+        return _SegLossFn.apply(logits, labels.long(), self.n_classes, self.w_ce, self.w_dice, self.group, self.loss_scale, route)
 
 
 def cosine_lr(base_lr: float, step: int, t_max: int) -> float:
@@ -654,8 +764,13 @@ class GraphedStep:
         stream = torch.cuda.current_stream(logits.device).cuda_stream
         self._logits, self._shape = logits, (B, C, H, W)           # (no probability map: the backward recomputes the softmax)
         self._sums = torch.zeros(1 + 3 * C, dtype=torch.float32, device=logits.device)
-        L.tc_seg_loss_fwd_tok(logits.data_ptr(), logits.stride(0), self.y.data_ptr(), None, self._sums.data_ptr(), B, C, H * W,
-                              _dt(logits), stream)
+        route = self.loss_fn._route(logits.device)                 # (weights, ignore_index): the class-weighted / ignoring entries
+        if route is None:
+            L.tc_seg_loss_fwd_tok(logits.data_ptr(), logits.stride(0), self.y.data_ptr(), None, self._sums.data_ptr(), B, C, H * W,
+                                  _dt(logits), stream)
+        else:
+            L.tc_seg_loss_fwd_w(logits.data_ptr(), logits.stride(0), self.y.data_ptr(), route[0].data_ptr(), route[1], None,
+                                self._sums.data_ptr(), B, C, H * W, _dt(logits), stream)
         self._npix_local = float(B * H * W)
 
     def _reduce_sums(self):
@@ -665,16 +780,21 @@ class GraphedStep:
         M, L = self.model, lib()
         B, C, H, W = self._shape
         lf, lg = self.loss_fn, self._logits
-        self.out = tuple(t.float() for t in loss_from_sums(self._sums, self._npix, lf.w_ce, lf.w_dice))
+        route = lf._route(lg.device)
+        self.out = tuple(t.float() for t in loss_from_sums(self._sums, self._npix, lf.w_ce, lf.w_dice, None if route is None else route[0]))
         stream = torch.cuda.current_stream(lg.device).cuda_stream
         # the gradient of the token-major logits, in the logits' own layout (their rows are padded to 16 bytes when the fused LayerNorm +
         # classifier produced them: Graph.ln_cls)
         d = torch.empty((B * H * W, lg.stride(0)), dtype=self.model.compute_dtype, device=lg.device)[:, :C]
         # a DynamicLossScale is read from its device state (word 0) by the kernel: the scale of every replay is the one the last left
         dyn = isinstance(lf.loss_scale, DynamicLossScale)
-        L.tc_seg_loss_bwd_tok(None, lg.data_ptr(), lg.stride(0), self.y.data_ptr(), self._sums.data_ptr(), d.data_ptr(), d.stride(0), B, C, H * W,
-                              float(lf.w_ce), float(lf.w_dice), float(self._npix), 1.0 if dyn else float(lf.loss_scale),
-                              lf.loss_scale.state(lg.device).data_ptr() if dyn else None, _dt(d), stream)
+        gscale, gscale_dev = (1.0, lf.loss_scale.state(lg.device).data_ptr()) if dyn else (float(lf.loss_scale), None)
+        if route is None:
+            L.tc_seg_loss_bwd_tok(None, lg.data_ptr(), lg.stride(0), self.y.data_ptr(), self._sums.data_ptr(), d.data_ptr(), d.stride(0), B, C,
+                                  H * W, float(lf.w_ce), float(lf.w_dice), float(self._npix), gscale, gscale_dev, _dt(d), stream)
+        else:                                  # the CE denominator comes from the (all-reduced) sums: no pixel count is passed
+            L.tc_seg_loss_bwd_w(None, lg.data_ptr(), lg.stride(0), self.y.data_ptr(), route[0].data_ptr(), route[1], self._sums.data_ptr(),
+                                d.data_ptr(), d.stride(0), B, C, H * W, float(lf.w_ce), float(lf.w_dice), gscale, gscale_dev, _dt(d), stream)
         M._backward(self._G, self._out_var, d, until="encoder_done")     # loss gradient, decoders, bridge
 
     def _bwd_leg(self, until: Optional[str]):

@@ -25,7 +25,7 @@ import torch.distributed as dist
 
 from .data import DeviceLoader, SynapseSlices
 from .evaluate import inference
-from .train import DynamicLossScale, FusedSGD, GraphedStep, SegLoss, cosine_lr, train_step
+from .train import DynamicLossScale, FusedSGD, GraphedStep, SegLoss, check_class_weights, check_ignore_index, cosine_lr, train_step
 
 
 @dataclass
@@ -49,9 +49,13 @@ class TrainConfig:
     log_every: int = 1                 # iterations between log lines (each one reads three scalars back from the GPU)
     loss_scale: Union[None, float, str] = None   # float16 storage: None = no scale (1), a number = static scale, "dynamic" = a default
                                        # train.DynamicLossScale (device-resident, adjusts itself inside the captured step)
+    class_weights: Optional[tuple] = None  # num_classes weights >= 0, not all zero, used as BOTH the CrossEntropyLoss weight and the Dice weight
+    ignore_index: Optional[int] = None     # a label value outside [0, num_classes) (e.g. 255) whose pixels count in neither loss term
 
     def __post_init__(self):
         make_loss_scale(self.loss_scale)
+        check_class_weights("class_weights", self.class_weights, self.num_classes, need_positive=True)
+        check_ignore_index(self.ignore_index, self.num_classes)
 
 
 def make_loss_scale(spec) -> Union[float, DynamicLossScale]:
@@ -101,7 +105,8 @@ def trainer_synapse(cfg: TrainConfig, model, snapshot_path: str, volumes: Option
     model.train()
     loss_scale = make_loss_scale(cfg.loss_scale)
     scaler = loss_scale if isinstance(loss_scale, DynamicLossScale) else None
-    loss_fn = SegLoss(cfg.num_classes, group=group, loss_scale=loss_scale)
+    loss_fn = SegLoss(cfg.num_classes, group=group, loss_scale=loss_scale, ce_weight=cfg.class_weights, dice_weight=cfg.class_weights,
+                      ignore_index=cfg.ignore_index)
     opt = FusedSGD(model, lr=cfg.base_lr, momentum=0.9, weight_decay=1e-4, clip_norm=5.0 if cfg.grad_clipping else None)
 
     def lr_at(it: int) -> float:
