@@ -5,50 +5,14 @@ import numpy as np
 import pytest
 import torch
 
+from metrics_util import DEV, dev as _dev, label_volume as _label_volume, mask_pairs
+
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
+MASK_PAIRS = mask_pairs(2024, (1, 3, 6), (2, 5, 3))
 
 
-def _dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
-
-
-def _ellipsoid(shape, centre, radii, g=None, rough=0.0):
-    """Boolean ellipsoid; `rough` perturbs the shell voxel by voxel (seeded)."""
-    grids = np.meshgrid(*[np.arange(n, dtype=np.float64) for n in shape], indexing="ij")
-    r2 = sum(((x - c) / r) ** 2 for x, c, r in zip(grids, centre, radii))
-    if rough:
-        r2 = r2 + g.uniform(-rough, rough, shape)
-    return r2 < 1.0
-
-
-def _mask_pairs():
-    g = np.random.default_rng(2024)
-    pairs = []
-    for shape in [(3, 8, 8), (5, 12, 10), (8, 20, 24), (12, 30, 30)]:                          # ellipsoids with a roughened shell
-        c = [(n - 1) / 2 for n in shape]
-        a = _ellipsoid(shape, [v + g.uniform(-1, 1) for v in c], [max(1.2, n / 3.2) for n in shape], g, 0.35)
-        b = _ellipsoid(shape, [v + g.uniform(-1.5, 1.5) for v in c], [max(1.2, n / 3.6) for n in shape], g, 0.35)
-        pairs.append((f"rough{shape}", a, b))
-    shape = (6, 16, 14)                                                                         # touching the array border
-    pairs.append(("border", _ellipsoid(shape, (0, 2, 3), (3, 6, 6)), _ellipsoid(shape, (5, 13, 12), (4, 7, 5), g, 0.3)))
-    pairs.append(("border-all", np.ones(shape, bool), _ellipsoid(shape, (2, 8, 7), (2.5, 5, 4))))
-    pairs.append(("one-slice", _ellipsoid((1, 14, 12), (0, 6, 5), (1, 4, 4)), _ellipsoid((1, 14, 12), (0, 8, 6), (1, 5, 3), g, 0.3)))
-    single = np.zeros((4, 9, 9), bool)
-    single[1, 3, 6] = True
-    pairs.append(("single-voxel", single, _ellipsoid((4, 9, 9), (2, 5, 3), (1.5, 3, 2.5))))
-    a = np.zeros((7, 10, 11), bool)
-    b = np.zeros((7, 10, 11), bool)
-    a[:2, :3, :3] = True
-    b[-2:, -3:, -2:] = True
-    pairs.append(("disjoint-corners", a, b))
-    pairs.append(("2-d", _ellipsoid((20, 26), (9, 12), (6, 8), g, 0.3), _ellipsoid((20, 26), (11, 13), (7, 6), g, 0.3)))
-    pairs.append(("2-d-border", _ellipsoid((9, 70), (0, 10), (4, 9)), _ellipsoid((9, 70), (8, 60), (5, 12))))
-    return pairs
-
-
-@pytest.mark.parametrize("name,a,b", _mask_pairs(), ids=[p[0] for p in _mask_pairs()])
+@pytest.mark.parametrize("name,a,b", MASK_PAIRS, ids=[p[0] for p in MASK_PAIRS])
 def test_hd95_device_follows_the_definition(name, a, b):
     """|hd95_device - oracle.eval_hd95| <= 1e-9.  The bound is derived: both sides interpolate in fp64 between the square roots of the same two
     integers (values < 1e3, ulp ~1e-13), and two different answers are at least sqrt(n+1) - sqrt(n) > 5e-4 apart for n < 1e6."""
@@ -73,19 +37,6 @@ def test_hd95_device_rejects_what_the_host_rejects():
             hd95_device(_dev(x), _dev(y))
     with pytest.raises(RuntimeError, match="no CPU fallback"):
         hd95_device(torch.from_numpy(b), torch.from_numpy(b))
-
-
-def _label_volume(shape, g, n_organs, skip=()):
-    """Seeded uint8 label volume: overlapping roughened ellipsoids, later labels painted over earlier ones.  A skipped organ draws the
-    same random numbers, so two volumes from one seed differ only in the organs skipped."""
-    lab = np.zeros(shape, np.uint8)
-    for k in range(1, n_organs + 1):
-        c = [g.uniform(0.2 * n, 0.8 * n) for n in shape]
-        r = [g.uniform(0.08 * n, 0.22 * n) + 1.0 for n in shape]
-        m = _ellipsoid(shape, c, r, g, 0.25)
-        if k not in skip:
-            lab[m] = k
-    return lab
 
 
 def test_intermediate_results_are_exact():

@@ -1,21 +1,23 @@
-// Evaluation metrics on the device: the integer side of calculate_metric_percase (utils.py:50-60, called per class at utils.py:96-98) --
+// Evaluation metrics on the device: the device side of calculate_metric_percase (utils.py:50-60, called per class at utils.py:96-98) --
 // per-class Dice counts and the exact HD95 order statistics of a predicted label volume against a ground-truth one, both uint8 [D,H,W].
 //
 //   surface voxel of a mask  = mask voxel with at least one of its 6 face neighbours outside the mask, the outside of the array counting as
 //                              background (scipy binary_erosion, connectivity 1, border_value 0);
-//   distance                 = Euclidean, unit spacing, from every surface voxel of one mask to the nearest surface voxel of the other, both
-//                              directions pooled;
+//   distance                 = Euclidean, from every surface voxel of one mask to the nearest surface voxel of the other, both directions
+//                              pooled; with a voxel spacing (sz, sy, sx) the squared distance is (sz dz)^2 + (sy dy)^2 + (sx dx)^2;
 //   HD95                     = numpy.percentile(pooled, 95).
 //
-// With unit spacing every squared distance is an integer, so everything here is int32 / integer atomics and the result does not depend on
-// arrival order: (1) one pass writes a surface map per label volume (a voxel has one label, so surf[v] = lab[v] on the surface of class
-// lab[v], else 0, holds every class) and the Dice counts; (2) the squared Euclidean distance transform to {surf == k} is separable: the
-// distance to the nearest source inside the row, then out[i] = min_j f[j] + (i-j)^2 along y and along z; (3) a histogram of the squared
-// distances met on the other mask's surface; (4) its two order statistics around position 0.95 (n-1).  The host takes two square roots.
+// (1) One pass writes a surface map per label volume (a voxel has one label, so surf[v] = lab[v] on the surface of class lab[v], else 0,
+// holds every class) and the Dice counts; (2) the squared Euclidean distance transform to {surf == k} is separable: the distance to the
+// nearest source inside the row, then out[i] = min_j f[j] + (s (i-j))^2 along y and along z -- one body per pass, instantiated for int32
+// maps (unit spacing: every squared distance is an integer) and for float64 maps; then the two order statistics around position
+// 0.95 (n-1) of the squared distances met on the other mask's surface: (3, 4) with unit spacing from a histogram indexed by the squared
+// distance, (5) with a spacing by a radix select over the doubles.  Integer atomics only, so no result depends on arrival order.  The
+// host takes two square roots.
 #include "tc_common.h"
 
 #define MT_MAXCLS 16
-#define MT_MAXDIM 2048                    // longest line: a [L][8] int32 tile is 64 KB of the 160 KB LDS, and 3 * 2047^2 + 2^28 stays far inside int32
+#define MT_MAXDIM 2048                    // longest line: a [L][8] tile is 64 KB (int32) or 128 KB (float64) of the 160 KB LDS, and 3 * 2047^2 + 2^28 stays far inside int32
 #define MT_INF TC_METRIC_NO_SOURCE
 
 // ---- (1) surfaces and counts -------------------------------------------------------------------------------------------------------
@@ -80,9 +82,23 @@ __global__ __launch_bounds__(256) void metric_surfaces_kernel(const unsigned cha
 }
 
 // ---- (2) exact squared Euclidean distance transform ---------------------------------------------------------------------------------
+// What the element type of a map decides: the value where there is no source, the squared length of d steps of size s, and the minimum.
+template <typename T> struct MtElem;
+template <> struct MtElem<int> {
+    static __device__ __forceinline__ int none() { return MT_INF; }
+    static __device__ __forceinline__ int sq(double, int d) { return d * d; }                  // unit spacing
+    static __device__ __forceinline__ int min(int a, int b) { return ::min(a, b); }
+};
+template <> struct MtElem<double> {
+    static __device__ __forceinline__ double none() { return __builtin_huge_val(); }
+    static __device__ __forceinline__ double sq(double s, int d) { const double t = s * d; return t * t; }
+    static __device__ __forceinline__ double min(double a, double b) { return fmin(a, b); }
+};
+
 // x: one wave per row.  The row's sources become one 64-bit ballot per 64 voxels; a voxel finds the nearest set bit on either side with
-// clz / ffs, walking whole words where its own has none.
-__global__ __launch_bounds__(256) void metric_edt_x_kernel(const unsigned char* __restrict__ surf, int k, int* __restrict__ d2, int rows, int W) {
+// clz / ffs, walking whole words where its own has none: d2 = (sx dx)^2, "no source" in a row without one.
+template <typename T>
+__global__ __launch_bounds__(256) void metric_edt_x_kernel(const unsigned char* __restrict__ surf, int k, T* __restrict__ d2, int rows, int W, double sx) {
     __shared__ unsigned long long masks[4][MT_MAXDIM / 64];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int row = blockIdx.x * 4 + wave;
@@ -98,83 +114,109 @@ __global__ __launch_bounds__(256) void metric_edt_x_kernel(const unsigned char* 
     }
     __syncthreads();
     if (!live) return;
-    int* o = d2 + (long long)row * W;
+    T* o = d2 + (long long)row * W;
     for (int c0 = 0; c0 < nch; ++c0) {
         const int x = c0 * 64 + lane;
         if (x >= W) break;
-        int best = MT_INF;
+        T best = MtElem<T>::none();
         if (any) {
-            int c = c0;
+            int near = MT_MAXDIM, c = c0;
             unsigned long long m = masks[wave][c] & (~0ull >> (63 - lane));          // sources at or left of x
             while (m == 0 && c > 0) m = masks[wave][--c];
-            if (m) { const int d = x - (c * 64 + 63 - __clzll((long long)m)); best = d * d; }
+            if (m) near = x - (c * 64 + 63 - __clzll((long long)m));
             c = c0;
             m = masks[wave][c] & (~0ull << lane);                                     // sources at or right of x
             while (m == 0 && c < nch - 1) m = masks[wave][++c];
-            if (m) { const int d = c * 64 + __ffsll((unsigned long long)m) - 1 - x; best = min(best, d * d); }
+            if (m) near = min(near, c * 64 + __ffsll((unsigned long long)m) - 1 - x);
+            best = MtElem<T>::sq(sx, near);
         }
         o[x] = best;
     }
 }
 
-// y and z: the array is [outer][L][inner] with the pass along L (y: outer = D, inner = W; z: outer = 1, inner = H*W).  A workgroup stages
-// TX neighbouring lines in LDS ([L][TX], lanes along the contiguous axis so global accesses stay coalesced and a half-wave reads one
-// conflict-free LDS row) and, for every output i, scans j outwards from i until (i-j)^2 can no longer beat the best found.  In place: a
-// workgroup reads its whole tile before it writes, and no other workgroup touches those lines.  A line without any finite value is left
-// as it is (min_j of 2^28 + (i-j)^2 is 2^28 at j = i), so only lines that the earlier passes reached are scanned.
-template <int TX>
-__global__ __launch_bounds__(256) void metric_edt_line_kernel(int* __restrict__ d2, int L, long long inner) {
-    extern __shared__ int mt_tile[];
+// y and z: the array is [outer][L][inner] with the pass along L (y: outer = D, inner = W; z: outer = 1, inner = H*W) and out[i] =
+// min_j f[j] + (s (i-j))^2.  A workgroup stages TX neighbouring lines in LDS ([L][TX], lanes along the contiguous axis so global accesses
+// stay coalesced; a half-wave reads whole neighbouring rows of the tile, 128 or 256 contiguous bytes: conflict-free, and every lane of a
+// wave is at the same step d of its scan) and, for every output i, scans j outwards from i until (s (i-j))^2 can no longer beat the best
+// found.  In place: a workgroup reads its whole tile before it writes, and no other workgroup touches those lines.  A line without any
+// finite value is left as it is (min_j of "no source" + (s (i-j))^2 is "no source" at j = i: 2^28 or +inf), so only lines that the
+// earlier passes reached are scanned.
+template <typename T, int TX>
+__global__ __launch_bounds__(256) void metric_edt_line_kernel(T* __restrict__ d2, int L, long long inner, double s) {
+    extern __shared__ double mt_lds[];                                              // one declaration for both element types, 8-byte aligned
+    T* tile = (T*)mt_lds;
     constexpr int NY = 256 / TX;
     const int tx = threadIdx.x % TX, ty = threadIdx.x / TX;
     const long long col = (long long)blockIdx.x * TX + tx;
     const bool ok = col < inner;
-    int* base = d2 + (long long)blockIdx.y * L * inner + (ok ? col : 0);
-    int* col_finite = mt_tile + L * TX;                                             // a line without a source stays as it is: nothing to scan for
+    T* base = d2 + (long long)blockIdx.y * L * inner + (ok ? col : 0);
+    int* col_finite = (int*)(tile + L * TX);                                        // a line without a source stays as it is: nothing to scan for
     if (threadIdx.x < TX) col_finite[threadIdx.x] = 0;
     __syncthreads();
+    const T none = MtElem<T>::none();
     int finite = 0;
     for (int i = ty; i < L; i += NY) {
-        const int v = ok ? base[i * inner] : MT_INF;
-        mt_tile[i * TX + tx] = v;
-        finite |= v < MT_INF;
+        const T v = ok ? base[i * inner] : none;
+        tile[i * TX + tx] = v;
+        finite |= v < none;
     }
     if (finite) col_finite[tx] = 1;
     if (!__syncthreads_or(finite)) return;
     if (!col_finite[tx]) return;                                                    // (no barrier follows)
     for (int i = ty; i < L; i += NY) {
-        int best = mt_tile[i * TX + tx];
+        T best = tile[i * TX + tx];
         const int far = max(i, L - 1 - i);
-        for (int d = 1; d <= far && d * d < best; ++d) {
-            const int dd = d * d;
-            if (i - d >= 0) best = min(best, mt_tile[(i - d) * TX + tx] + dd);
-            if (i + d < L) best = min(best, mt_tile[(i + d) * TX + tx] + dd);
+        for (int d = 1; d <= far; ++d) {
+            const T dd = MtElem<T>::sq(s, d);
+            if (!(dd < best)) break;
+            if (i - d >= 0) best = MtElem<T>::min(best, tile[(i - d) * TX + tx] + dd);
+            if (i + d < L) best = MtElem<T>::min(best, tile[(i + d) * TX + tx] + dd);
         }
         if (ok) base[i * inner] = best;
     }
 }
 
-static int mt_line_pass(int* d2, int outer, int L, long long inner, hipStream_t s) {
+// TX is the widest of 32, 16, 8 lines whose [L][TX] tile is at most 64 KB (so two workgroups share a compute unit), else 8: 32 / 16 / 8
+// for L <= 512 / 1024 / 2048 on int32 and for L <= 256 / 512 / 2048 on float64 -- at L = 512, 1024, 2048 (int32) and 256, 512, 2048
+// (float64) that is 32, 16, 8.  Behind the tile lies one flag per line: up to 64 KB + 128 B (int32), 128 KB + 32 B (float64).
+template <typename T>
+static int mt_line_pass(T* d2, int outer, int L, long long inner, double sp, hipStream_t s) {
     if (L <= 1) return TC_OK;
-    const int tx = L <= 512 ? 32 : (L <= 1024 ? 16 : 8);
-    const size_t smem = (size_t)(L + 1) * tx * sizeof(int);                          // the tile and one flag per line: <= 64 KB + 128 B
+    const size_t fits = 64 * 1024 / sizeof(T);
+    const int tx = (size_t)L * 32 <= fits ? 32 : ((size_t)L * 16 <= fits ? 16 : 8);
+    const size_t smem = (size_t)L * tx * sizeof(T) + tx * sizeof(int);
     const dim3 grid((unsigned)((inner + tx - 1) / tx), (unsigned)outer);
-    const void* fn = tx == 32 ? (const void*)metric_edt_line_kernel<32> : tx == 16 ? (const void*)metric_edt_line_kernel<16> : (const void*)metric_edt_line_kernel<8>;
-    if (smem > 64 * 1024) (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    if (tx == 32) hipLaunchKernelGGL(metric_edt_line_kernel<32>, grid, dim3(256), smem, s, d2, L, inner);
-    else if (tx == 16) hipLaunchKernelGGL(metric_edt_line_kernel<16>, grid, dim3(256), smem, s, d2, L, inner);
-    else hipLaunchKernelGGL(metric_edt_line_kernel<8>, grid, dim3(256), smem, s, d2, L, inner);
+    void (*fn)(T*, int, long long, double) = tx == 32 ? metric_edt_line_kernel<T, 32> : (tx == 16 ? metric_edt_line_kernel<T, 16> : metric_edt_line_kernel<T, 8>);
+    if (smem > 64 * 1024 && hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess) return TC_ERR_LAUNCH;
+    hipLaunchKernelGGL(fn, grid, dim3(256), smem, s, d2, L, inner, sp);
     return tc_launch_status();
 }
 
+template <typename T>
+static int mt_edt(const unsigned char* surf, int k, T* d2, int D, int H, int W, int zfaces, double sz, double sy, double sx, hipStream_t s) {
+    const int rows = D * H;
+    hipLaunchKernelGGL(metric_edt_x_kernel<T>, dim3((rows + 3) / 4), dim3(256), 0, s, surf, k, d2, rows, W, sx);
+    int rc = tc_launch_status();
+    if (rc == TC_OK) rc = mt_line_pass(d2, D, H, W, sy, s);
+    if (rc == TC_OK && zfaces) rc = mt_line_pass(d2, 1, D, (long long)H * W, sz, s);
+    return rc;
+}
+
 // ---- (3) histogram of squared distances ----------------------------------------------------------------------------------------------
+// The pooled multiset of class k: d2_gt on the prediction's surface and d2_pred on the ground truth's, each value handed to `f`.
+template <typename T, typename F>
+__device__ __forceinline__ void mt_for_pooled(const unsigned char* __restrict__ sP, const unsigned char* __restrict__ sG, const T* __restrict__ d2P,
+                                              const T* __restrict__ d2G, int k, int n, F f) {
+    for (long long v = (long long)blockIdx.x * 256 + threadIdx.x; v < n; v += (long long)gridDim.x * 256) {
+        if (sP[v] == k) f(d2G[v]);
+        if (sG[v] == k) f(d2P[v]);
+    }
+}
+
 __global__ __launch_bounds__(256) void metric_hist_kernel(const unsigned char* __restrict__ sP, const unsigned char* __restrict__ sG,
                                                           const int* __restrict__ d2P, const int* __restrict__ d2G, int k,
                                                           unsigned int* __restrict__ hist, long long nbins, int n) {
-    for (long long v = (long long)blockIdx.x * 256 + threadIdx.x; v < n; v += (long long)gridDim.x * 256) {
-        if (sP[v] == k) { const int d = d2G[v]; if (d < nbins) atomicAdd(&hist[d], 1u); }       // d >= nbins only when the other surface is empty
-        if (sG[v] == k) { const int d = d2P[v]; if (d < nbins) atomicAdd(&hist[d], 1u); }
-    }
+    mt_for_pooled(sP, sG, d2P, d2G, k, n, [&](int d) { if (d < nbins) atomicAdd(&hist[d], 1u); });    // d >= nbins only when the other surface is empty
 }
 
 // ---- (4) order statistics --------------------------------------------------------------------------------------------------------------
@@ -207,109 +249,19 @@ __global__ __launch_bounds__(256) void metric_select_kernel(const unsigned int* 
     }
 }
 
-// ---- (5) anisotropic voxel spacing: the same transform and order statistics in fp64 ---------------------------------------------------
-// With a spacing (sz, sy, sx) a squared distance (sz dz)^2 + (sy dy)^2 + (sx dx)^2 is no integer any more, so there is no histogram to index
-// with it.  The transform keeps its shape in doubles; the two order statistics come from a most-significant-digit radix select over the bit
-// patterns (non-negative doubles order like their bits read as uint64): integer histograms of one 8-bit digit per pass, eight passes.
+// ---- (5) order statistics of float64 maps -----------------------------------------------------------------------------------------------
+// With a spacing a squared distance is no integer any more, so there is no histogram to index with it.  The two order statistics come from
+// a most-significant-digit radix select over the bit patterns (non-negative doubles order like their bits read as uint64): integer
+// histograms of one 8-bit digit per pass, eight passes.
 #define MT_F64_INF_BITS 0x7ff0000000000000ull
 #define MT_SEL_PASSES 8
 #define MT_SEL_HIST_WORDS (MT_SEL_PASSES * 2 * 256)       // uint32 [pass][wanted position][digit], then one MtSelState
 struct MtSelState { unsigned long long prefix[2], rank[2], n; };   // per wanted position: the digits fixed so far and the position among the values that share them
 static_assert(MT_SEL_HIST_WORDS * 4 + sizeof(MtSelState) <= TC_METRIC_SELECT_WORK_BYTES, "the header's work size");
 
-// x: metric_edt_x_kernel with the nearest source's distance scaled: d2 = (sx dx)^2, +inf in a row without a source.
-__global__ __launch_bounds__(256) void metric_edt_x_f64_kernel(const unsigned char* __restrict__ surf, int k, double* __restrict__ d2, int rows, int W, double sx) {
-    __shared__ unsigned long long masks[4][MT_MAXDIM / 64];
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int row = blockIdx.x * 4 + wave;
-    const bool live = row < rows;
-    const int nch = (W + 63) >> 6;
-    const unsigned char* s = surf + (long long)(live ? row : 0) * W;
-    unsigned long long any = 0;
-    for (int c = 0; c < nch; ++c) {
-        const int x = c * 64 + lane;
-        const unsigned long long m = __ballot(live && x < W && s[x] == k);
-        if (lane == 0) masks[wave][c] = m;
-        any |= m;
-    }
-    __syncthreads();
-    if (!live) return;
-    double* o = d2 + (long long)row * W;
-    for (int c0 = 0; c0 < nch; ++c0) {
-        const int x = c0 * 64 + lane;
-        if (x >= W) break;
-        double best = __builtin_huge_val();
-        if (any) {
-            int near = MT_MAXDIM, c = c0;
-            unsigned long long m = masks[wave][c] & (~0ull >> (63 - lane));          // sources at or left of x
-            while (m == 0 && c > 0) m = masks[wave][--c];
-            if (m) near = x - (c * 64 + 63 - __clzll((long long)m));
-            c = c0;
-            m = masks[wave][c] & (~0ull << lane);                                     // sources at or right of x
-            while (m == 0 && c < nch - 1) m = masks[wave][++c];
-            if (m) near = min(near, c * 64 + __ffsll((unsigned long long)m) - 1 - x);
-            const double t = sx * near;
-            best = t * t;
-        }
-        o[x] = best;
-    }
-}
-
-// y and z: metric_edt_line_kernel on doubles, out[i] = min_j f[j] + (s (i-j))^2.  The tile is [L][TX] doubles with lanes along the contiguous
-// axis: a half-wave reads 32 / TX whole neighbouring rows, 256 contiguous bytes, which is one conflict-free bank row of an 8-byte LDS read
-// (every lane of a wave is at the same step d of its scan).  TX = 32, 16, 8 for L <= 256, 512, 2048: 64 KB of tile up to L = 1024, so two
-// workgroups share a compute unit, and 128 KB of the 160 KB for the longest lines.
-template <int TX>
-__global__ __launch_bounds__(256) void metric_edt_line_f64_kernel(double* __restrict__ d2, int L, long long inner, double s) {
-    extern __shared__ double mt_tile_f64[];
-    constexpr int NY = 256 / TX;
-    const int tx = threadIdx.x % TX, ty = threadIdx.x / TX;
-    const long long col = (long long)blockIdx.x * TX + tx;
-    const bool ok = col < inner;
-    double* base = d2 + (long long)blockIdx.y * L * inner + (ok ? col : 0);
-    int* col_finite = (int*)(mt_tile_f64 + L * TX);                                 // a line without a source stays as it is: nothing to scan for
-    if (threadIdx.x < TX) col_finite[threadIdx.x] = 0;
-    __syncthreads();
-    const double inf = __builtin_huge_val();
-    int finite = 0;
-    for (int i = ty; i < L; i += NY) {
-        const double v = ok ? base[i * inner] : inf;
-        mt_tile_f64[i * TX + tx] = v;
-        finite |= v < inf;
-    }
-    if (finite) col_finite[tx] = 1;
-    if (!__syncthreads_or(finite)) return;
-    if (!col_finite[tx]) return;                                                    // (no barrier follows)
-    for (int i = ty; i < L; i += NY) {
-        double best = mt_tile_f64[i * TX + tx];
-        const int far = max(i, L - 1 - i);
-        for (int d = 1; d <= far; ++d) {
-            const double t = s * d, dd = t * t;
-            if (!(dd < best)) break;
-            if (i - d >= 0) best = fmin(best, mt_tile_f64[(i - d) * TX + tx] + dd);
-            if (i + d < L) best = fmin(best, mt_tile_f64[(i + d) * TX + tx] + dd);
-        }
-        if (ok) base[i * inner] = best;
-    }
-}
-
-static int mt_line_pass_f64(double* d2, int outer, int L, long long inner, double sp, hipStream_t s) {
-    if (L <= 1) return TC_OK;
-    const int tx = L <= 256 ? 32 : (L <= 512 ? 16 : 8);
-    const size_t smem = (size_t)L * tx * sizeof(double) + tx * sizeof(int);          // the tile and one flag per line: <= 128 KB + 32 B
-    const dim3 grid((unsigned)((inner + tx - 1) / tx), (unsigned)outer);
-    const void* fn = tx == 32 ? (const void*)metric_edt_line_f64_kernel<32> : tx == 16 ? (const void*)metric_edt_line_f64_kernel<16> : (const void*)metric_edt_line_f64_kernel<8>;
-    if (smem > 64 * 1024 && hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess) return TC_ERR_LAUNCH;
-    if (tx == 32) hipLaunchKernelGGL(metric_edt_line_f64_kernel<32>, grid, dim3(256), smem, s, d2, L, inner, sp);
-    else if (tx == 16) hipLaunchKernelGGL(metric_edt_line_f64_kernel<16>, grid, dim3(256), smem, s, d2, L, inner, sp);
-    else hipLaunchKernelGGL(metric_edt_line_f64_kernel<8>, grid, dim3(256), smem, s, d2, L, inner, sp);
-    return tc_launch_status();
-}
-
-// One pass of the radix select.  The pooled multiset of class k is d2_gt on the prediction's surface and d2_pred on the ground truth's
-// (+inf, the distance to an empty surface, is not counted).  Of the values whose leading 8 * pass bits equal the prefix fixed for a wanted
-// position, the next 8-bit digit is counted: in LDS first, then one global atomic per workgroup and used bin.  While both positions share
-// their prefix (always in pass 0) only row 0 is filled.
+// One pass of the radix select over the pooled multiset (+inf, the distance to an empty surface, is not counted).  Of the values whose
+// leading 8 * pass bits equal the prefix fixed for a wanted position, the next 8-bit digit is counted: in LDS first, then one global atomic
+// per workgroup and used bin.  While both positions share their prefix (always in pass 0) only row 0 is filled.
 __global__ __launch_bounds__(256) void metric_select_count_kernel(const unsigned char* __restrict__ sP, const unsigned char* __restrict__ sG,
                                                                   const double* __restrict__ d2P, const double* __restrict__ d2G, int k,
                                                                   unsigned int* __restrict__ work, int pass, int n) {
@@ -327,10 +279,7 @@ __global__ __launch_bounds__(256) void metric_select_count_kernel(const unsigned
         if (lead == p0) atomicAdd(&lh[0][digit], 1u);
         else if (lead == p1) atomicAdd(&lh[1][digit], 1u);
     };
-    for (long long v = (long long)blockIdx.x * 256 + threadIdx.x; v < n; v += (long long)gridDim.x * 256) {
-        if (sP[v] == k) count(d2G[v]);
-        if (sG[v] == k) count(d2P[v]);
-    }
+    mt_for_pooled(sP, sG, d2P, d2G, k, n, count);
     __syncthreads();
     unsigned int* hist = work + pass * 512;
     if (lh[0][threadIdx.x]) atomicAdd(&hist[threadIdx.x], lh[0][threadIdx.x]);
@@ -399,13 +348,7 @@ extern "C" int tc_metric_surfaces(const unsigned char* pred, const unsigned char
 
 extern "C" int tc_metric_edt(const unsigned char* surf, int k, int* d2, int D, int H, int W, int zfaces, void* stream) {
     if (!surf || !d2 || !mt_shape_ok(D, H, W) || k <= 0 || k >= MT_MAXCLS) return TC_ERR_ARG;
-    hipStream_t s = (hipStream_t)stream;
-    const int rows = D * H;
-    hipLaunchKernelGGL(metric_edt_x_kernel, dim3((rows + 3) / 4), dim3(256), 0, s, surf, k, d2, rows, W);
-    int rc = tc_launch_status();
-    if (rc == TC_OK) rc = mt_line_pass(d2, D, H, W, s);
-    if (rc == TC_OK && zfaces) rc = mt_line_pass(d2, 1, D, (long long)H * W, s);
-    return rc;
+    return mt_edt(surf, k, d2, D, H, W, zfaces, 1.0, 1.0, 1.0, (hipStream_t)stream);
 }
 
 extern "C" int tc_metric_hist(const unsigned char* surf_pred, const unsigned char* surf_gt, const int* d2_pred, const int* d2_gt, int k,
@@ -430,13 +373,7 @@ extern "C" int tc_metric_edt_f64(const unsigned char* surf, int k, double* d2, i
                                  void* stream) {
     if (!surf || !d2 || !mt_shape_ok(D, H, W) || k <= 0 || k >= MT_MAXCLS || !mt_spacing_ok(sz) || !mt_spacing_ok(sy) || !mt_spacing_ok(sx))
         return TC_ERR_ARG;
-    hipStream_t s = (hipStream_t)stream;
-    const int rows = D * H;
-    hipLaunchKernelGGL(metric_edt_x_f64_kernel, dim3((rows + 3) / 4), dim3(256), 0, s, surf, k, d2, rows, W, sx);
-    int rc = tc_launch_status();
-    if (rc == TC_OK) rc = mt_line_pass_f64(d2, D, H, W, sy, s);
-    if (rc == TC_OK && zfaces) rc = mt_line_pass_f64(d2, 1, D, (long long)H * W, sz, s);
-    return rc;
+    return mt_edt(surf, k, d2, D, H, W, zfaces, sz, sy, sx, (hipStream_t)stream);
 }
 
 extern "C" int tc_metric_select_f64(const unsigned char* surf_pred, const unsigned char* surf_gt, const double* d2_pred, const double* d2_gt, int k,

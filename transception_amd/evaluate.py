@@ -171,19 +171,16 @@ def edt_squared(surf: torch.Tensor, k: int, out: Optional[torch.Tensor] = None, 
     With `voxelspacing`: the float64 map of min (sz dz)^2 + (sy dy)^2 + (sx dx)^2 (tc_metric_edt_f64; +inf everywhere if there is none)."""
     if not surf.is_cuda:
         raise RuntimeError(NO_CPU)
-    D, H, W = _shape3(surf.shape)
-    if voxelspacing is not None:
-        sz, sy, sx = _spacing3(voxelspacing, surf.dim())
-        if out is None:
-            out = torch.empty(surf.shape, dtype=torch.float64, device=surf.device)
-        elif out.dtype != torch.float64 or out.shape != surf.shape or not out.is_contiguous():
-            raise ValueError("with voxelspacing `out` is a contiguous float64 map of surf's shape")
-        lib().tc_metric_edt_f64(surf.contiguous().data_ptr(), k, out.data_ptr(), D, H, W, int(surf.dim() == 3), sz, sy, sx,
-                                torch.cuda.current_stream(surf.device).cuda_stream)
-        return out
+    spaced = voxelspacing is not None
+    spacing = _spacing3(voxelspacing, surf.dim()) if spaced else ()
+    dtype = torch.float64 if spaced else torch.int32
     if out is None:
-        out = torch.empty(surf.shape, dtype=torch.int32, device=surf.device)
-    lib().tc_metric_edt(surf.data_ptr(), k, out.data_ptr(), D, H, W, int(surf.dim() == 3), torch.cuda.current_stream(surf.device).cuda_stream)
+        out = torch.empty(surf.shape, dtype=dtype, device=surf.device)
+    elif spaced and (out.dtype != dtype or out.shape != surf.shape or not out.is_contiguous()):
+        raise ValueError("with voxelspacing `out` is a contiguous float64 map of surf's shape")
+    entry = lib().tc_metric_edt_f64 if spaced else lib().tc_metric_edt
+    entry(surf.contiguous().data_ptr(), k, out.data_ptr(), *_shape3(surf.shape), int(surf.dim() == 3), *spacing,
+          torch.cuda.current_stream(surf.device).cuda_stream)
     return out
 
 
@@ -191,33 +188,31 @@ def metrics_order_stats(pred: torch.Tensor, label: torch.Tensor, classes: int, v
     """int64 [2,classes,3] on the device: [0] the Dice counts, [1] (n, d2_lo, d2_hi) per class (tc_metric_select).  Allocates
     `metrics_scratch_bytes(pred.shape, classes, voxelspacing)`; the two distance maps are reused class by class.  Nothing is synchronised.
     With `voxelspacing` d2_lo and d2_hi are doubles (tc_metric_select_f64): read them with `result[1, :, 1:].view(torch.float64)`."""
-    if voxelspacing is not None:
-        spacing = _spacing3(voxelspacing, pred.dim())
+    spaced = voxelspacing is not None
+    spacing = _spacing3(voxelspacing, pred.dim())[3 - pred.dim():] if spaced else None
     sp, sg, counts = surfaces_counts(pred, label, classes)
     D, H, W = _shape3(pred.shape)
     dev = pred.device
     L, stream = lib(), torch.cuda.current_stream(dev).cuda_stream
-    if voxelspacing is not None:
+    if spaced:
         work = torch.empty(TC_METRIC_SELECT_WORK_BYTES, dtype=torch.uint8, device=dev)
-        dp, dg = torch.empty(pred.shape, dtype=torch.float64, device=dev), torch.empty(pred.shape, dtype=torch.float64, device=dev)
         res = torch.zeros((2, classes, 3), dtype=torch.int64, device=dev)             # class 0 is never selected: (0, 0.0, 0.0)
-        res[0] = counts
-        for k in range(1, classes):
-            edt_squared(sp, k, dp, spacing[3 - pred.dim():])
-            edt_squared(sg, k, dg, spacing[3 - pred.dim():])
-            L.tc_metric_select_f64(sp.data_ptr(), sg.data_ptr(), dp.data_ptr(), dg.data_ptr(), k, classes, D, H, W, work.data_ptr(),
-                                   res[1].data_ptr(), stream)
-        return res
-    nbins = metrics_hist_bins(pred.shape)
-    hist = torch.zeros((classes, nbins), dtype=torch.int32, device=dev)               # uint32 to the library
-    dp, dg = torch.empty(pred.shape, dtype=torch.int32, device=dev), torch.empty(pred.shape, dtype=torch.int32, device=dev)
-    res = torch.empty((2, classes, 3), dtype=torch.int64, device=dev)
+    else:
+        nbins = metrics_hist_bins(pred.shape)
+        hist = torch.zeros((classes, nbins), dtype=torch.int32, device=dev)           # uint32 to the library
+        res = torch.empty((2, classes, 3), dtype=torch.int64, device=dev)             # tc_metric_select writes every class
+    dp, dg = (torch.empty(pred.shape, dtype=torch.float64 if spaced else torch.int32, device=dev) for _ in range(2))
     res[0] = counts
     for k in range(1, classes):
-        edt_squared(sp, k, dp)
-        edt_squared(sg, k, dg)
-        L.tc_metric_hist(sp.data_ptr(), sg.data_ptr(), dp.data_ptr(), dg.data_ptr(), k, hist.data_ptr(), nbins, classes, D, H, W, stream)
-    L.tc_metric_select(hist.data_ptr(), nbins, classes, res[1].data_ptr(), stream)
+        edt_squared(sp, k, dp, spacing)
+        edt_squared(sg, k, dg, spacing)
+        if spaced:
+            L.tc_metric_select_f64(sp.data_ptr(), sg.data_ptr(), dp.data_ptr(), dg.data_ptr(), k, classes, D, H, W, work.data_ptr(),
+                                   res[1].data_ptr(), stream)
+        else:
+            L.tc_metric_hist(sp.data_ptr(), sg.data_ptr(), dp.data_ptr(), dg.data_ptr(), k, hist.data_ptr(), nbins, classes, D, H, W, stream)
+    if not spaced:
+        L.tc_metric_select(hist.data_ptr(), nbins, classes, res[1].data_ptr(), stream)
     return res
 
 
