@@ -1193,16 +1193,17 @@ def test_dwconv_multi_matches_torch(G, Ch, side):
         close(Bs[i].grad, br[i].grad, 5e-5, 1e-4, f"db{i}")
 
 
-def test_dwconv_multi_grouped(G):
-    """Same, with three stacked weight groups (the three MB paths of a stage run as one grouped launch)."""
+def _dwconv_multi_grouped(G, Ch, Gn, tag):
+    """The three ConvRelPosEnc convolutions on column slices of one buffer with Gn stacked weight groups in one flat arena (the three MB
+    paths of a stage run as one grouped launch), forward and backward: (y, dx, gradient arena) of the engine and of F.conv2d."""
     from transception_amd.engine import P
-    Ch, side, B, Gn = 8, 14, 2, 3
+    side, B = 14, 2
     C = 8 * Ch
     widths, ks = [2 * Ch, 3 * Ch, 3 * Ch], [3, 5, 7]
     rows = B * side * side
-    x, gy = T("dwmg.x", (Gn * rows, 3 * C)), T("dwmg.g", (Gn * rows, C))
+    x, gy = T(f"{tag}.x", (Gn * rows, 3 * C)), T(f"{tag}.g", (Gn * rows, C))
     per = sum(w * k * k + w for w, k in zip(widths, ks))
-    arena = T("dwmg.p", (Gn * per,), 0.3).to(DEV)
+    arena = T(f"{tag}.p", (Gn * per,), 0.3).to(DEV)
     garena = torch.zeros_like(arena)
     offs, o = [], 0
     for w, k in zip(widths, ks):
@@ -1229,10 +1230,65 @@ def test_dwconv_multi_grouped(G):
         xs.append(xv.colslice(2 * C + c0, 2 * C + c0 + wd)); os_.append(out.colslice(c0, c0 + wd)); c0 += wd
     with G.grouped(Gn, per):
         G.dwconv_multi(xs, Ws, Bs, (B, side, side), ks, os_)
-    close(out.data, ref, 2e-5, 2e-5, "y")
+    y = out.data.clone()
     run_bwd(G, out, gy)
-    close(G.grad_of(xv), xr.grad, 2e-5, 5e-5, "dx")
-    close(garena, ar.grad, 5e-5, 1e-4, "dw/db of all groups")
+    return (y, G.grad_of(xv), garena), (ref, xr.grad, ar.grad)
+
+
+def test_dwconv_multi_grouped(G):
+    """Same, with three stacked weight groups (the three MB paths of a stage run as one grouped launch)."""
+    (y, dx, garena), (ref, dxr, gar) = _dwconv_multi_grouped(G, 8, 3, "dwmg")
+    close(y, ref, 2e-5, 2e-5, "y")
+    close(dx, dxr, 2e-5, 5e-5, "dx")
+    close(garena, gar, 5e-5, 1e-4, "dw/db of all groups")
+
+
+@pytest.mark.parametrize("Gn", [1, 3])
+def test_dwconv_multi_deferred_weight_gradient_fold(Gn, monkeypatch):
+    """tc_dwconv_multi (mode 3) with its walkers' sums parked + tc_dw_fold (the default) against the launch that folds at its own tail
+    (TC_DW_DEFER=0), on the relative-position triple at one and at three stacked weight groups: the same dx bit for bit, dw / db to
+    summation order."""
+    from transception_amd import _lib, engine
+    from transception_amd.engine import Graph
+    res = {}
+    for defer in (True, False):
+        monkeypatch.setattr(engine, "_DW_DEFER", defer)
+        G = Graph(torch.float32, torch.device(DEV), training=True, record=True)
+        calls0 = _lib._Lib.calls
+        (_, dx, garena), (_, dxr, gar) = _dwconv_multi_grouped(G, 16, Gn, f"dwmd{Gn}")
+        assert float(garena.abs().max()) > 0
+        res[defer] = (dx.clone(), garena.clone(), _lib._Lib.calls - calls0)
+    assert res[True][2] == res[False][2] + 1                # the same C-ABI calls and the one tc_dw_fold: the sums were parked
+    assert torch.equal(res[True][0], res[False][0])
+    close(res[True][1], res[False][1].cpu(), 1e-5 * max(1.0, float(res[False][1].abs().max())), 1e-5, "dw / db")
+    close(res[True][0], dxr, 2e-5, 5e-5, "dx vs torch")
+    close(res[True][1], gar, 5e-5, 1e-4, "dw / db vs torch")
+
+
+def test_mixffn_deferred_weight_gradient_fold(monkeypatch):
+    """tc_ffn_mid_bwd (the fp32 MixFFN backward) with its walkers' sums parked + tc_dw_fold (the default) against the launch that folds at
+    its own tail (TC_DW_DEFER=0), three stacked weight groups on a non-square map: the same input gradients bit for bit, the parameter
+    gradients (the convolution's dw / db and the LayerNorm's dgamma / dbeta among them) to summation order."""
+    from test_ffn_fused_gpu import _engine_run, _params
+    from transception_amd import engine
+    C, B, H, W, groups = 64, 2, 20, 24, 3
+    gen = torch.Generator().manual_seed(11)
+    flat, offs, shapes, tot = _params(C, groups, gen)
+    M = groups * B * H * W
+    x, res_in, gout = torch.randn(M, C, generator=gen), torch.randn(M, C, generator=gen), torch.randn(M, C, generator=gen)
+    res = {}
+    for defer in (True, False):
+        monkeypatch.setattr(engine, "_DW_DEFER", defer)
+        res[defer] = _engine_run(torch.float32, True, x, flat, offs, shapes, tot, groups, B, H, W, res_in, gout)
+    for i in (0, 1, 2):                                     # output, dx, dresidual
+        assert torch.equal(res[True][i], res[False][i])
+    assert res[True][4] == res[False][4] + 1                # the same C-ABI calls and the one tc_dw_fold: the sums were parked
+    for g in range(groups):
+        for k in offs:
+            n = int(torch.tensor(shapes[k]).prod())
+            a, b = res[True][3][g * tot + offs[k]:g * tot + offs[k] + n], res[False][3][g * tot + offs[k]:g * tot + offs[k] + n]
+            assert float(b.abs().max()) > 0, k
+            close(a, b, 1e-5 * max(1.0, float(b.abs().max())), 1e-5, f"d{k}[group {g}]")
 
 
 def _flat_params(shapes, tag):

@@ -653,6 +653,93 @@ __global__ __launch_bounds__(256) void dw_tile_kernel(const T* __restrict__ src,
                                  dw_xcd_tile((int)blockIdx.x, (int)gridDim.x), blockIdx.y, blockIdx.z, smem, stat, (int)gridDim.y);
 }
 
+// segment of workgroup `lin` of a multi-segment grid (segment i's workgroups start at s[i].blk0)
+template <typename A> __device__ __forceinline__ int dw_seg_of(const A& a, int lin) {
+    int si = 0;
+    if (a.n > 1 && lin >= a.s[1].blk0) si = 1;
+    if (a.n > 2 && lin >= a.s[2].blk0) si = 2;
+    if (a.n > 3 && lin >= a.s[3].blk0) si = 3;
+    return si;
+}
+
+// Sum v of tap t, channel ch, to the gradient it belongs to: taps 0 .. kk - 1 are the filter's, tap kk the convolution's bias, and (the
+// walkers of tc_ffn_mid_bwd only) taps kk + 1 / kk + 2 the dgamma / dbeta of the LayerNorm behind the convolution.  All but dw may be null;
+// the pointers are weight group 0's, the group's own parameters goff floats further.
+__device__ __forceinline__ void dw_route_tap(int t, int kk, int ch, float v, float* dw, float* db, float* dgamma, float* dbeta, long long goff) {
+    if (t < kk) atomicAdd(dw + goff + (long long)ch * kk + t, v);         // (shared modules: a weight may have two writers)
+    else if (t == kk) { if (db) atomicAdd(db + goff + ch, v); }
+    else if (t == kk + 1) { if (dgamma) atomicAdd(dgamma + goff + ch, v); }
+    else if (dbeta) atomicAdd(dbeta + goff + ch, v);
+}
+
+// Tail of a weight-gradient walker (NTH threads; walker bx of the gx of group bz's channel chunk by of gy, channels from c0): its NT x CH sums,
+// [tap][channel] in LDS at lflat, leave the workgroup one of three ways (the host's walk_ws decides): parked, two-level fold, or atomics.
+// dw / db / dgamma / dbeta, goff: as dw_route_tap (NT == K * K + 1: a plain convolution, no dgamma / dbeta taps, goff already applied).  True for
+// the walker that routed taps.
+template <int K, int NT, int CH, int NTH>
+__device__ __forceinline__ bool dw_walker_tail(const float* lflat, float* __restrict__ ws_part, int* __restrict__ ws_cnt, const int bz, const int by,
+                                               const int gy, const int bx, const int gx, const int c0, const int C, float* dw, float* db, float* dgamma,
+                                               float* dbeta, const long long goff) {
+    int gm = 1;
+    const float* pgroup = nullptr;
+    if (ws_part && !ws_cnt) {
+        // Deferred (ws_bytes < 0): the sums go, plainly, to a buffer of this launch's own -- [group * chunks + chunk][walker][tap][channel] --
+        // and tc_dw_fold adds the walkers of every such launch of a backward leg in one launch: no write-through stores, no arrival
+        // counter, no last-arriver fold and no contended atomics at the tail of every launch (0.19 ms of a 12.2 ms step).
+        float* part = ws_part + ((long long)(bz * gy + by) * gx + bx) * (NT * CH);
+        for (int f = threadIdx.x; f < NT * CH; f += NTH) part[f] = lflat[f];
+        return false;
+    }
+    if (ws_part) {
+        // Two-level fold (same protocol as the GEMM split-K fix-up): the workgroups of a (group, channel chunk) park their sums in
+        // the workspace, DW_FOLD consecutive ones share an arrival counter, the last to arrive adds them and is the only one that
+        // touches the gradients atomically -- a contended fp32 atomic costs ~0.13 us and 128-170 workgroups used to queue on every word.
+        constexpr int FG = DW_FOLD;
+        const int chain = bz * gy + by, grp = bx / FG, ngrp = (gx + FG - 1) / FG;
+        gm = min(FG, gx - grp * FG);
+        float* part = ws_part + ((long long)chain * gx + bx) * (NT * CH);
+        pgroup = ws_part + ((long long)chain * gx + grp * FG) * (NT * CH);
+        if (gm > 1) {
+            for (int f = threadIdx.x; f < NT * CH; f += NTH) __hip_atomic_store(part + f, lflat[f], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __builtin_amdgcn_s_waitcnt(0);                          // vmcnt(0): THIS thread's write-through stores have been acknowledged
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");  // (the barrier alone does not wait for stores in flight)
+            __syncthreads();
+            __shared__ int s_last;
+            if (threadIdx.x == 0) {
+                int* c = ws_cnt + chain * ngrp + grp;
+                const int old = atomicAdd(c, 1);
+                s_last = (old == gm - 1);
+                if (s_last) atomicExch(c, 0);                       // (self-resetting: every launch leaves its counters zero)
+            }
+            __syncthreads();
+            if (!s_last) return false;
+        }
+    }
+    for (int f = threadIdx.x; f < NT * CH; f += NTH) {
+        const int t = f / CH, cc = f - t * CH, ch = c0 + cc;                // lflat is [tap][channel]
+        if (ch >= C) continue;
+        float v;
+        if (gm > 1) {
+            float tmp[DW_FOLD];                                   // all loads in flight before the first add (they bypass L2: ~2 us each)
+#pragma unroll
+            for (int m = 0; m < DW_FOLD; ++m)
+                tmp[m] = m < gm ? __hip_atomic_load(pgroup + (long long)m * (NT * CH) + f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.f;
+            v = 0.f;
+#pragma unroll
+            for (int m = 0; m < DW_FOLD; ++m) v += tmp[m];
+        } else {
+            v = lflat[f];
+        }
+        if constexpr (NT == K * K + 1) {                        // (dw_route_tap's first two cases, written out: through the call the code of every kernel on dw_tile_wgrad_body changes)
+            if (t < K * K) atomicAdd(dw + (long long)ch * K * K + t, v);
+            else if (db) atomicAdd(db + ch, v);
+        } else {
+            dw_route_tap(t, K * K, ch, v, dw, db, dgamma, dbeta, goff);
+        }
+    }
+    return true;
+}
+
 // dw[c,ky,kx] += sum_pix dy[pix] * x[pix + (ky-P, kx-P)] ; db[c] += sum_pix dy[pix].  x tile (+halo) and dy tile in LDS; a thread
 // owns (16-byte channel lane, filter row ky) and a share of the tile's (row, 4-pixel run) units, K x VEC sums in registers
 // across all the tiles its workgroup visits; LDS float atomics fold the workgroup, then one global atomic per tap and channel.
@@ -775,60 +862,7 @@ __device__ __forceinline__ void dw_tile_wgrad_body(const T* __restrict__ x, int 
 #ifdef TC_DBG_DW_NOFOLD                                            // what-if build (scripts/exp): weight gradients dropped, timing only
     return;
 #endif
-    float* lflat = &lacc[0][0];
-    int gm = 1;
-    const float* pgroup = nullptr;
-    if (ws_part && !ws_cnt) {
-        // Deferred (tc_dwconv_bwd with ws_bytes < 0): the sums go, plainly, to a buffer of this launch's own -- [group * chunks + chunk][walker]
-        // [tap][channel] -- and tc_dw_fold adds the walkers of every such launch of a backward leg in one launch: no write-through stores, no
-        // arrival counter, no last-arriver fold and no contended atomics at the tail of every launch (0.19 ms of a 12.2 ms step).
-        float* part = ws_part + ((long long)(bz * gy + by) * gx + bx) * (NT * CH);
-        for (int f = threadIdx.x; f < NT * CH; f += 256) part[f] = lflat[f];
-        return;
-    }
-    if (ws_part) {
-        // Two-level fold (same protocol as the GEMM split-K fix-up): the workgroups of a (group, channel chunk) park their sums in
-        // the workspace, 16 consecutive ones share an arrival counter, the last to arrive adds the 16 and is the only one that
-        // touches dw / db atomically -- a contended fp32 atomic costs ~0.13 us and 128-170 workgroups used to queue on every word.
-        constexpr int FG = DW_FOLD;
-        const int chain = bz * gy + by, grp = bx / FG, ngrp = (gx + FG - 1) / FG;
-        gm = min(FG, gx - grp * FG);
-        float* part = ws_part + ((long long)chain * gx + bx) * (NT * CH);
-        pgroup = ws_part + ((long long)chain * gx + grp * FG) * (NT * CH);
-        if (gm > 1) {
-            for (int f = threadIdx.x; f < NT * CH; f += 256) __hip_atomic_store(part + f, lflat[f], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __builtin_amdgcn_s_waitcnt(0);                          // vmcnt(0): THIS thread's write-through stores have been acknowledged
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");   // (the barrier alone does not wait for stores in flight)
-            __syncthreads();
-            __shared__ int s_last;
-            if (threadIdx.x == 0) {
-                int* c = ws_cnt + chain * ngrp + grp;
-                const int old = atomicAdd(c, 1);
-                s_last = (old == gm - 1);
-                if (s_last) atomicExch(c, 0);
-            }
-            __syncthreads();
-            if (!s_last) return;
-        }
-    }
-    for (int f = threadIdx.x; f < NT * CH; f += 256) {
-        const int t = f / CH, cc = f - t * CH, ch = c0 + cc;                // lacc is [tap][channel]
-        if (ch >= C) continue;
-        float v;
-        if (gm > 1) {
-            float tmp[DW_FOLD];                                   // all 16 loads in flight before the first add (they bypass L2: ~2 us each)
-#pragma unroll
-            for (int m = 0; m < DW_FOLD; ++m)
-                tmp[m] = m < gm ? __hip_atomic_load(pgroup + (long long)m * (NT * CH) + f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.f;
-            v = 0.f;
-#pragma unroll
-            for (int m = 0; m < DW_FOLD; ++m) v += tmp[m];
-        } else {
-            v = lflat[f];
-        }
-        if (t < K * K) atomicAdd(dw + (long long)ch * K * K + t, v);
-        else if (db) atomicAdd(db + ch, v);
-    }
+    dw_walker_tail<K, NT, CH, 256>(&lacc[0][0], ws_part, ws_cnt, bz, by, gy, bx, gx, c0, C, dw, db, nullptr, nullptr, 0);
 }
 
 template <typename T, int K, int CG>
@@ -874,83 +908,118 @@ template <typename T> bool dw_tile_ok(const void* a, int lda, const void* b, int
     return C % VEC == 0 && lda % VEC == 0 && ldb % VEC == 0 && (uintptr_t)a % 16 == 0 && (uintptr_t)b % 16 == 0;
 }
 
+#define TC_DW_CASES(X) X(3, 2) X(3, 4) X(3, 8) X(5, 2) X(5, 4) X(5, 8) X(7, 2) X(7, 4) X(7, 8)
+
+// Pixel-tile geometry of the 16-byte tile kernels on a [B, H, W, C] map -- the host's view of DwTile / FfnTile: cg 16-byte lanes (ch channels)
+// per chunk, tiles of TH x 16 pixels.  Every launcher and every plan reads this record.
+struct TileGeom { int cg, ch, chunks, TH, tilesW, tilesH; long long ntiles; };
+inline TileGeom tile_geom(int B, int H, int W, int C, int cg, int vec) {
+    TileGeom t;
+    t.cg = cg; t.ch = cg * vec; t.chunks = (C + t.ch - 1) / t.ch;
+    t.TH = (256 / cg) / 4; t.tilesW = (W + 15) / 16; t.tilesH = (H + t.TH - 1) / t.TH;
+    t.ntiles = (long long)B * t.tilesW * t.tilesH;
+    return t;
+}
+template <typename T> TileGeom dw_tile_geom(int B, int H, int W, int C) { return tile_geom(B, H, W, C, dw_pick_cg<T>(C), Vec16<T>::N); }
+
+// Walker layout of a launch's weight-gradient sums.  Segment i runs gx walkers per (group, channel chunk); each leaves nt x ch floats at
+// [group * chunks + chunk][walker][tap][channel], from float part0 of the launch's buffer on, and (tail fold only) every DW_FOLD walkers share
+// an arrival counter, from word cnt0 on.  ONE function per launch family builds it (dw_bwd_layout, dw_multi_layout, ffn_mid_layout); the
+// family's launcher and its plan entry both call that function, so the walkers write exactly the buffer the caller was told to allocate.
+constexpr int WALK_SEGS = 4;
+struct WalkSeg { TileGeom t; int gx, nt; long long cnt0, part0; };
+struct WalkLayout { WalkSeg s[WALK_SEGS]; long long cnts = 0, part_floats = 0; };
+inline void walk_add(WalkLayout& l, int i, const TileGeom& t, long long gx, int nt, int groups) {
+    l.s[i] = WalkSeg{t, (int)gx, nt, l.cnts, l.part_floats};
+    l.cnts += (long long)t.chunks * groups * ((gx + DW_FOLD - 1) / DW_FOLD);
+    l.part_floats += (long long)t.chunks * groups * gx * nt * t.ch;
+}
+// ~target walkers in total, shared out in proportion to each segment's tiles x chunks x cost (an even split gave the 56x56 map of a bridge
+// layer 16 workgroups of 28 tiles each next to 1-tile workgroups of the 7x7 map)
+inline WalkLayout walk_layout(const TileGeom* t, const int* cost, const int* nt, int nseg, int groups, int target) {
+    WalkLayout l;
+    long long total_work = 0;
+    for (int i = 0; i < nseg; ++i) total_work += t[i].ntiles * t[i].chunks * cost[i];
+    for (int i = 0; i < nseg; ++i) {
+        const long long gx = (long long)((double)target * (double)t[i].ntiles * cost[i] / (double)(total_work > 0 ? total_work : 1) / groups + 0.5);
+        walk_add(l, i, t[i], gx < 1 ? 1 : (gx > t[i].ntiles ? t[i].ntiles : gx), nt[i], groups);
+    }
+    return l;
+}
+inline void walk_site(const WalkSeg& w, int C, int k, int groups, TcDwFold* site) {      // what tc_dw_fold needs to know of a segment's sums
+    site->C = C; site->k = k; site->groups = groups; site->ch = w.t.ch; site->chunks = w.t.chunks; site->gx = w.gx; site->nt = w.nt;
+}
+// Where the walkers leave their sums.  ws_bytes < 0: parked in the caller's own buffer for tc_dw_fold (part only) -- TC_ERR_ARG if it is
+// unaligned or smaller than the layout.  Otherwise the TcGemm.ws contract: the first 16 KiB are zeroed arrival counters and the sums follow
+// (part and cnt: the two-level fold at the launch's tail), usable only if it is 16-byte aligned, large enough and the layout has at most 4096
+// counters; a workspace that is not usable is not an error: plain atomics (neither).
+struct WalkWs { float* part = nullptr; int* cnt = nullptr; };
+inline int walk_ws(void* ws, long long ws_bytes, const WalkLayout& l, WalkWs& o) {
+    if (ws && ws_bytes < 0) {
+        if (-ws_bytes < l.part_floats * 4 || (uintptr_t)ws % 16) return TC_ERR_ARG;
+        o.part = reinterpret_cast<float*>(ws);
+    } else if (ws && (uintptr_t)ws % 16 == 0 && ws_bytes >= 16384 + l.part_floats * 4 && l.cnts <= 4096) {
+        o.cnt = reinterpret_cast<int*>(ws); o.part = reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + 16384);
+    }
+    return TC_OK;
+}
+
+// the single convolution's walkers (tc_dwconv_bwd, tc_dwconv_bwd_weight): one workgroup per CU, each visiting ~7 tiles -- measured best with
+// the fold (contended fp32 atomics cost ~0.13 us each: few contributors per word)
+template <typename T> WalkLayout dw_bwd_layout(int B, int H, int W, int C, int k, int groups) {
+    const TileGeom t = dw_tile_geom<T>(B, H, W, C);
+    long long gx = tc_dw_wg_target() / (t.chunks * groups);
+    if (gx > t.ntiles) gx = t.ntiles;
+    WalkLayout l;
+    walk_add(l, 0, t, gx < 1 ? 1 : gx, k * k + 1, groups);
+    return l;
+}
+
 template <typename T, int MODE>
 int launch_tile(const void* src, int lds_, const void* w, const void* bias, void* y, int ldy, const void* dy, int lddy, float* dw,
                 float* db, int B, int H, int W, int C, int k, int add_input, int accumulate, int groups, long long wstride,
                 hipStream_t s, void* ws = nullptr, long long ws_bytes = 0, float* stat = nullptr) {
-    constexpr int VEC = Vec16<T>::N;
-    const int cg = dw_pick_cg<T>(C);
-    if (stat && (MODE != 0 || C % (cg * VEC))) return TC_ERR_ARG;
-    const int chunks = (C + cg * VEC - 1) / (cg * VEC);
-    const int TH = (256 / cg) / 4, tilesW = (W + 15) / 16, tilesH = (H + TH - 1) / TH;
-    const long long ntiles = (long long)B * tilesW * tilesH;
-    if (ntiles > 0x7fffffffLL) return TC_ERR_ARG;
-#define TC_TILE(KK, CGG)                                                                                                                \
-    if (MODE == 2) {                                                                                                                    \
-        int gx = tc_dw_wg_target() / (chunks * groups);   /* measured best with the fold: one workgroup per CU, each visiting ~7 tiles */ /* contended fp32 atomics cost ~0.13 us each: few contributors per word */          \
-        if (gx > ntiles) gx = (int)ntiles;                                                                                              \
-        constexpr int NTC = ((KK) * (KK) + 1) * (CGG) * VEC;                                                                            \
-        float* wp = nullptr; int* wc = nullptr;                                                                                         \
-        if (ws && (uintptr_t)ws % 16 == 0 && ws_bytes >= 16384 + (long long)chunks * groups * (gx < 1 ? 1 : gx) * NTC * 4 &&             \
-            (long long)chunks * groups * (((gx < 1 ? 1 : gx) + DW_FOLD - 1) / DW_FOLD) <= 4096) {                                                      \
-            wc = reinterpret_cast<int*>(ws); wp = reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + 16384);                         \
-        }                                                                                          \
-        gx = gx < 1 ? 1 : gx;                                                                                                           \
-        dim3 grid((unsigned)(ntiles < gx ? ntiles : gx), chunks, groups);                                                               \
-        hipLaunchKernelGGL((dw_tile_wgrad_kernel<T, KK, CGG>), grid, dim3(256), 0, s, (const T*)src, lds_, (const T*)dy, lddy, dw, db,  \
-                           B, H, W, C, wstride, tilesW, tilesH, wp, wc);                                                                        \
-    } else {                                                                                                                            \
-        dim3 grid((unsigned)ntiles, chunks, groups);                                                                                    \
-        hipLaunchKernelGGL((dw_tile_kernel<T, KK, CGG, (MODE == 2 ? 0 : MODE)>), grid, dim3(256), 0, s, (const T*)src, lds_,            \
-                           (const T*)w, (const T*)bias, (T*)y, ldy, B, H, W, C, add_input, accumulate, wstride, tilesW, tilesH, stat);  \
+    const TileGeom t = dw_tile_geom<T>(B, H, W, C);
+    if (stat && (MODE != 0 || C % t.ch)) return TC_ERR_ARG;
+    if (t.ntiles > 0x7fffffffLL) return TC_ERR_ARG;
+    dim3 grid((unsigned)t.ntiles, t.chunks, groups);
+    WalkWs o;
+    if (MODE == 2) {
+        const WalkLayout l = dw_bwd_layout<T>(B, H, W, C, k, groups);
+        walk_ws(ws_bytes < 0 ? nullptr : ws, ws_bytes, l, o);              // (this entry has no deferred form: tail fold or atomics)
+        grid.x = (unsigned)l.s[0].gx;
     }
-#define TC_TILE_K(KK) { if (cg == 8) { TC_TILE(KK, 8) } else if (cg == 4) { TC_TILE(KK, 4) } else { TC_TILE(KK, 2) } }
-    if (k == 3) TC_TILE_K(3) else if (k == 5) TC_TILE_K(5) else TC_TILE_K(7)
-#undef TC_TILE_K
-#undef TC_TILE
+#define TC_CASE(KK, CGG)                                                                                                                \
+    if (k == KK && t.cg == CGG) {                                                                                                       \
+        if (MODE == 2)                                                                                                                  \
+            hipLaunchKernelGGL((dw_tile_wgrad_kernel<T, KK, CGG>), grid, dim3(256), 0, s, (const T*)src, lds_, (const T*)dy, lddy, dw, db,  \
+                               B, H, W, C, wstride, t.tilesW, t.tilesH, o.part, o.cnt);                                                 \
+        else                                                                                                                            \
+            hipLaunchKernelGGL((dw_tile_kernel<T, KK, CGG, (MODE == 2 ? 0 : MODE)>), grid, dim3(256), 0, s, (const T*)src, lds_,        \
+                               (const T*)w, (const T*)bias, (T*)y, ldy, B, H, W, C, add_input, accumulate, wstride, t.tilesW, t.tilesH, stat); \
+    }
+    TC_DW_CASES(TC_CASE)
+#undef TC_CASE
     return tc_launch_status();
-}
-
-struct DwGeom { int cg, ch, chunks, gx, nt; };
-template <typename T> DwGeom dw_bwd_geom(int B, int H, int W, int C, int k, int groups) {     // ONE statement of the one-launch backward's geometry: launch_tile_bwd launches it, tc_dwconv_bwd_plan hands it to the fold
-    constexpr int VEC = Vec16<T>::N;
-    DwGeom g;
-    g.cg = dw_pick_cg<T>(C); g.ch = g.cg * VEC; g.chunks = (C + g.ch - 1) / g.ch;
-    const int TH = (256 / g.cg) / 4, tilesW = (W + 15) / 16, tilesH = (H + TH - 1) / TH;
-    const long long ntiles = (long long)B * tilesW * tilesH;
-    long long gx = tc_dw_wg_target() / (g.chunks * groups);
-    if (gx > ntiles) gx = ntiles;
-    g.gx = (int)(gx < 1 ? 1 : gx); g.nt = k * k + 1;
-    return g;
 }
 
 template <typename T>
 int launch_tile_bwd(const void* dy, int lddy, const void* w, void* dx, int lddx, const void* x, int ldx, float* dw, float* db, int B, int H, int W,
                     int C, int k, int add_input, int accumulate, int groups, long long wstride, hipStream_t s, void* ws, long long ws_bytes) {
-    constexpr int VEC = Vec16<T>::N;
-    const DwGeom geo = dw_bwd_geom<T>(B, H, W, C, k, groups);      // (the plan the caller sized and described its deferred sums with)
-    const int cg = geo.cg, chunks = geo.chunks;
-    const int TH = (256 / cg) / 4, tilesW = (W + 15) / 16, tilesH = (H + TH - 1) / TH;
-    const long long ntiles = (long long)B * tilesW * tilesH;
-    if (ntiles > 0x3fffffffLL) return TC_ERR_ARG;
-#define TC_TILE(KK, CGG) {                                                                                                              \
-        const int gx = geo.gx;                                                                                                          \
-        constexpr int NTC = ((KK) * (KK) + 1) * (CGG) * VEC;                                                                            \
-        float* wp = nullptr; int* wc = nullptr;                                                                                         \
-        if (ws && ws_bytes < 0) {                                  /* deferred: the caller's own buffer, folded later by tc_dw_fold */   \
-            if (-ws_bytes < (long long)chunks * groups * gx * NTC * 4 || (uintptr_t)ws % 16) return TC_ERR_ARG;                          \
-            wp = reinterpret_cast<float*>(ws);                                                                                          \
-        } else if (ws && (uintptr_t)ws % 16 == 0 && ws_bytes >= 16384 + (long long)chunks * groups * gx * NTC * 4 &&                     \
-            (long long)chunks * groups * ((gx + DW_FOLD - 1) / DW_FOLD) <= 4096) {                                                      \
-            wc = reinterpret_cast<int*>(ws); wp = reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + 16384);                         \
-        }                                                                                                                               \
-        dim3 grid((unsigned)(gx + ntiles), chunks, groups);                                                                             \
+    const WalkLayout l = dw_bwd_layout<T>(B, H, W, C, k, groups);  // (the plan the caller sized and described its deferred sums with)
+    const TileGeom& t = l.s[0].t;
+    const int gx = l.s[0].gx;
+    if (t.ntiles > 0x3fffffffLL) return TC_ERR_ARG;
+    WalkWs o;
+    if (walk_ws(ws, ws_bytes, l, o) != TC_OK) return TC_ERR_ARG;
+    const dim3 grid((unsigned)(gx + t.ntiles), t.chunks, groups);
+#define TC_CASE(KK, CGG)                                                                                                                \
+    if (k == KK && t.cg == CGG)                                                                                                         \
         hipLaunchKernelGGL((dw_tile_bwd_kernel<T, KK, CGG>), grid, dim3(256), 0, s, (const T*)dy, lddy, (const T*)w, (T*)dx, lddx,       \
-                           (const T*)x, ldx, dw, db, B, H, W, C, add_input, accumulate, wstride, tilesW, tilesH, wp, wc, gx, (int)ntiles); }
-#define TC_TILE_K(KK) { if (cg == 8) TC_TILE(KK, 8) else if (cg == 4) TC_TILE(KK, 4) else TC_TILE(KK, 2) }
-    if (k == 3) TC_TILE_K(3) else if (k == 5) TC_TILE_K(5) else TC_TILE_K(7)
-#undef TC_TILE_K
-#undef TC_TILE
+                           (const T*)x, ldx, dw, db, B, H, W, C, add_input, accumulate, wstride, t.tilesW, t.tilesH, o.part, o.cnt, gx, \
+                           (int)t.ntiles);
+    TC_DW_CASES(TC_CASE)
+#undef TC_CASE
     return tc_launch_status();
 }
 
@@ -980,19 +1049,14 @@ struct DwSegDev {
     int C, k, cg, chunks, tilesW, tilesH, gx, blk0, lds_, ldy, lddy, B, H, W;
     int nt;           // mode 3: input-gradient tiles per chunk row, after the gx weight-gradient walkers
 };
-constexpr int DW_MULTI_MAX = 4;
+constexpr int DW_MULTI_MAX = WALK_SEGS;
 struct DwMultiDev { DwSegDev s[DW_MULTI_MAX]; int n, add_input, accumulate; long long wstride; };
-
-#define TC_DW_CASES(X) X(3, 2) X(3, 4) X(3, 8) X(5, 2) X(5, 4) X(5, 8) X(7, 2) X(7, 4) X(7, 8)
 
 template <typename T, int MODE>
 __global__ __launch_bounds__(256) void dw_multi_kernel(DwMultiDev a) {
     extern __shared__ uint4 dsm[];
-    int lin = blockIdx.x, si = 0;
-    if (a.n > 1 && lin >= a.s[1].blk0) si = 1;
-    if (a.n > 2 && lin >= a.s[2].blk0) si = 2;
-    if (a.n > 3 && lin >= a.s[3].blk0) si = 3;
-    const DwSegDev& g = a.s[si];
+    int lin = blockIdx.x;
+    const DwSegDev& g = a.s[dw_seg_of(a, lin)];
     lin -= g.blk0;
     const int bx = dw_xcd_tile(lin % g.gx, g.gx), by = lin / g.gx;
 #define TC_CASE(KK, CGG)                                                                                                            \
@@ -1009,11 +1073,8 @@ __global__ __launch_bounds__(256) void dw_multi_kernel(DwMultiDev a) {
 template <typename T>
 __global__ __launch_bounds__(256) void dw_multi_wgrad_kernel(DwMultiDev a) {
     extern __shared__ uint4 dsm[];
-    int lin = blockIdx.x, si = 0;
-    if (a.n > 1 && lin >= a.s[1].blk0) si = 1;
-    if (a.n > 2 && lin >= a.s[2].blk0) si = 2;
-    if (a.n > 3 && lin >= a.s[3].blk0) si = 3;
-    const DwSegDev& g = a.s[si];
+    int lin = blockIdx.x;
+    const DwSegDev& g = a.s[dw_seg_of(a, lin)];
     lin -= g.blk0;
     const int bx = lin % g.gx, by = lin / g.gx;
 #define TC_CASE(KK, CGG)                                                                                                            \
@@ -1031,11 +1092,8 @@ __global__ __launch_bounds__(256) void dw_multi_wgrad_kernel(DwMultiDev a) {
 template <typename T>
 __global__ __launch_bounds__(256) void dw_multi_bwd_kernel(DwMultiDev a) {
     extern __shared__ uint4 dsm[];
-    int lin = blockIdx.x, si = 0;
-    if (a.n > 1 && lin >= a.s[1].blk0) si = 1;
-    if (a.n > 2 && lin >= a.s[2].blk0) si = 2;
-    if (a.n > 3 && lin >= a.s[3].blk0) si = 3;
-    const DwSegDev& g = a.s[si];
+    int lin = blockIdx.x;
+    const DwSegDev& g = a.s[dw_seg_of(a, lin)];
     lin -= g.blk0;
     const int nw = g.gx * g.chunks;
     const bool wg = lin < nw;
@@ -1062,76 +1120,50 @@ template <typename T> int dw_smem_q(int k, int cg, bool wgrad) {
     return 0;
 }
 
-// Weight-gradient walkers of segment i of a multi-segment launch: ~tc_dw_wg_target() workgroups in total, shared out in proportion to each
-// segment's tiles x chunks x (k + 2) (an even split gave the 56x56 map of a bridge layer 16 workgroups of 28 tiles each next to 1-tile
-// workgroups of the 7x7 map).  ONE statement: launch_multi launches it, tc_dwconv_multi_plan describes the deferred sums with it.
-template <typename T> long long dw_multi_work(const TcDwSeg* segs, int nseg) {
-    constexpr int VEC = Vec16<T>::N;
-    long long total_work = 0;
+// Weight-gradient walkers of a multi-segment launch: ~tc_dw_wg_target() workgroups in total; the cost of a tile grows roughly with k (k filter
+// rows per thread, k-wide window).  launch_multi launches this layout, tc_dwconv_multi_plan describes the deferred sums with it.
+template <typename T> WalkLayout dw_multi_layout(const TcDwSeg* segs, int nseg, int groups) {
+    TileGeom t[DW_MULTI_MAX];
+    int cost[DW_MULTI_MAX], nt[DW_MULTI_MAX];
     for (int i = 0; i < nseg; ++i) {
-        const int cg = dw_pick_cg<T>(segs[i].C), TH = (256 / cg) / 4;
-        total_work += (long long)segs[i].B * ((segs[i].W + 15) / 16) * ((segs[i].H + TH - 1) / TH) * ((segs[i].C + cg * VEC - 1) / (cg * VEC)) *
-                      (segs[i].k + 2);                  // cost per tile grows roughly with k (k filter rows per thread, k-wide window)
+        t[i] = dw_tile_geom<T>(segs[i].B, segs[i].H, segs[i].W, segs[i].C);
+        cost[i] = segs[i].k + 2; nt[i] = segs[i].k * segs[i].k + 1;
     }
-    return total_work;
-}
-inline long long dw_multi_gx(long long ntiles, int k, long long total_work, int groups) {
-    long long gx = (long long)((double)tc_dw_wg_target() * (double)ntiles * (k + 2) / (double)(total_work > 0 ? total_work : 1) / groups + 0.5);
-    return gx < 1 ? 1 : (gx > ntiles ? ntiles : gx);
+    return walk_layout(t, cost, nt, nseg, groups, tc_dw_wg_target());
 }
 
 template <typename T>
 int launch_multi(const TcDwSeg* segs, int nseg, int mode, int add_input, int accumulate, int groups, long long wstride, void* ws,
                  long long ws_bytes, hipStream_t s) {
-    constexpr int VEC = Vec16<T>::N;
     DwMultiDev a;
     a.n = nseg; a.add_input = add_input; a.accumulate = accumulate;
     a.wstride = wstride;
-    long long blk = 0, part_floats = 0, cnts = 0;
+    long long blk = 0;
     int smem_q = 0;
     const bool wgm = mode >= 2;                                  // weight-gradient walkers in the grid (mode 3: followed by the input-gradient tiles)
-    const bool defer = wgm && ws && ws_bytes < 0;                // the walkers' sums go to the caller's own buffer (tc_dw_fold adds them later)
-    if (defer && (uintptr_t)ws % 16) return TC_ERR_ARG;
-    const bool have_ws = !defer && wgm && ws && (uintptr_t)ws % 16 == 0 && ws_bytes > 16384;
-    const long long total_work = dw_multi_work<T>(segs, nseg);
+    const WalkLayout l = wgm ? dw_multi_layout<T>(segs, nseg, groups) : WalkLayout{};
+    WalkWs o;
+    if (wgm && walk_ws(ws, ws_bytes, l, o) != TC_OK) return TC_ERR_ARG;
     for (int i = 0; i < nseg; ++i) {
         const TcDwSeg& g = segs[i];
+        const WalkSeg& wk = l.s[i];
+        const TileGeom t = wgm ? wk.t : dw_tile_geom<T>(g.B, g.H, g.W, g.C);
         DwSegDev& d = a.s[i];
         d.src = g.x; d.w = g.w; d.bias = g.bias; d.y = g.y; d.dy = g.dy; d.dw = g.dw; d.db = g.db; d.C = g.C; d.k = g.k;
         d.lds_ = g.ldx; d.ldy = g.ldy; d.lddy = g.lddy; d.B = g.B; d.H = g.H; d.W = g.W;
-        const int B = g.B, H = g.H, W = g.W;
-        d.cg = dw_pick_cg<T>(g.C);
+        d.cg = t.cg; d.chunks = t.chunks; d.tilesW = t.tilesW; d.tilesH = t.tilesH; d.nt = (int)t.ntiles;
         d.stat = mode == 0 ? g.stat : nullptr;
-        if (d.stat && (g.k != 3 || g.C % (d.cg * VEC))) return TC_ERR_ARG;
-        d.chunks = (g.C + d.cg * VEC - 1) / (d.cg * VEC);
-        const int TH = (256 / d.cg) / 4;
-        d.tilesW = (W + 15) / 16; d.tilesH = (H + TH - 1) / TH;
-        const long long ntiles = (long long)B * d.tilesW * d.tilesH;
-        d.nt = (int)ntiles;
-        if (wgm) {
-            // ~256 workgroups in total, shared out in proportion to each segment's tiles x chunks (an even split gave the 56x56
-            // map of a bridge layer 16 workgroups of 28 tiles each next to 1-tile workgroups of the 7x7 map)
-            const long long gx = dw_multi_gx(ntiles, g.k, total_work, groups);
-            d.gx = (int)gx;
-            const long long nt_ch = (long long)(g.k * g.k + 1) * d.cg * VEC;
-            d.wsc = have_ws ? reinterpret_cast<int*>(ws) + cnts : nullptr;
-            d.wsp = have_ws ? reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + 16384) + part_floats : nullptr;
-            if (defer) d.wsp = reinterpret_cast<float*>(ws) + part_floats;
-            cnts += (long long)d.chunks * groups * ((gx + DW_FOLD - 1) / DW_FOLD);
-            part_floats += (long long)d.chunks * groups * gx * nt_ch;
-        } else {
-            d.gx = (int)ntiles; d.wsc = nullptr; d.wsp = nullptr;
-        }
+        if (d.stat && (g.k != 3 || g.C % t.ch)) return TC_ERR_ARG;
+        d.gx = wgm ? wk.gx : (int)t.ntiles;                    // (modes 0 / 1: one workgroup per tile, no walkers)
+        d.wsc = o.cnt ? o.cnt + wk.cnt0 : nullptr;
+        d.wsp = o.part ? o.part + wk.part0 : nullptr;
         d.blk0 = (int)blk;
-        blk += ((long long)d.gx + (mode == 3 ? ntiles : 0)) * d.chunks;
-        const int q = dw_smem_q<T>(g.k, d.cg, wgm), q2 = mode == 3 ? dw_smem_q<T>(g.k, d.cg, false) : 0;
+        blk += ((long long)d.gx + (mode == 3 ? t.ntiles : 0)) * t.chunks;
+        const int q = dw_smem_q<T>(g.k, t.cg, wgm), q2 = mode == 3 ? dw_smem_q<T>(g.k, t.cg, false) : 0;
         smem_q = q > smem_q ? q : smem_q;
         smem_q = q2 > smem_q ? q2 : smem_q;
     }
     if (blk > 0x7fffffffLL) return TC_ERR_ARG;
-    if (defer && part_floats * 4 > -ws_bytes) return TC_ERR_ARG;
-    if (wgm && have_ws && (cnts > 4096 || 16384 + part_floats * 4 > ws_bytes))
-        for (int i = 0; i < nseg; ++i) { a.s[i].wsc = nullptr; a.s[i].wsp = nullptr; }
     const size_t smem = (size_t)smem_q * 16;
     dim3 grid((unsigned)blk, groups);
     if (mode == 0) {
@@ -1166,7 +1198,7 @@ struct FfnSegDev {
     float* dw; float* db; float* dgamma; float* dbeta; float* wsp; int* wsc;
     int C, ldg, ldd, ldh, lddh, B, H, W, nch2, chunks, tilesW, tilesH, gx, blk0;
 };
-constexpr int FFN_MULTI_MAX = 4;
+constexpr int FFN_MULTI_MAX = WALK_SEGS;
 struct FfnMultiDev { FfnSegDev s[FFN_MULTI_MAX]; int n; int dbg_nofold; long long wstride; };
 
 template <typename T> struct FfnTile {
@@ -1452,87 +1484,35 @@ __device__ __forceinline__ void ffn_mid_bwd_body(const FfnSegDev& a, long long w
     __syncthreads();
     MSTAMP(8);
     if (dbg_nofold) return;                                       // timing what-if only (the host passes 0): parameter gradients are dropped
-    float* lflat = &lacc[0][0];
-    int gm = 1;
-    const float* pgroup = nullptr;
-    if (a.wsp && !a.wsc) {                                        // deferred (ws_bytes < 0): sums parked for tc_dw_fold, as dw_tile_wgrad_body
-        float* part = a.wsp + ((long long)(bz * a.chunks + by) * a.gx + bx) * (NT * CH);
-        for (int f = tid; f < NT * CH; f += NTH) part[f] = lflat[f];
-        return;
+    if (dw_walker_tail<K, NT, CH, NTH>(&lacc[0][0], a.wsp, a.wsc, bz, by, a.chunks, bx, a.gx, c0, C, a.dw, a.db, a.dgamma, a.dbeta, bz * wstride)) {
+        MSTAMP(9);
     }
-    if (a.wsp) {                                                  // two-level fold, as dw_tile_wgrad_body
-        constexpr int FG = DW_FOLD;
-        const int chain = bz * a.chunks + by, grp = bx / FG, ngrp = (a.gx + FG - 1) / FG;
-        gm = min(FG, a.gx - grp * FG);
-        float* part = a.wsp + ((long long)chain * a.gx + bx) * (NT * CH);
-        pgroup = a.wsp + ((long long)chain * a.gx + grp * FG) * (NT * CH);
-        if (gm > 1) {
-            for (int f = tid; f < NT * CH; f += NTH) __hip_atomic_store(part + f, lflat[f], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __builtin_amdgcn_s_waitcnt(0);
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-            __syncthreads();
-            __shared__ int s_last;
-            if (tid == 0) {
-                int* cn = a.wsc + chain * ngrp + grp;
-                const int old = atomicAdd(cn, 1);
-                s_last = (old == gm - 1);
-                if (s_last) atomicExch(cn, 0);
-            }
-            __syncthreads();
-            if (!s_last) return;
-        }
-    }
-    float* dwp = a.dw + bz * wstride;
-    float* dbp = a.db ? a.db + bz * wstride : nullptr;
-    float* dgp = a.dgamma ? a.dgamma + bz * wstride : nullptr;
-    float* dbtp = a.dbeta ? a.dbeta + bz * wstride : nullptr;
-    for (int f = tid; f < NT * CH; f += NTH) {
-        const int t = f / CH, cc = f - t * CH, ch = c0 + cc;
-        if (ch >= C) continue;
-        float v;
-        if (gm > 1) {
-            float tmp[DW_FOLD];
-#pragma unroll
-            for (int m = 0; m < DW_FOLD; ++m)
-                tmp[m] = m < gm ? __hip_atomic_load(pgroup + (long long)m * (NT * CH) + f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.f;
-            v = 0.f;
-#pragma unroll
-            for (int m = 0; m < DW_FOLD; ++m) v += tmp[m];
-        } else {
-            v = lflat[f];
-        }
-        if (t < K * K) atomicAdd(dwp + (long long)ch * K * K + t, v);
-        else if (t == K * K) { if (dbp) atomicAdd(dbp + ch, v); }
-        else if (t == K * K + 1) { if (dgp) atomicAdd(dgp + ch, v); }
-        else if (dbtp) atomicAdd(dbtp + ch, v);
-    }
-    MSTAMP(9);
 }
 
 template <typename T, int NTH>
 __global__ __launch_bounds__(NTH, 1) void ffn_mid_bwd_kernel(FfnMultiDev q) {
     extern __shared__ uint4 dsm[];
-    int lin = blockIdx.x, si = 0;
-    if (q.n > 1 && lin >= q.s[1].blk0) si = 1;
-    if (q.n > 2 && lin >= q.s[2].blk0) si = 2;
-    if (q.n > 3 && lin >= q.s[3].blk0) si = 3;
-    const FfnSegDev& g = q.s[si];
+    int lin = blockIdx.x;
+    const FfnSegDev& g = q.s[dw_seg_of(q, lin)];
     lin -= g.blk0;
     ffn_mid_bwd_body<T, NTH>(g, q.wstride, lin % g.gx, lin / g.gx, blockIdx.y, dsm, q.dbg_nofold);
 }
 
-// Tile walkers of segment i of a tc_ffn_mid_bwd launch: ~tc_mid_wg_target() workgroups in total, shared out by tiles x chunks.  ONE statement
-// for launch_ffn_mid_bwd and tc_ffn_mid_plan (the deferred sums are laid out by it).
-template <typename T> long long ffn_mid_work(const TcFfnSeg* segs, int nseg) {
+template <typename T> TileGeom ffn_tile_geom(int B, int H, int W, int C) {
     using D = FfnTile<T>;
-    long long total_work = 0;
-    for (int i = 0; i < nseg; ++i)
-        total_work += (long long)segs[i].B * ((segs[i].W + 15) / 16) * ((segs[i].H + D::TH - 1) / D::TH) * ((segs[i].C + D::CH - 1) / D::CH);
-    return total_work;
+    static_assert(D::TH == (256 / D::CG) / 4 && D::TW == 16 && D::CH == D::CG * D::VEC, "FfnTile is a tile_geom() tile");
+    return tile_geom(B, H, W, C, D::CG, D::VEC);
 }
-inline long long ffn_mid_gx(long long ntiles, long long total_work, int groups) {
-    long long gx = (long long)((double)tc_mid_wg_target() * (double)ntiles / (double)(total_work > 0 ? total_work : 1) / groups + 0.5);
-    return gx < 1 ? 1 : (gx > ntiles ? ntiles : gx);
+// Tile walkers of a tc_ffn_mid_bwd launch: ~tc_mid_wg_target() workgroups in total (one per CU), shared out by tiles x chunks; every channel
+// chunk gets gx of them.  launch_ffn_mid_bwd launches this layout, tc_ffn_mid_plan describes the deferred sums with it.
+template <typename T> WalkLayout ffn_mid_layout(const TcFfnSeg* segs, int nseg, int groups) {
+    TileGeom t[FFN_MULTI_MAX];
+    int cost[FFN_MULTI_MAX], nt[FFN_MULTI_MAX];
+    for (int i = 0; i < nseg; ++i) {
+        t[i] = ffn_tile_geom<T>(segs[i].B, segs[i].H, segs[i].W, segs[i].C);
+        cost[i] = 1; nt[i] = FfnTile<T>::NT;
+    }
+    return walk_layout(t, cost, nt, nseg, groups, tc_mid_wg_target());
 }
 
 template <typename T>
@@ -1541,13 +1521,13 @@ int launch_ffn_mid_bwd(const TcFfnSeg* segs, int nseg, int groups, long long wst
     static_assert(D::smem_q * 16 <= 64 * 1024, "static dynamic-LDS limit");
     FfnMultiDev q;
     q.n = nseg; q.wstride = wstride; q.dbg_nofold = 0;
-    long long blk = 0, part_floats = 0, cnts = 0;
-    const bool defer = ws && ws_bytes < 0;                       // the walkers' sums go to the caller's own buffer (tc_dw_fold adds them later)
-    if (defer && (uintptr_t)ws % 16) return TC_ERR_ARG;
-    const bool have_ws = !defer && ws && (uintptr_t)ws % 16 == 0 && ws_bytes > 16384;
-    const long long total_work = ffn_mid_work<T>(segs, nseg);
+    long long blk = 0;
+    const WalkLayout l = ffn_mid_layout<T>(segs, nseg, groups);
+    WalkWs o;
+    if (walk_ws(ws, ws_bytes, l, o) != TC_OK) return TC_ERR_ARG;
     for (int i = 0; i < nseg; ++i) {
         const TcFfnSeg& g = segs[i];
+        const WalkSeg& wk = l.s[i];
         FfnSegDev& d = q.s[i];
         if (!g.gp || !g.d || !g.h || !g.dh || !g.stat || !g.part2 || !g.w || !g.gamma || !g.dw || g.C <= 0 || g.C % D::VEC || g.nch2 < 1 ||
             !dw_tile_ok<T>(g.gp, g.ldg, g.d, g.ldd, g.C) || !dw_tile_ok<T>(g.h, g.ldh, g.dh, g.lddh, g.C) ||
@@ -1556,24 +1536,13 @@ int launch_ffn_mid_bwd(const TcFfnSeg* segs, int nseg, int groups, long long wst
         d.gp = g.gp; d.d = g.d; d.h = g.h; d.dh = g.dh; d.stat = g.stat; d.part2 = g.part2; d.w = g.w; d.gamma = g.gamma;
         d.dw = g.dw; d.db = g.db; d.dgamma = g.dgamma; d.dbeta = g.dbeta;
         d.C = g.C; d.ldg = g.ldg; d.ldd = g.ldd; d.ldh = g.ldh; d.lddh = g.lddh; d.B = g.B; d.H = g.H; d.W = g.W; d.nch2 = g.nch2;
-        d.chunks = (g.C + D::CH - 1) / D::CH;
-        d.tilesW = (g.W + 15) / 16; d.tilesH = (g.H + D::TH - 1) / D::TH;
-        const long long ntiles = (long long)g.B * d.tilesW * d.tilesH;
-        // ~256 workgroups in total (one per CU), shared out by tiles x chunks; every channel chunk gets gx tile walkers
-        const long long gx = ffn_mid_gx(ntiles, total_work, groups);
-        d.gx = (int)gx;
-        d.wsc = have_ws ? reinterpret_cast<int*>(ws) + cnts : nullptr;
-        d.wsp = have_ws ? reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + 16384) + part_floats : nullptr;
-        if (defer) d.wsp = reinterpret_cast<float*>(ws) + part_floats;
-        cnts += (long long)d.chunks * groups * ((gx + DW_FOLD - 1) / DW_FOLD);
-        part_floats += (long long)d.chunks * groups * gx * D::NT * D::CH;
+        d.chunks = wk.t.chunks; d.tilesW = wk.t.tilesW; d.tilesH = wk.t.tilesH; d.gx = wk.gx;
+        d.wsc = o.cnt ? o.cnt + wk.cnt0 : nullptr;
+        d.wsp = o.part ? o.part + wk.part0 : nullptr;
         d.blk0 = (int)blk;
-        blk += gx * d.chunks;
+        blk += (long long)wk.gx * wk.t.chunks;
     }
     if (blk > 0x7fffffffLL) return TC_ERR_ARG;
-    if (defer && part_floats * 4 > -ws_bytes) return TC_ERR_ARG;
-    if (have_ws && (cnts > 4096 || 16384 + part_floats * 4 > ws_bytes))
-        for (int i = 0; i < nseg; ++i) { q.s[i].wsc = nullptr; q.s[i].wsp = nullptr; }
     const size_t smem = (size_t)D::smem_q * 16;
     // 512 threads: two waves per SIMD (one wave per SIMD, 256 threads: 14.18 vs 13.95 ms per step)
     hipLaunchKernelGGL((ffn_mid_bwd_kernel<T, 512>), dim3((unsigned)blk, groups), dim3(512), smem, s, q);
@@ -1665,21 +1634,17 @@ __global__ __launch_bounds__(256) void dw_fold_kernel(const DwFoldDev q) {
     v = (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
     const int tap = f / t.ch, ch = c0 + (f - tap * t.ch);
     if (ch >= t.C) return;
-    if (tap < t.kk) atomicAdd(t.dw + g * t.wstride + (long long)ch * t.kk + tap, v);      // (shared modules: a weight may have two writers)
-    else if (tap == t.kk) { if (t.db) atomicAdd(t.db + g * t.wstride + ch, v); }
-    else if (tap == t.kk + 1) { if (t.dgamma) atomicAdd(t.dgamma + g * t.wstride + ch, v); }   // tc_ffn_mid_bwd: the LayerNorm behind the convolution
-    else if (t.dbeta) atomicAdd(t.dbeta + g * t.wstride + ch, v);
+    dw_route_tap(tap, t.kk, ch, v, t.dw, t.db, t.dgamma, t.dbeta, g * t.wstride);
 }
 }  // namespace
 
 extern "C" long long tc_dwconv_bwd_plan(int B, int H, int W, int C, int k, int groups, int dtype, TcDwFold* site) {
     if (!site || groups < 1 || !dw_args_ok(B, H, W, C, k, 1, 0)) return 0;
     TC_DISPATCH_DTYPE(dtype, {
-        constexpr int VEC = Vec16<T>::N;
-        if (C % VEC) return 0;
-        const DwGeom g = dw_bwd_geom<T>(B, H, W, C, k, groups);
-        site->C = C; site->k = k; site->groups = groups; site->ch = g.ch; site->chunks = g.chunks; site->gx = g.gx; site->nt = g.nt;
-        return (long long)g.chunks * groups * g.gx * g.nt * g.ch;
+        if (C % Vec16<T>::N) return 0;
+        const WalkLayout l = dw_bwd_layout<T>(B, H, W, C, k, groups);
+        walk_site(l.s[0], C, k, groups, site);
+        return l.part_floats;
     });
     return 0;
 }
@@ -1687,23 +1652,15 @@ extern "C" long long tc_dwconv_bwd_plan(int B, int H, int W, int C, int k, int g
 // the same for the weight-gradient walkers of a tc_dwconv_multi launch (mode 2 or 3): sites[i] / offs[i] (floats into the one buffer) per segment
 extern "C" long long tc_dwconv_multi_plan(const TcDwSeg* segs, int nseg, int groups, int dtype, TcDwFold* sites, long long* offs) {
     if (!segs || !sites || !offs || nseg < 1 || nseg > DW_MULTI_MAX || groups < 1) return 0;
-    long long total = 0;
     TC_DISPATCH_DTYPE(dtype, {
-        constexpr int VEC = Vec16<T>::N;
         for (int i = 0; i < nseg; ++i)
-            if (segs[i].C % VEC || !dw_args_ok(segs[i].B, segs[i].H, segs[i].W, segs[i].C, segs[i].k, 1, 0)) return 0;
-        const long long total_work = dw_multi_work<T>(segs, nseg);
-        for (int i = 0; i < nseg; ++i) {                         // launch_multi's numbers
-            const TcDwSeg& g = segs[i];
-            const int cg = dw_pick_cg<T>(g.C), ch = cg * VEC, chunks = (g.C + ch - 1) / ch, TH = (256 / cg) / 4;
-            const long long ntiles = (long long)g.B * ((g.W + 15) / 16) * ((g.H + TH - 1) / TH);
-            const long long gx = dw_multi_gx(ntiles, g.k, total_work, groups);
-            sites[i].C = g.C; sites[i].k = g.k; sites[i].groups = groups; sites[i].ch = ch; sites[i].chunks = chunks; sites[i].gx = (int)gx;
-            sites[i].nt = g.k * g.k + 1;
-            offs[i] = total;
-            total += (long long)chunks * groups * gx * (g.k * g.k + 1) * ch;
+            if (segs[i].C % Vec16<T>::N || !dw_args_ok(segs[i].B, segs[i].H, segs[i].W, segs[i].C, segs[i].k, 1, 0)) return 0;
+        const WalkLayout l = dw_multi_layout<T>(segs, nseg, groups);
+        for (int i = 0; i < nseg; ++i) {
+            walk_site(l.s[i], segs[i].C, segs[i].k, groups, &sites[i]);
+            offs[i] = l.s[i].part0;
         }
-        return total;
+        return l.part_floats;
     });
     return 0;
 }
@@ -1813,8 +1770,8 @@ extern "C" int tc_dwconv_multi(const TcDwSeg* segs, int nseg, int mode, int add_
 /* see include/transception_hip.h */
 extern "C" int tc_ffn_chunk(int C, int dtype) {
     if (C <= 0) return TC_ERR_ARG;
-    if (dtype == TC_F32) return dw_pick_cg<float>(C) * Vec16<float>::N;
-    if (dtype == TC_BF16 || dtype == TC_F16) return dw_pick_cg<bf16_t>(C) * Vec16<bf16_t>::N;
+    if (dtype == TC_F32) return dw_tile_geom<float>(1, 1, 1, C).ch;
+    if (dtype == TC_BF16 || dtype == TC_F16) return dw_tile_geom<bf16_t>(1, 1, 1, C).ch;
     return TC_ERR_ARG;
 }
 
@@ -1836,21 +1793,14 @@ extern "C" int tc_mid_dbg_read(long long* dst) { return (int)hipMemcpyFromSymbol
 extern "C" long long tc_ffn_mid_plan(const TcFfnSeg* segs, int nseg, int groups, int dtype, TcDwFold* sites, long long* offs) {
     if (!segs || !sites || !offs || nseg < 1 || nseg > FFN_MULTI_MAX || groups < 1) return 0;
     TC_DISPATCH_DTYPE(dtype, {
-        using D = FfnTile<T>;
-        long long total = 0;
-        const long long total_work = ffn_mid_work<T>(segs, nseg);
-        for (int i = 0; i < nseg; ++i) {                         // launch_ffn_mid_bwd's numbers
-            const TcFfnSeg& g = segs[i];
-            if (g.C <= 0 || g.C % D::VEC) return 0;
-            const int chunks = (g.C + D::CH - 1) / D::CH;
-            const long long ntiles = (long long)g.B * ((g.W + 15) / 16) * ((g.H + D::TH - 1) / D::TH);
-            const long long gx = ffn_mid_gx(ntiles, total_work, groups);
-            sites[i].C = g.C; sites[i].k = 3; sites[i].groups = groups; sites[i].ch = D::CH; sites[i].chunks = chunks; sites[i].gx = (int)gx;
-            sites[i].nt = D::NT;
-            offs[i] = total;
-            total += (long long)chunks * groups * gx * D::NT * D::CH;
+        for (int i = 0; i < nseg; ++i)
+            if (segs[i].C <= 0 || segs[i].C % Vec16<T>::N) return 0;
+        const WalkLayout l = ffn_mid_layout<T>(segs, nseg, groups);
+        for (int i = 0; i < nseg; ++i) {
+            walk_site(l.s[i], segs[i].C, 3, groups, &sites[i]);
+            offs[i] = l.s[i].part0;
         }
-        return total;
+        return l.part_floats;
     });
     return 0;
 }

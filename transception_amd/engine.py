@@ -18,7 +18,7 @@ from typing import Callable, Dict, List, Optional, Tuple
 
 import torch
 
-from ._lib import (ATTN_DKV_SPLITS, EW_COPY, EW_DEINTERLEAVE, EW_PATCHIFY, TcEffAtt, TcEwSeg, TcFfnBwd, TcFfnFused, ACT_COORD, ACT_GELU, ACT_HSWISH, ACT_NONE, ACT_SCALE, ACT_SIGMOID, FFN_EP, FFN_LN_A, FFN_LN_B, TC_BF16, TC_F16, TC_F32, TcDwSeg, TcFfnSeg,
+from ._lib import (ATTN_DKV_SPLITS, EW_COPY, EW_DEINTERLEAVE, EW_PATCHIFY, TcEffAtt, TcEwSeg, TcFfnBwd, TcFfnFused, ACT_COORD, ACT_GELU, ACT_HSWISH, ACT_NONE, ACT_SCALE, ACT_SIGMOID, FFN_EP, FFN_LN_A, FFN_LN_B, TC_BF16, TC_F16, TC_F32, TcDwFold, TcDwSeg, TcFfnSeg,
                    TcGemm, lib)
 
 _DT = {torch.float32: TC_F32, torch.bfloat16: TC_BF16, torch.float16: TC_F16}
@@ -401,9 +401,29 @@ class Graph:
                 json.dump(SEG_LABELS, f)
         return True
 
+    def _dw_walkers(self, plan, launch, dests):
+        """One depthwise weight-gradient launch.  plan(sites, offs) -> the floats its walkers would park, with sites[i]'s geometry and its
+        offset offs[i] filled in (0 floats, or plan None: this launch cannot defer); launch(ws_ptr, ws_bytes) launches it; dests[i] = site i's
+        (dw, db, dgamma, dbeta, wstride).  The sums are parked in a buffer of the launch's own and the sites queued for the leg's one
+        tc_dw_fold, or, where the launch cannot defer, folded at its tail through the shared workspace."""
+        n = len(dests)
+        sites, offs = (TcDwFold * n)(), (C.c_longlong * n)()
+        nf = int(plan(sites, offs)) if plan is not None else 0
+        if nf <= 0:
+            ws = _workspace(self.dev)
+            launch(ws.data_ptr(), ws.numel())
+            return
+        part = self.f32(nf)
+        launch(_ptr(part), -4 * nf)
+        for i, (dw, db, dgamma, dbeta, wstride) in enumerate(dests):
+            site = TcDwFold()
+            C.memmove(C.byref(site), C.byref(sites[i]), C.sizeof(TcDwFold))
+            site.part, site.wstride = _ptr(part) + 4 * offs[i], wstride
+            site.dw, site.db, site.dgamma, site.dbeta = dw, db, dgamma, dbeta
+            self._dw_pending.append((site, part))
+
     def _flush_dw_folds(self):
         """One launch adds the parked walker sums of every depthwise weight gradient since the last flush (tc_dw_fold)."""
-        from ._lib import TcDwFold
         for c0 in range(0, len(self._dw_pending), 48):                # (tc_dw_fold takes up to 48 sites: its argument block stays below 4 KiB)
             chunk = self._dw_pending[c0:c0 + 48]
             arr = (TcDwFold * len(chunk))(*[site for site, _ in chunk])
@@ -901,27 +921,13 @@ class Graph:
                                    _ptr(t["lg"].data), _ptr(t["wd"].grad) if hg else None, _ptr(t["bd"].grad) if hg else None,
                                    _ptr(t["lg"].grad) if hg else None, _ptr(t["lb"].grad) if hg else None,
                                    t["C4"], t["C4"], t["C4"], t["C4"], t["C4"], t["B"], t["H"], t["W"], t["nch2"])
-            nf = 0
-            if _DW_DEFER and all(t["wd"].grad is not None for t in st):     # the walkers' sums parked; one tc_dw_fold per backward leg
-                from ._lib import TcDwFold
-                sites, offs = (TcDwFold * n)(), (C.c_longlong * n)()
-                nf = int(L.tc_ffn_mid_plan(segs, n, Gn, self.dt, sites, offs))
-            if nf > 0:
-                part = self.f32(nf)
-                _timed("hbm:ffn_mid_bwd (MixFFN LayerNorm backward + dw3x3 input/weight gradients)",
-                       sum(4.0 * t["x"].rows * t["C4"] * t["h"].element_size() for t in st),
-                       lambda: L.tc_ffn_mid_bwd(segs, n, Gn, gs, _ptr(part), -4 * nf, self.dt, self.stream))
-                for i, t in enumerate(st):
-                    sf = TcDwFold()
-                    C.memmove(C.byref(sf), C.byref(sites[i]), C.sizeof(TcDwFold))
-                    sf.part, sf.wstride = _ptr(part) + 4 * offs[i], gs
-                    sf.dw, sf.db, sf.dgamma, sf.dbeta = _ptr(t["wd"].grad), _ptr(t["bd"].grad), _ptr(t["lg"].grad), _ptr(t["lb"].grad)
-                    self._dw_pending.append((sf, part))
-            else:
-                ws = _workspace(self.dev)
-                _timed("hbm:ffn_mid_bwd (MixFFN LayerNorm backward + dw3x3 input/weight gradients)",
-                       sum(4.0 * t["x"].rows * t["C4"] * t["h"].element_size() for t in st),
-                       lambda: L.tc_ffn_mid_bwd(segs, n, Gn, gs, ws.data_ptr(), ws.numel(), self.dt, self.stream))
+            self._dw_walkers(
+                (lambda sites, offs: L.tc_ffn_mid_plan(segs, n, Gn, self.dt, sites, offs))
+                if _DW_DEFER and all(t["wd"].grad is not None for t in st) else None,
+                lambda wsp, wsb: _timed("hbm:ffn_mid_bwd (MixFFN LayerNorm backward + dw3x3 input/weight gradients)",
+                                        sum(4.0 * t["x"].rows * t["C4"] * t["h"].element_size() for t in st),
+                                        lambda: L.tc_ffn_mid_bwd(segs, n, Gn, gs, wsp, wsb, self.dt, self.stream)),
+                [(_ptr(t["wd"].grad), _ptr(t["bd"].grad), _ptr(t["lg"].grad), _ptr(t["lb"].grad), gs) for t in st])
             # fc1: dX = dh W1, dW1 = dh^T x (+ db1)
             g2 = []
             for i, t in enumerate(st):
@@ -1187,25 +1193,16 @@ class Graph:
             if x.requires_grad and w.grad is not None and stride == 1 and _DW_BWD_ONE:
                 gx, acc = self.wgrad(x)                       # both gradients in one launch (they share dy and nothing else)
                 vec = 16 // es
-                from ._lib import TcDwFold
-                site = TcDwFold()
-                nf = (int(self.L.tc_dwconv_bwd_plan(B, H, W, Cc, k, Gn, self.dt, C.byref(site)))
-                      if (_DW_DEFER and not (x.ld % vec or dy.stride(0) % vec or gx.stride(0) % vec or _ptr(dy) % 16 or _ptr(x.data) % 16 or _ptr(gx) % 16))
-                      else 0)
-                if nf > 0:                                    # the walkers' sums parked in a buffer of this launch's own; one tc_dw_fold per backward leg
-                    part = self.f32(nf)
-                    _timed("hbm:dwconv_bwd (input + weight gradient, one launch)", (2.0 * x.rows * (1 + acc) + 2.0 * out.rows) * Cc * es,
-                           lambda: self.L.tc_dwconv_bwd(_ptr(dy), dy.stride(0), _ptr(x.data), x.ld, _ptr(w.data), _ptr(gx), gx.stride(0), _ptr(w.grad),
-                                                        _ptr(b.grad) if b is not None else None, B, H, W, Cc, k, int(add_input), acc, Gn, w.gs,
-                                                        _ptr(part), -4 * nf, self.dt, self.stream))
-                    site.part, site.dw, site.db, site.wstride = _ptr(part), _ptr(w.grad), _ptr(b.grad) if b is not None else None, w.gs
-                    self._dw_pending.append((site, part))
-                    return
-                ws = _workspace(self.dev)
-                _timed("hbm:dwconv_bwd (input + weight gradient, one launch)", (2.0 * x.rows * (1 + acc) + 2.0 * out.rows) * Cc * es,
-                       lambda: self.L.tc_dwconv_bwd(_ptr(dy), dy.stride(0), _ptr(x.data), x.ld, _ptr(w.data), _ptr(gx), gx.stride(0), _ptr(w.grad),
-                                                    _ptr(b.grad) if b is not None else None, B, H, W, Cc, k, int(add_input), acc, Gn, w.gs,
-                                                    ws.data_ptr(), ws.numel(), self.dt, self.stream))
+                db = _ptr(b.grad) if b is not None else None
+                # only the tile kernels park their sums: dw_tile_ok (dwconv.hip) restated, as tc_dwconv_bwd applies it to its three maps
+                tile_ok = not (x.ld % vec or dy.stride(0) % vec or gx.stride(0) % vec or _ptr(dy) % 16 or _ptr(x.data) % 16 or _ptr(gx) % 16)
+                self._dw_walkers(
+                    (lambda sites, offs: self.L.tc_dwconv_bwd_plan(B, H, W, Cc, k, Gn, self.dt, C.byref(sites[0]))) if _DW_DEFER and tile_ok else None,
+                    lambda wsp, wsb: _timed("hbm:dwconv_bwd (input + weight gradient, one launch)", (2.0 * x.rows * (1 + acc) + 2.0 * out.rows) * Cc * es,
+                                            lambda: self.L.tc_dwconv_bwd(_ptr(dy), dy.stride(0), _ptr(x.data), x.ld, _ptr(w.data), _ptr(gx), gx.stride(0),
+                                                                         _ptr(w.grad), db, B, H, W, Cc, k, int(add_input), acc, Gn, w.gs, wsp, wsb,
+                                                                         self.dt, self.stream)),
+                    [(_ptr(w.grad), db, None, None, w.gs)])
                 return
             if x.requires_grad:
                 gx, acc = self.wgrad(x)
@@ -1256,22 +1253,10 @@ class Graph:
                 sg = segs([_ptr(x.data) for x in xs], wd, none, [_ptr(t) for t, _ in g], [_ptr(d) for d in dys],
                           [_ptr(w.grad) for w in ws], [_ptr(b.grad) if b is not None else None for b in bs],
                           [x.ld for x in xs], [t.stride(0) for t, _ in g], ldd)
-                if _DW_DEFER:                                     # the walkers' sums parked; one tc_dw_fold per backward leg
-                    from ._lib import TcDwFold
-                    sites, offs = (TcDwFold * n)(), (C.c_longlong * n)()
-                    nf = int(self.L.tc_dwconv_multi_plan(sg, n, Gn, self.dt, sites, offs))
-                    if nf > 0:
-                        part = self.f32(nf)
-                        self.L.tc_dwconv_multi(sg, n, 3, int(add_input), acc, Gn, gs, _ptr(part), -4 * nf, self.dt, self.stream)
-                        for i in range(n):
-                            st = TcDwFold()
-                            C.memmove(C.byref(st), C.byref(sites[i]), C.sizeof(TcDwFold))
-                            st.part, st.dw, st.wstride = _ptr(part) + 4 * offs[i], _ptr(ws[i].grad), gs
-                            st.db = _ptr(bs[i].grad) if bs[i] is not None else None
-                            self._dw_pending.append((st, part))
-                        return
-                wk = _workspace(self.dev)
-                self.L.tc_dwconv_multi(sg, n, 3, int(add_input), acc, Gn, gs, wk.data_ptr(), wk.numel(), self.dt, self.stream)
+                self._dw_walkers(
+                    (lambda sites, offs: self.L.tc_dwconv_multi_plan(sg, n, Gn, self.dt, sites, offs)) if _DW_DEFER else None,
+                    lambda wsp, wsb: self.L.tc_dwconv_multi(sg, n, 3, int(add_input), acc, Gn, gs, wsp, wsb, self.dt, self.stream),
+                    [(_ptr(w.grad), _ptr(b.grad) if b is not None else None, None, None, gs) for w, b in zip(ws, bs)])
                 return
             if xs[0].requires_grad:
                 g = [self.wgrad(x) for x in xs]
