@@ -58,7 +58,7 @@ template <int MODE> __global__ __launch_bounds__(256) void rate_kernel(float* ou
             for (int e = 0; e < 8; e += 2) { const tc_f32x2 x = {v[e], v[e + 1]}; const tc_f32x2 u = x * phi_poly2(x); v[e] = u.x * 1.5f - 0.3f; v[e + 1] = u.y * 1.5f + 0.2f; }
         } else if constexpr (MODE == 6) {                          // A-S value + gradient (the backward's pair), packed
 #pragma unroll
-            for (int e = 0; e < 8; e += 2) { tc_f32x2 pdf; const tc_f32x2 x = {v[e], v[e + 1]}; const tc_f32x2 cdf = gelu_cdf_pdf2_fast(x, pdf); const tc_f32x2 u = x * cdf + (cdf + x * pdf) * 0.1f; v[e] = u.x - 0.3f; v[e + 1] = u.y + 0.2f; }
+            for (int e = 0; e < 8; e += 2) { tc_f32x2 pdf; const tc_f32x2 x = {v[e], v[e + 1]}; const tc_f32x2 cdf = gelu_cdf_pdf2<true>(x, pdf); const tc_f32x2 u = x * cdf + (cdf + x * pdf) * 0.1f; v[e] = u.x - 0.3f; v[e + 1] = u.y + 0.2f; }
         } else if constexpr (MODE == 8) {                          // 8 x v_dot2_f32_bf16 (two bf16 products into an fp32 accumulator)
             const unsigned w = __float_as_uint(seed) | 0x3f803f80u;
 #pragma unroll

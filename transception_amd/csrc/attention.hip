@@ -12,7 +12,6 @@
 // (workgroup owns 128 queries, loops over keys); scores are recomputed from the saved log-sum-exp.
 #include "tc_common.h"
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 namespace {
 
@@ -55,7 +54,7 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const T* __restrict__ Q, 
     const float qs = scale * LOG2E;
 #pragma unroll
     for (int t = 0; t < 32; ++t) qreg[t] = (q < Nq) ? ldf<T>(Qb + (long long)q * ldq + 2 * t + h) * qs : 0.f;
-    f32x16 acc0, acc1;
+    tc_f32x16 acc0, acc1;
 #pragma unroll
     for (int r = 0; r < 16; ++r) { acc0[r] = 0.f; acc1[r] = 0.f; }
     float m = NEG_BIG, lsum = 0.f;
@@ -65,7 +64,7 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const T* __restrict__ Q, 
         load_tile<T>(Ks, LDK, Kb, ldk, kv0, Nk, tid, 256);
         load_tile<T>(Vs, D, Vb, ldv, kv0, Nk, tid, 256);
         __syncthreads();
-        f32x16 s;
+        tc_f32x16 s;
 #pragma unroll
         for (int r = 0; r < 16; ++r) s[r] = 0.f;
         const float* kp = Ks + krow * LDK + h;
@@ -141,7 +140,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(const T* __restrict__ 
     }
     const float l2 = ok ? lse[(long long)b * Nq + q] * LOG2E : 0.f;
     const float dl = ok ? delta[(long long)b * Nq + q] : 0.f;
-    f32x16 acc0, acc1;
+    tc_f32x16 acc0, acc1;
 #pragma unroll
     for (int r = 0; r < 16; ++r) { acc0[r] = 0.f; acc1[r] = 0.f; }
     const int krow = pi_row(j);
@@ -150,7 +149,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(const T* __restrict__ 
         load_tile<T>(Ks, LDK, K + b * skv, ldk, kv0, Nk, tid, 256);
         load_tile<T>(Vs, LDK, V + b * skv, ldv, kv0, Nk, tid, 256);
         __syncthreads();
-        f32x16 s, dp;
+        tc_f32x16 s, dp;
 #pragma unroll
         for (int r = 0; r < 16; ++r) { s[r] = 0.f; dp[r] = 0.f; }
         const float* kp = Ks + krow * LDK + h;
@@ -210,7 +209,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(const T* __restrict__
         kreg[t] = kok ? ldf<T>(K + b * skv + (long long)key * ldk + 2 * t + h) * qs : 0.f;
         vreg[t] = kok ? ldf<T>(V + b * skv + (long long)key * ldv + 2 * t + h) : 0.f;
     }
-    f32x16 dk0, dk1, dv0, dv1;
+    tc_f32x16 dk0, dk1, dv0, dv1;
 #pragma unroll
     for (int r = 0; r < 16; ++r) { dk0[r] = dk1[r] = dv0[r] = dv1[r] = 0.f; }
     const T* Qb = Q + b * sq;
@@ -227,7 +226,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(const T* __restrict__
         }
         __builtin_amdgcn_s_waitcnt(0xc07f);          // lgkmcnt(0): LDS writes of this wave have landed
         __builtin_amdgcn_wave_barrier();
-        f32x16 s, dp;
+        tc_f32x16 s, dp;
 #pragma unroll
         for (int r = 0; r < 16; ++r) { s[r] = 0.f; dp[r] = 0.f; }
         // S[query][key] and dP[query][key]: A = Q / dO rows (read through pi so register r of half h is query 16h + r)
@@ -300,7 +299,7 @@ constexpr int LDR = D + 8;       // bf16 row stride of row-major [key][d] tiles 
 constexpr int LDTB = KB + 8;     // bf16 row stride of transposed [d][key] tiles (272 B)
 
 __device__ __forceinline__ bf16x8 ld_frag(const bf16_t* p) { return *reinterpret_cast<const bf16x8*>(p); }
-__device__ __forceinline__ bf16x8 pack8(const f32x16& v, int o) {
+__device__ __forceinline__ bf16x8 pack8(const tc_f32x16& v, int o) {
     bf16x8 r;
 #pragma unroll
     for (int i = 0; i < 8; ++i) r[i] = (__bf16)v[o + i];
@@ -335,7 +334,7 @@ __global__ __launch_bounds__(256) void attn_fwd_bf16_kernel(const bf16_t* __rest
         qf[ks] = *reinterpret_cast<const bf16x8*>(&v);
     }
     const float qs = scale * LOG2E;
-    f32x16 acc0, acc1;
+    tc_f32x16 acc0, acc1;
 #pragma unroll
     for (int r = 0; r < 16; ++r) { acc0[r] = 0.f; acc1[r] = 0.f; }
     float m = NEG_BIG, lsum = 0.f;
@@ -352,7 +351,7 @@ __global__ __launch_bounds__(256) void attn_fwd_bf16_kernel(const bf16_t* __rest
         for (int sub = 0; sub < KB / 32; ++sub) {
             const int kv0 = kb0 + 32 * sub;
             if (kv0 >= Nk) break;
-            f32x16 s;
+            tc_f32x16 s;
 #pragma unroll
             for (int r = 0; r < 16; ++r) s[r] = 0.f;
             const bf16_t* kp = Ks + (32 * sub + krow) * LDR + 8 * h;
@@ -416,7 +415,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_bf16_kernel(const bf16_t* __r
     const float qs = scale * LOG2E;
     const float l2 = ok ? lse[(long long)b * Nq + q] * LOG2E : 0.f;
     const float dl = ok ? delta[(long long)b * Nq + q] : 0.f;
-    f32x16 acc0, acc1;
+    tc_f32x16 acc0, acc1;
 #pragma unroll
     for (int r = 0; r < 16; ++r) { acc0[r] = 0.f; acc1[r] = 0.f; }
     const int krow = pi_row(j);
@@ -434,7 +433,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_bf16_kernel(const bf16_t* __r
         for (int sub = 0; sub < KB / 32; ++sub) {
             const int kv0 = kb0 + 32 * sub;
             if (kv0 >= Nk) break;
-            f32x16 s, dp;
+            tc_f32x16 s, dp;
 #pragma unroll
             for (int r = 0; r < 16; ++r) { s[r] = 0.f; dp[r] = 0.f; }
             const bf16_t* kp = Ks + (32 * sub + krow) * LDR + 8 * h;
@@ -497,7 +496,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_bf16_kernel(const bf16_t* __
         vf[ks] = *reinterpret_cast<const bf16x8*>(&c);
     }
     const float qs = scale * LOG2E;
-    f32x16 dk0, dk1, dv0, dv1;
+    tc_f32x16 dk0, dk1, dv0, dv1;
 #pragma unroll
     for (int r = 0; r < 16; ++r) { dk0[r] = dk1[r] = dv0[r] = dv1[r] = 0.f; }
     const int qrow = pi_row(j);
@@ -518,7 +517,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_bf16_kernel(const bf16_t* __
         }
         __builtin_amdgcn_s_waitcnt(0xc07f);
         __builtin_amdgcn_wave_barrier();
-        f32x16 s, dp;
+        tc_f32x16 s, dp;
 #pragma unroll
         for (int r = 0; r < 16; ++r) { s[r] = 0.f; dp[r] = 0.f; }
         const bf16_t* qp = Qs + qrow * LDR + 8 * h;

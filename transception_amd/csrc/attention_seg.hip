@@ -10,7 +10,6 @@
 #include <type_traits>
 #include <cstdlib>
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 namespace {
@@ -31,7 +30,7 @@ struct Segs {
 __device__ __forceinline__ int pi_row(int i) { return 16 * ((i >> 2) & 1) + (i & 3) + 4 * (i >> 3); }
 __device__ __forceinline__ int d_row(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
 template <typename V8> __device__ __forceinline__ V8 ld_frag(const bf16_t* p) { return *reinterpret_cast<const V8*>(p); }
-template <typename H> __device__ __forceinline__ typename TcHalf<H>::v8 pack8(const f32x16& v, int o) {
+template <typename H> __device__ __forceinline__ typename TcHalf<H>::v8 pack8(const tc_f32x16& v, int o) {
     typename TcHalf<H>::v8 r;
 #pragma unroll
     for (int i = 0; i < 8; ++i) r[i] = (typename TcHalf<H>::e)v[o + i];
@@ -40,16 +39,8 @@ template <typename H> __device__ __forceinline__ typename TcHalf<H>::v8 pack8(co
 // [keys][d] tiles kept row-major in LDS and consumed as MFMA A-operands with keys as the k index are gathered by the hardware
 // transpose read: lane i of a 16-lane group hands in the address of key row (i >> 2) of a 4-key block, d columns 4 (i & 3).., and
 // receives column i.  With 144-byte rows the 4 rows of a read must lie 4 rows apart to start 16 banks apart, so the keys of every
-// 16-key group are stored 4x4-transposed (row = (key & ~15) | (key & 3) << 2 | (key >> 2) & 3): conflict-free, one 16-byte LDS
-// store per strip instead of eight 2-byte transposed ones.
-typedef short s16x4_t __attribute__((ext_vector_type(4)));
-typedef short s16x8_t __attribute__((ext_vector_type(8)));
-template <typename V8> __device__ __forceinline__ V8 ld_frag_tr(const bf16_t* lo, const bf16_t* hi) {
-    const s16x4_t a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4_t __attribute__((address_space(3)))*)(lo));
-    const s16x4_t b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4_t __attribute__((address_space(3)))*)(hi));
-    return __builtin_bit_cast(V8, (s16x8_t)__builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7));
-}
-__device__ __forceinline__ int key_row(int r) { return (r & ~15) | ((r & 3) << 2) | ((r >> 2) & 3); }
+// 16-key group are stored 4x4-transposed (tc_krow of tc_common.h; the stream generators call it key_row order): conflict-free, one
+// 16-byte LDS store per strip instead of eight 2-byte transposed ones.  The read itself is tc_lds_tr8.
 __device__ __forceinline__ float fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
 
 // Forward.  ONE workgroup of FW_NW = 12 waves per CU; each wave owns a 32-query tile (the tiles are numbered through the four scales of
@@ -106,7 +97,7 @@ __global__ __launch_bounds__(FW_NT, 1) void attn_fwd_seg_kernel(const bf16_t* __
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks) qf[ks] = ld_frag<V8>(wtile + j * LDR + 16 * ks + 8 * h);
     }
-    f32x16 acc0, acc1;                                           // (qs = scale * log2(e), or 1 when Q arrives scaled)
+    tc_f32x16 acc0, acc1;                                           // (qs = scale * log2(e), or 1 when Q arrives scaled)
 #pragma unroll
     for (int r = 0; r < 16; ++r) { acc0[r] = 0.f; acc1[r] = 0.f; }
     float m = NEG_BIG, lsum = 0.f;
@@ -127,7 +118,7 @@ __global__ __launch_bounds__(FW_NT, 1) void attn_fwd_seg_kernel(const bf16_t* __
 #pragma unroll
         for (int i = 0; i < FW_NF; ++i) {
             const int id = tid + i * FW_NT, isv = id >= FW_NC, r = (id - isv * FW_NC) >> 3, c8 = (id & 7) * 8;
-            if (id < 2 * FW_NC) *reinterpret_cast<uint4*>(base + isv * (KB * LDR) + (isv ? key_row(r) : r) * LDR + c8) = st[i];
+            if (id < 2 * FW_NC) *reinterpret_cast<uint4*>(base + isv * (KB * LDR) + (isv ? tc_krow(r) : r) * LDR + c8) = st[i];
         }
     };
     const int nt = (Nk + KB - 1) / KB;
@@ -146,7 +137,7 @@ __global__ __launch_bounds__(FW_NT, 1) void attn_fwd_seg_kernel(const bf16_t* __
 #pragma unroll 1
         for (int sub = 0; sub < nsub; ++sub) {
             // S^T tile: 4 chained MFMAs
-            f32x16 s;
+            tc_f32x16 s;
 #pragma unroll
             for (int r = 0; r < 16; ++r) s[r] = 0.f;
             const bf16_t* kp = Ks + (32 * sub + krow) * LDR + 8 * h;
@@ -166,7 +157,7 @@ __global__ __launch_bounds__(FW_NT, 1) void attn_fwd_seg_kernel(const bf16_t* __
                 return ceilf(fmaxf(__uint_as_float(pr[0]), __uint_as_float(pr[1])) * qs);
             };
             if (kv0 == 0) m = rowmax();                         // the row's first sub-tile sets the reference exponent
-            f32x16 p;
+            tc_f32x16 p;
             float rs = 0.f;
 #pragma unroll
             for (int r = 0; r < 16; ++r) { p[r] = fast_exp2(fmaf(s[r], qs, -m)); rs += p[r]; }
@@ -188,8 +179,8 @@ __global__ __launch_bounds__(FW_NT, 1) void attn_fwd_seg_kernel(const bf16_t* __
 #pragma unroll
             for (int k2 = 0; k2 < 2; ++k2) {
                 const V8 pb = pack8<H>(p, 8 * k2);
-                acc0 = TcHalf<H>::mfma(ld_frag_tr<V8>(vp + (2 * k2) * LDR, vp + (2 * k2 + 1) * LDR), pb, acc0);
-                acc1 = TcHalf<H>::mfma(ld_frag_tr<V8>(vp + (2 * k2) * LDR + 32, vp + (2 * k2 + 1) * LDR + 32), pb, acc1);
+                acc0 = TcHalf<H>::mfma(tc_lds_tr8<V8>(vp + (2 * k2) * LDR, vp + (2 * k2 + 1) * LDR), pb, acc0);
+                acc1 = TcHalf<H>::mfma(tc_lds_tr8<V8>(vp + (2 * k2) * LDR + 32, vp + (2 * k2 + 1) * LDR + 32), pb, acc1);
             }
         }
         __syncthreads();
@@ -291,7 +282,7 @@ __global__ __launch_bounds__(AS_NW * 64, 1) void attn_fwd_asm_kernel(const bf16_
 #pragma unroll
         for (int s = 0; s < AS_AHEAD - 1; ++s) {                // sub-tiles 0..4 into ring slots 0..4 (rows past Nk: a duplicate, masked later)
             const uint4 x = *reinterpret_cast<const uint4*>(src + (long long)min(32 * s + sr, Nk - 1) * ld + 8 * sc);
-            *reinterpret_cast<uint4*>(as_smem + s * AS_SLOT + (role ? AS_VOFF + key_row(sr) * (LDR * 2) : sr * (LDR * 2)) + 16 * sc) = x;
+            *reinterpret_cast<uint4*>(as_smem + s * AS_SLOT + (role ? AS_VOFF + tc_krow(sr) * (LDR * 2) : sr * (LDR * 2)) + 16 * sc) = x;
         }
     }
     __syncthreads();
@@ -300,7 +291,7 @@ __global__ __launch_bounds__(AS_NW * 64, 1) void attn_fwd_asm_kernel(const bf16_
         const int gi = lane & 15, gq = (lane >> 4) & 1, nsub = (Nk + 31) / 32, nv = Nk - 32 * (nsub - 1);
         const unsigned kbase = lds0 + pi_row(j) * (LDR * 2) + 16 * h;
         const unsigned vbase = lds0 + AS_VOFF + (16 * h + 4 * (gi >> 2)) * (LDR * 2) + 32 * gq + 8 * (gi & 3);
-        const unsigned wbase = lds0 + (role == 1 ? AS_VOFF + key_row(sr) * (LDR * 2) : sr * (LDR * 2)) + 16 * sc;
+        const unsigned wbase = lds0 + (role == 1 ? AS_VOFF + tc_krow(sr) * (LDR * 2) : sr * (LDR * 2)) + 16 * sc;
         const int ld = role == 1 ? ldv : ldk;
         unsigned goff = (unsigned)(((32 * (AS_AHEAD - 1) + sr) * ld + 8 * sc) * 2);           // sub-tile 5 is the first one the stream loads
         const unsigned qaddr = lds0 + AS_WT0 + wave * AS_WT + j * (LDR * 2) + 16 * h, oaddr = qaddr - 8 * h;
@@ -341,8 +332,8 @@ __global__ __launch_bounds__(AS_NW * 64, 1) void attn_fwd_asm_kernel(const bf16_
 
 // dQ.  Same organisation as the forward kernel: one 12-wave workgroup per CU, a 32-query tile per wave, K/V tiles double-buffered in
 // LDS behind one barrier per tile, Q / dO / dQ tiles through the wave's LDS tile as whole 128-byte rows.
-// K is stored ONCE, rows in key_row order: conflict-free both for the 16-byte fragment reads of S^T = K Q^T (row
-// key_row(pi_row(j))) and for the transpose reads of dQ^T += K^T dS^T.
+// K is stored ONCE, rows in tc_krow order: conflict-free both for the 16-byte fragment reads of S^T = K Q^T (row
+// tc_krow(pi_row(j))) and for the transpose reads of dQ^T += K^T dS^T.
 // O != nullptr: delta = rowsum(O dO) of the wave's 32 rows is computed HERE from the dO rows the wave loads anyway (+ the O rows) and
 // written to `delta` for the dK/dV kernel, which is launched behind this one -- no separate delta pass over O and dO.
 // QM = 1 (Q stored as q * scale * log2(e)): -lse * log2(e) is the INITIAL value of the S accumulator (P = exp2(S) directly), dS is
@@ -436,10 +427,10 @@ __global__ __launch_bounds__(FW_NT, 1) void attn_bwd_dq_seg_kernel(const bf16_t*
         st[32 + j] = -dl0;
     }
     constexpr bool QSC = QM != 0;                               // QM bit 0: -l2 is the C operand of S; bit 1: -delta the C operand of dP
-    f32x16 acc0, acc1;
+    tc_f32x16 acc0, acc1;
 #pragma unroll
     for (int r = 0; r < 16; ++r) { acc0[r] = 0.f; acc1[r] = 0.f; }
-    const int krow = pi_row(j), kprow = key_row(krow);
+    const int krow = pi_row(j), kprow = tc_krow(krow);
     uint4 st[FW_NF];
     auto fetch = [&](int kb0) __attribute__((always_inline)) {
 #pragma unroll
@@ -455,7 +446,7 @@ __global__ __launch_bounds__(FW_NT, 1) void attn_bwd_dq_seg_kernel(const bf16_t*
 #pragma unroll
         for (int i = 0; i < FW_NF; ++i) {
             const int id = tid + i * FW_NT, isv = id >= FW_NC, r = (id - isv * FW_NC) >> 3, c8 = (id & 7) * 8;
-            if (id < 2 * FW_NC) *reinterpret_cast<uint4*>(base + isv * (KB * LDR) + (isv ? r : key_row(r)) * LDR + c8) = st[i];
+            if (id < 2 * FW_NC) *reinterpret_cast<uint4*>(base + isv * (KB * LDR) + (isv ? r : tc_krow(r)) * LDR + c8) = st[i];
         }
     };
     const int nt = (Nk + KB - 1) / KB;
@@ -476,7 +467,7 @@ __global__ __launch_bounds__(FW_NT, 1) void attn_bwd_dq_seg_kernel(const bf16_t*
 #pragma unroll 1
         for (int sub = 0; sub < nsub; ++sub) {
             const int kv0 = kb0 + 32 * sub;
-            f32x16 s, dp;
+            tc_f32x16 s, dp;
 #pragma unroll
             for (int r = 0; r < 16; ++r) { s[r] = (QM & 1) ? -l2 : 0.f; dp[r] = (QM & 2) ? -dl0 : 0.f; }
             const bf16_t* kp = Ks + (32 * sub + kprow) * LDR + 8 * h;
@@ -498,8 +489,8 @@ __global__ __launch_bounds__(FW_NT, 1) void attn_bwd_dq_seg_kernel(const bf16_t*
 #pragma unroll
             for (int k2 = 0; k2 < 2; ++k2) {
                 const V8 db = pack8<H>(s, 8 * k2);
-                acc0 = TcHalf<H>::mfma(ld_frag_tr<V8>(kt + (2 * k2) * LDR, kt + (2 * k2 + 1) * LDR), db, acc0);
-                acc1 = TcHalf<H>::mfma(ld_frag_tr<V8>(kt + (2 * k2) * LDR + 32, kt + (2 * k2 + 1) * LDR + 32), db, acc1);
+                acc0 = TcHalf<H>::mfma(tc_lds_tr8<V8>(kt + (2 * k2) * LDR, kt + (2 * k2 + 1) * LDR), db, acc0);
+                acc1 = TcHalf<H>::mfma(tc_lds_tr8<V8>(kt + (2 * k2) * LDR + 32, kt + (2 * k2 + 1) * LDR + 32), db, acc1);
             }
         }
         __syncthreads();
@@ -564,7 +555,7 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_bwd_dkv_seg_kernel(const bf16
                                                                     const float* __restrict__ delta, float* __restrict__ dkv32, Segs sg, int Nk,
                                                                     float scale, float qs, int tiles_per_chunk) {
     constexpr int QS = DKV_QS, NT = QS / 32, NI = QS * 8 / 256, LDQ = D + 8;
-    // Q and dO of a stage are stored ONCE, row-major with the rows of every 16-row group 4x4-transposed (key_row): conflict-free both
+    // Q and dO of a stage are stored ONCE, row-major with the rows of every 16-row group 4x4-transposed (tc_krow): conflict-free both
     // for the 16-byte fragment reads of S = Q K^T / dP = dO V^T and for the hardware transpose reads (ds_read_b64_tr_b16) that gather
     // the dO^T / Q^T operands of the dV^T / dK^T products -- the first version kept transposed copies written with 2-byte stores
     // two stage buffers: the next 64-query stage is stored (from registers loaded a stage earlier) while the current one is consumed,
@@ -589,7 +580,7 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_bwd_dkv_seg_kernel(const bf16
     }
     // qs = scale * log2(e) and dS = P (dP - delta) scale multiplies the UNSCALED Q into dK; with Q stored as q * qs (qs passed as 1)
     // the factor of dS is ln 2 = scale / (scale * log2(e)) instead (`scale` is passed as ln 2 by the host in that case)
-    f32x16 dk0, dk1, dv0, dv1;
+    tc_f32x16 dk0, dk1, dv0, dv1;
 #pragma unroll
     for (int r = 0; r < 16; ++r) { dk0[r] = dk1[r] = dv0[r] = dv1[r] = 0.f; }
     const int qrow = pi_row(j);
@@ -640,8 +631,8 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_bwd_dkv_seg_kernel(const bf16
 #pragma unroll
             for (int i = 0; i < NI; ++i) {
                 int r, c8, g; fmap(i, r, c8, g);
-                *reinterpret_cast<uint4*>(&Qw[key_row(r) * LDQ + c8]) = qr[i];
-                *reinterpret_cast<uint4*>(&dOw[key_row(r) * LDQ + c8]) = gr[i];
+                *reinterpret_cast<uint4*>(&Qw[tc_krow(r) * LDQ + c8]) = qr[i];
+                *reinterpret_cast<uint4*>(&dOw[tc_krow(r) * LDQ + c8]) = gr[i];
             }
         }
         if (tid < QS) { lw[tid] = lr; lw[QS + tid] = dr; }
@@ -663,7 +654,7 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_bwd_dkv_seg_kernel(const bf16
         const float* dls = lss + QS;
         // S / dP of 32-query tile qt + 1 are issued BEFORE the exp2 / multiply / pack / dV^T / dK^T work of tile qt (DKV_PIPE, within a
         // stage): two waves per SIMD do not cover each other's dependent chains, the wave's own next tile does
-        auto sdp = [&](int qt, f32x16& s, f32x16& dp, f32x16& lq, f32x16& dq) __attribute__((always_inline)) {
+        auto sdp = [&](int qt, tc_f32x16& s, tc_f32x16& dp, tc_f32x16& lq, tc_f32x16& dq) __attribute__((always_inline)) {
             // the 16 log-sum-exps and (scaled) deltas of this lane's query rows: four 16-byte LDS reads each instead of 16 scalar ones
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
@@ -677,15 +668,15 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_bwd_dkv_seg_kernel(const bf16
 #pragma unroll
                 for (int r = 0; r < 16; ++r) { s[r] = 0.f; dp[r] = 0.f; }
             }
-            const bf16_t* qp = Qs + (32 * qt + key_row(qrow)) * LDQ + 8 * h;
-            const bf16_t* gp = dOs + (32 * qt + key_row(qrow)) * LDQ + 8 * h;
+            const bf16_t* qp = Qs + (32 * qt + tc_krow(qrow)) * LDQ + 8 * h;
+            const bf16_t* gp = dOs + (32 * qt + tc_krow(qrow)) * LDQ + 8 * h;
 #pragma unroll
             for (int ks = 0; ks < 4; ++ks) {
                 s = TcHalf<H>::mfma(ld_frag<V8>(qp + 16 * ks), kf[ks], s);
                 dp = TcHalf<H>::mfma(ld_frag<V8>(gp + 16 * ks), vf[ks], dp);
             }
         };
-        auto fold = [&](int qt, f32x16& s, f32x16& dp, const f32x16& lq, const f32x16& dq) __attribute__((always_inline)) {
+        auto fold = [&](int qt, tc_f32x16& s, tc_f32x16& dp, const tc_f32x16& lq, const tc_f32x16& dq) __attribute__((always_inline)) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 if (QSC) {
@@ -704,14 +695,14 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_bwd_dkv_seg_kernel(const bf16
 #pragma unroll
             for (int k2 = 0; k2 < 2; ++k2) {
                 const V8 pb = pack8<H>(s, 8 * k2), db = pack8<H>(dp, 8 * k2);
-                dv0 = TcHalf<H>::mfma(ld_frag_tr<V8>(gt + (2 * k2) * LDQ, gt + (2 * k2 + 1) * LDQ), pb, dv0);
-                dv1 = TcHalf<H>::mfma(ld_frag_tr<V8>(gt + (2 * k2) * LDQ + 32, gt + (2 * k2 + 1) * LDQ + 32), pb, dv1);
-                dk0 = TcHalf<H>::mfma(ld_frag_tr<V8>(qtp + (2 * k2) * LDQ, qtp + (2 * k2 + 1) * LDQ), db, dk0);
-                dk1 = TcHalf<H>::mfma(ld_frag_tr<V8>(qtp + (2 * k2) * LDQ + 32, qtp + (2 * k2 + 1) * LDQ + 32), db, dk1);
+                dv0 = TcHalf<H>::mfma(tc_lds_tr8<V8>(gt + (2 * k2) * LDQ, gt + (2 * k2 + 1) * LDQ), pb, dv0);
+                dv1 = TcHalf<H>::mfma(tc_lds_tr8<V8>(gt + (2 * k2) * LDQ + 32, gt + (2 * k2 + 1) * LDQ + 32), pb, dv1);
+                dk0 = TcHalf<H>::mfma(tc_lds_tr8<V8>(qtp + (2 * k2) * LDQ, qtp + (2 * k2 + 1) * LDQ), db, dk0);
+                dk1 = TcHalf<H>::mfma(tc_lds_tr8<V8>(qtp + (2 * k2) * LDQ + 32, qtp + (2 * k2 + 1) * LDQ + 32), db, dk1);
             }
         };
 #if DKV_PIPE
-        f32x16 sv[2], dpv[2], lqv[2], dqv[2];
+        tc_f32x16 sv[2], dpv[2], lqv[2], dqv[2];
         sdp(0, sv[0], dpv[0], lqv[0], dqv[0]);
 #pragma unroll
         for (int qt = 0; qt < NT; ++qt) {
@@ -721,7 +712,7 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_bwd_dkv_seg_kernel(const bf16
 #else
 #pragma unroll
         for (int qt = 0; qt < NT; ++qt) {
-            f32x16 s, dp, lq, dq;
+            tc_f32x16 s, dp, lq, dq;
             sdp(qt, s, dp, lq, dq);
             fold(qt, s, dp, lq, dq);
         }
@@ -754,7 +745,7 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_bwd_dkv_seg_kernel(const bf16
 }
 
 // dQ, hand-scheduled (gen_dq_asm.py; Q stored scaled, 16-byte addressable rows, at least two key sub-tiles): the forward stream's workgroup
-// and ring (attn_fwd_asm_kernel), K rows in key_row order and V rows in natural order.  This function computes the row deltas (and the
+// and ring (attn_fwd_asm_kernel), K rows in tc_krow order and V rows in natural order.  This function computes the row deltas (and the
 // per-tile statistics of the dK/dV stream), stages sub-tiles 0..4, runs the stream and stores the dQ tile it leaves in the wave's LDS tile.
 #include "attn_dq_asm.inc"
 template <typename H>
@@ -818,17 +809,17 @@ __global__ __launch_bounds__(AS_NW * 64, 1) void attn_bwd_dq_asm_kernel(const bf
 #pragma unroll
         for (int s = 0; s < AS_AHEAD - 1; ++s) {                // sub-tiles 0..4 into ring slots 0..4 (rows past Nk: a duplicate, masked by the stream)
             const uint4 x = *reinterpret_cast<const uint4*>(src + (long long)min(32 * s + sr, Nk - 1) * ld + 8 * sc);
-            *reinterpret_cast<uint4*>(as_smem + s * AS_SLOT + (role ? AS_VOFF + sr * (LDR * 2) : key_row(sr) * (LDR * 2)) + 16 * sc) = x;
+            *reinterpret_cast<uint4*>(as_smem + s * AS_SLOT + (role ? AS_VOFF + sr * (LDR * 2) : tc_krow(sr) * (LDR * 2)) + 16 * sc) = x;
         }
     }
     __syncthreads();
     {
         const unsigned lds0 = (unsigned)(uintptr_t)as_smem;
         const int gi = lane & 15, gq = (lane >> 4) & 1, nsub = (Nk + 31) / 32, nv = Nk - 32 * (nsub - 1);
-        const unsigned kbase = lds0 + key_row(pi_row(j)) * (LDR * 2) + 16 * h;
+        const unsigned kbase = lds0 + tc_krow(pi_row(j)) * (LDR * 2) + 16 * h;
         const unsigned vbase = lds0 + AS_VOFF + pi_row(j) * (LDR * 2) + 16 * h;
         const unsigned tbase = lds0 + (16 * h + 4 * (gi >> 2)) * (LDR * 2) + 32 * gq + 8 * (gi & 3);
-        const unsigned wbase = lds0 + (role == 1 ? AS_VOFF + sr * (LDR * 2) : key_row(sr) * (LDR * 2)) + 16 * sc;
+        const unsigned wbase = lds0 + (role == 1 ? AS_VOFF + sr * (LDR * 2) : tc_krow(sr) * (LDR * 2)) + 16 * sc;
         const int ld = role == 1 ? ldv : ldk;
         unsigned goff = (unsigned)(((32 * (AS_AHEAD - 1) + sr) * ld + 8 * sc) * 2);
         const long long qrow = live ? trow0 + min(j, max(0, min(32, nq - tq0) - 1)) : 0;     // rows past the tile's end: a valid row whose column is never stored
@@ -914,8 +905,8 @@ __global__ __launch_bounds__(256 * PAIR, 3 - PAIR) void attn_bwd_dkv_asm_kernel(
         const uint4 qv = in ? *reinterpret_cast<const uint4*>(Q + row * ldq + 8 * sc) : make_uint4(0u, 0u, 0u, 0u);
         const uint4 gv = in ? *reinterpret_cast<const uint4*>(dO + row * lddo + 8 * sc) : make_uint4(0u, 0u, 0u, 0u);
         unsigned char* slot = da_smem + s * DA_SLOT;
-        *reinterpret_cast<uint4*>(slot + key_row(sr) * (LDR * 2) + 16 * sc) = qv;
-        *reinterpret_cast<uint4*>(slot + DA_TILE + key_row(sr) * (LDR * 2) + 16 * sc) = gv;
+        *reinterpret_cast<uint4*>(slot + tc_krow(sr) * (LDR * 2) + 16 * sc) = qv;
+        *reinterpret_cast<uint4*>(slot + DA_TILE + tc_krow(sr) * (LDR * 2) + 16 * sc) = gv;
         if (tid < 16) {
             uint4 sv = t < ntiles ? *reinterpret_cast<const uint4*>(nstat + ((long long)b * ntiles + t) * 64 + 4 * tid) : make_uint4(0u, 0u, 0u, 0u);
             if (s < t_mask) {                                    // [-lse log2e x 32 | -delta x 32] of a tile that counts for nothing
@@ -950,8 +941,8 @@ __global__ __launch_bounds__(256 * PAIR, 3 - PAIR) void attn_bwd_dkv_asm_kernel(
         const unsigned lds0 = (unsigned)(uintptr_t)da_smem;
         const int gi = lane & 15, gq = (lane >> 4) & 1;
         const unsigned vq = (unsigned)((sr * ldq + 8 * sc) * 2), vg = (unsigned)((sr * lddo + 8 * sc) * 2), vs = (unsigned)(16 * (tid & 15));
-        const unsigned wq = lds0 + key_row(sr) * (LDR * 2) + 16 * sc, ws = lds0 + 2 * DA_TILE + 16 * (tid & 15);
-        const unsigned rb = lds0 + key_row(pi_row(j)) * (LDR * 2) + 16 * h;
+        const unsigned wq = lds0 + tc_krow(sr) * (LDR * 2) + 16 * sc, ws = lds0 + 2 * DA_TILE + 16 * (tid & 15);
+        const unsigned rb = lds0 + tc_krow(pi_row(j)) * (LDR * 2) + 16 * h;
         const unsigned tb = lds0 + (16 * h + 4 * (gi >> 2)) * (LDR * 2) + 32 * gq + 8 * (gi & 3);
 #ifdef TC_DKV_B128STATS
         const unsigned sb = lds0 + 2 * DA_TILE + 64 * h;

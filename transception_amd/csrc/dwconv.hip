@@ -182,21 +182,17 @@ __global__ __launch_bounds__(256) void dw_wgrad3_kernel(const T* __restrict__ dy
 // the K x K input window held in registers (K new loads per output instead of K*K; column slots rotate at compile time).
 //   MODE 0: y = conv(x) (+bias) (+x)          MODE 1: dx = conv^T(dy) (+dy)  [same walk with flipped taps]
 //   MODE 2: dw[c,ky,kx] += sum dy * x ;  db[c] += sum dy   (block-level LDS reduction, then one atomic per block and tap)
-template <typename T, int CPT> __device__ __forceinline__ void ldv(const T* p, float* o);
-template <> __device__ __forceinline__ void ldv<float, 4>(const float* p, float* o) { const float4 v = *reinterpret_cast<const float4*>(p); o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = v.w; }
-template <> __device__ __forceinline__ void ldv<float, 2>(const float* p, float* o) { const float2 v = *reinterpret_cast<const float2*>(p); o[0] = v.x; o[1] = v.y; }
-template <> __device__ __forceinline__ void ldv<bf16_t, 4>(const bf16_t* p, float* o) { const float4 v = ld4<bf16_t>(p); o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = v.w; }
-template <> __device__ __forceinline__ void ldv<bf16_t, 2>(const bf16_t* p, float* o) { const unsigned r = *reinterpret_cast<const unsigned*>(p); o[0] = __uint_as_float(r << 16); o[1] = __uint_as_float(r & 0xffff0000u); }
-template <> __device__ __forceinline__ void ldv<f16_t, 4>(const f16_t* p, float* o) { const float4 v = ld4<f16_t>(p); o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = v.w; }
-template <> __device__ __forceinline__ void ldv<f16_t, 2>(const f16_t* p, float* o) { unpack2<f16_t>(*reinterpret_cast<const unsigned*>(p), o[0], o[1]); }
-template <typename T, int CPT> __device__ __forceinline__ void stv(T* p, const float* o);
-template <> __device__ __forceinline__ void stv<float, 4>(float* p, const float* o) { *reinterpret_cast<float4*>(p) = make_float4(o[0], o[1], o[2], o[3]); }
-template <> __device__ __forceinline__ void stv<float, 2>(float* p, const float* o) { *reinterpret_cast<float2*>(p) = make_float2(o[0], o[1]); }
-template <> __device__ __forceinline__ void stv<bf16_t, 4>(bf16_t* p, const float* o) { st4<bf16_t>(p, make_float4(o[0], o[1], o[2], o[3])); }
-template <> __device__ __forceinline__ void stv<bf16_t, 2>(bf16_t* p, const float* o) { *reinterpret_cast<unsigned*>(p) = pack2bf(o[0], o[1]); }
-
-template <> __device__ __forceinline__ void stv<f16_t, 4>(f16_t* p, const float* o) { st4<f16_t>(p, make_float4(o[0], o[1], o[2], o[3])); }
-template <> __device__ __forceinline__ void stv<f16_t, 2>(f16_t* p, const float* o) { *reinterpret_cast<unsigned*>(p) = pack2h(o[0], o[1]); }
+// CPT = 4 or 2 consecutive channels of a thread, as floats
+template <typename T, int CPT> __device__ __forceinline__ void ldv(const T* p, float* o) {
+    if constexpr (CPT == 4) { const float4 v = ld4<T>(p); o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = v.w; }
+    else if constexpr (std::is_same<T, float>::value) { const float2 v = *reinterpret_cast<const float2*>(p); o[0] = v.x; o[1] = v.y; }
+    else unpack2<T>(*reinterpret_cast<const unsigned*>(p), o[0], o[1]);
+}
+template <typename T, int CPT> __device__ __forceinline__ void stv(T* p, const float* o) {
+    if constexpr (CPT == 4) st4<T>(p, make_float4(o[0], o[1], o[2], o[3]));
+    else if constexpr (std::is_same<T, float>::value) *reinterpret_cast<float2*>(p) = make_float2(o[0], o[1]);
+    else *reinterpret_cast<unsigned*>(p) = pack2<T>(o[0], o[1]);
+}
 
 template <typename T, int K, int CPT, int MODE>
 __global__ __launch_bounds__(256) void dw_strip_kernel(const T* __restrict__ x, int ldx, const T* __restrict__ w, const T* __restrict__ bias,
@@ -369,93 +365,6 @@ int launch_strip(const void* x, int ldx, const void* w, const void* bias, const 
 // every thread then produces a run of 4 horizontally adjacent pixels for its VEC channels from LDS.
 //   VEC = channels per 16 bytes (8 bf16 / 4 fp32); CG = 16-byte lanes per pixel (8/4/2: 64/32/16 bf16 channels per workgroup,
 //   picked on the host to waste the fewest lanes on the 16/24/48/80/120-channel maps of the multi-branch stages).
-template <typename T> struct Vec16;
-template <> struct Vec16<float> { static constexpr int N = 4; };
-template <> struct Vec16<bf16_t> { static constexpr int N = 8; };
-template <> struct Vec16<f16_t> { static constexpr int N = 8; };
-template <typename T> __device__ __forceinline__ void unpack16(const uint4& r, float* o);
-template <> __device__ __forceinline__ void unpack16<float>(const uint4& r, float* o) {
-    o[0] = __uint_as_float(r.x); o[1] = __uint_as_float(r.y); o[2] = __uint_as_float(r.z); o[3] = __uint_as_float(r.w);
-}
-template <> __device__ __forceinline__ void unpack16<bf16_t>(const uint4& r, float* o) {
-    o[0] = __uint_as_float(r.x << 16); o[1] = __uint_as_float(r.x & 0xffff0000u);
-    o[2] = __uint_as_float(r.y << 16); o[3] = __uint_as_float(r.y & 0xffff0000u);
-    o[4] = __uint_as_float(r.z << 16); o[5] = __uint_as_float(r.z & 0xffff0000u);
-    o[6] = __uint_as_float(r.w << 16); o[7] = __uint_as_float(r.w & 0xffff0000u);
-}
-template <> __device__ __forceinline__ void unpack16<f16_t>(const uint4& r, float* o) {
-    unpack2<f16_t>(r.x, o[0], o[1]); unpack2<f16_t>(r.y, o[2], o[3]); unpack2<f16_t>(r.z, o[4], o[5]); unpack2<f16_t>(r.w, o[6], o[7]);
-}
-template <typename T> __device__ __forceinline__ uint4 pack16(const float* o);
-template <> __device__ __forceinline__ uint4 pack16<float>(const float* o) {
-    return make_uint4(__float_as_uint(o[0]), __float_as_uint(o[1]), __float_as_uint(o[2]), __float_as_uint(o[3]));
-}
-template <> __device__ __forceinline__ uint4 pack16<bf16_t>(const float* o) {
-    return make_uint4(pack2bf(o[0], o[1]), pack2bf(o[2], o[3]), pack2bf(o[4], o[5]), pack2bf(o[6], o[7]));
-}
-
-template <> __device__ __forceinline__ uint4 pack16<f16_t>(const float* o) {
-    return make_uint4(pack2h(o[0], o[1]), pack2h(o[2], o[3]), pack2h(o[4], o[5]), pack2h(o[6], o[7]));
-}
-// the same vectors as pairs for the packed fp32 pipe (v_pk_fma_f32: two multiply-adds per issue slot)
-template <typename T> __device__ __forceinline__ void unpack16v(const uint4& r, tc_f32x2* o);
-template <> __device__ __forceinline__ void unpack16v<float>(const uint4& r, tc_f32x2* o) {
-    o[0] = tc_f32x2{__uint_as_float(r.x), __uint_as_float(r.y)}; o[1] = tc_f32x2{__uint_as_float(r.z), __uint_as_float(r.w)};
-}
-template <> __device__ __forceinline__ void unpack16v<bf16_t>(const uint4& r, tc_f32x2* o) {
-    o[0] = tc_f32x2{__uint_as_float(r.x << 16), __uint_as_float(r.x & 0xffff0000u)};
-    o[1] = tc_f32x2{__uint_as_float(r.y << 16), __uint_as_float(r.y & 0xffff0000u)};
-    o[2] = tc_f32x2{__uint_as_float(r.z << 16), __uint_as_float(r.z & 0xffff0000u)};
-    o[3] = tc_f32x2{__uint_as_float(r.w << 16), __uint_as_float(r.w & 0xffff0000u)};
-}
-template <> __device__ __forceinline__ void unpack16v<f16_t>(const uint4& r, tc_f32x2* o) {
-    float a, b;
-    unpack2<f16_t>(r.x, a, b); o[0] = tc_f32x2{a, b};
-    unpack2<f16_t>(r.y, a, b); o[1] = tc_f32x2{a, b};
-    unpack2<f16_t>(r.z, a, b); o[2] = tc_f32x2{a, b};
-    unpack2<f16_t>(r.w, a, b); o[3] = tc_f32x2{a, b};
-}
-template <typename T> __device__ __forceinline__ uint4 pack16v(const tc_f32x2* o);
-template <> __device__ __forceinline__ uint4 pack16v<float>(const tc_f32x2* o) {
-    return make_uint4(__float_as_uint(o[0].x), __float_as_uint(o[0].y), __float_as_uint(o[1].x), __float_as_uint(o[1].y));
-}
-template <> __device__ __forceinline__ uint4 pack16v<bf16_t>(const tc_f32x2* o) {
-    return make_uint4(pack2bf(o[0].x, o[0].y), pack2bf(o[1].x, o[1].y), pack2bf(o[2].x, o[2].y), pack2bf(o[3].x, o[3].y));
-}
-
-template <> __device__ __forceinline__ uint4 pack16v<f16_t>(const tc_f32x2* o) {
-    return make_uint4(pack2h(o[0].x, o[0].y), pack2h(o[1].x, o[1].y), pack2h(o[2].x, o[2].y), pack2h(o[3].x, o[3].y));
-}
-
-// SV consecutive channels (a whole 16-byte vector or half of one) from LDS / to global memory, as packed pairs
-template <typename T, int SV> __device__ __forceinline__ void unpack_sv(const void* p, tc_f32x2* o);
-template <> __device__ __forceinline__ void unpack_sv<float, 4>(const void* p, tc_f32x2* o) { unpack16v<float>(*reinterpret_cast<const uint4*>(p), o); }
-template <> __device__ __forceinline__ void unpack_sv<float, 2>(const void* p, tc_f32x2* o) { const float2 v = *reinterpret_cast<const float2*>(p); o[0] = tc_f32x2{v.x, v.y}; }
-template <> __device__ __forceinline__ void unpack_sv<bf16_t, 8>(const void* p, tc_f32x2* o) { unpack16v<bf16_t>(*reinterpret_cast<const uint4*>(p), o); }
-template <> __device__ __forceinline__ void unpack_sv<bf16_t, 4>(const void* p, tc_f32x2* o) {
-    const uint2 r = *reinterpret_cast<const uint2*>(p);
-    o[0] = tc_f32x2{__uint_as_float(r.x << 16), __uint_as_float(r.x & 0xffff0000u)};
-    o[1] = tc_f32x2{__uint_as_float(r.y << 16), __uint_as_float(r.y & 0xffff0000u)};
-}
-template <> __device__ __forceinline__ void unpack_sv<f16_t, 8>(const void* p, tc_f32x2* o) { unpack16v<f16_t>(*reinterpret_cast<const uint4*>(p), o); }
-template <> __device__ __forceinline__ void unpack_sv<f16_t, 4>(const void* p, tc_f32x2* o) {
-    const uint2 r = *reinterpret_cast<const uint2*>(p);
-    float a, b;
-    unpack2<f16_t>(r.x, a, b); o[0] = tc_f32x2{a, b};
-    unpack2<f16_t>(r.y, a, b); o[1] = tc_f32x2{a, b};
-}
-template <typename T, int SV> __device__ __forceinline__ void store_sv(T* p, const tc_f32x2* o);
-template <> __device__ __forceinline__ void store_sv<float, 4>(float* p, const tc_f32x2* o) { *reinterpret_cast<uint4*>(p) = pack16v<float>(o); }
-template <> __device__ __forceinline__ void store_sv<float, 2>(float* p, const tc_f32x2* o) { *reinterpret_cast<float2*>(p) = make_float2(o[0].x, o[0].y); }
-template <> __device__ __forceinline__ void store_sv<bf16_t, 8>(bf16_t* p, const tc_f32x2* o) { *reinterpret_cast<uint4*>(p) = pack16v<bf16_t>(o); }
-template <> __device__ __forceinline__ void store_sv<bf16_t, 4>(bf16_t* p, const tc_f32x2* o) {
-    *reinterpret_cast<uint2*>(p) = make_uint2(pack2bf(o[0].x, o[0].y), pack2bf(o[1].x, o[1].y));
-}
-template <> __device__ __forceinline__ void store_sv<f16_t, 8>(f16_t* p, const tc_f32x2* o) { *reinterpret_cast<uint4*>(p) = pack16v<f16_t>(o); }
-template <> __device__ __forceinline__ void store_sv<f16_t, 4>(f16_t* p, const tc_f32x2* o) {
-    *reinterpret_cast<uint2*>(p) = make_uint2(pack2h(o[0].x, o[0].y), pack2h(o[1].x, o[1].y));
-}
-
 template <int K, int CG> struct DwTile {
     static constexpr int PT = 256 / CG, R = 4, TW = 16, TH = PT / (TW / R), P = (K - 1) / 2;
     static constexpr int IW = TW + K - 1, IH = TH + K - 1;
@@ -467,7 +376,7 @@ template <int K, int CG> struct DwTile {
 // fill becomes a chain of memory round trips.
 template <typename T, int CG>
 __device__ __forceinline__ bool dw_inside(int v, int h0, int w0, int NH, int NW, int H, int W, int crem, int& off_pix, int& cgi) {
-    constexpr int VEC = Vec16<T>::N;
+    constexpr int VEC = TcVec16<T>::N;
     cgi = v % CG;
     const int pix = v / CG, ix = pix % NW, iy = pix / NW;
     const int ih = h0 + iy, iw = w0 + ix;
@@ -476,7 +385,7 @@ __device__ __forceinline__ bool dw_inside(int v, int h0, int w0, int NH, int NW,
 }
 template <typename T, int CG, int NREG, int NTH = 256>
 __device__ __forceinline__ void dw_fetch(uint4 (&reg)[NREG], const T* img, int ld, int h0, int w0, int NH, int NW, int H, int W, int crem) {
-    constexpr int VEC = Vec16<T>::N;
+    constexpr int VEC = TcVec16<T>::N;
 #pragma unroll
     for (int i = 0; i < NREG; ++i) {
         int op, cgi;
@@ -508,11 +417,11 @@ __device__ __forceinline__ void dw_stage(uint4* tile, const T* img, int ld, int 
 
 // LDS needs of the tile bodies, in uint4 (the multi-segment launches size one dynamic buffer for the largest body they contain)
 template <typename T, int K, int CG> constexpr int dw_tile_smem_q() {
-    return DwTile<K, CG>::IH * DwTile<K, CG>::IW * (CG + (CG == 8 ? 2 : 1)) + (K * K * CG * Vec16<T>::N + 3) / 4;
+    return DwTile<K, CG>::IH * DwTile<K, CG>::IW * (CG + (CG == 8 ? 2 : 1)) + (K * K * CG * TcVec16<T>::N + 3) / 4;
 }
 template <typename T, int K, int CG> constexpr int dw_wgrad_smem_q() {
     return DwTile<K, CG>::IH * DwTile<K, CG>::IW * (CG + 1) + DwTile<K, CG>::TH * DwTile<K, CG>::TW * (CG + 1) +
-           ((K * K + 1) * CG * Vec16<T>::N + 3) / 4;
+           ((K * K + 1) * CG * TcVec16<T>::N + 3) / 4;
 }
 
 // body of one workgroup (bx = tile, by = channel chunk, bz = weight group); `smem` holds dw_tile_smem_q() uint4
@@ -527,7 +436,7 @@ __device__ __forceinline__ void dw_tile_body(const T* __restrict__ src, int lds_
                                              int tilesH, const int bx, const int by, const int bz, uint4* smem,
                                              float* __restrict__ stat = nullptr, int nchunks = 0) {
     using D = DwTile<K, CG>;
-    constexpr int VEC = Vec16<T>::N, CH = CG * VEC, R = D::R, P = D::P;
+    constexpr int VEC = TcVec16<T>::N, CH = CG * VEC, R = D::R, P = D::P;
     constexpr int PIXQ = CG + (CG == 8 ? 2 : 1);
     uint4* tile = smem;
     float (*wsm)[CH] = reinterpret_cast<float (*)[CH]>(smem + D::IH * D::IW * PIXQ);
@@ -573,7 +482,7 @@ __device__ __forceinline__ void dw_tile_body(const T* __restrict__ src, int lds_
     for (int ky = 0; ky < K; ++ky) {
         float in[R + K - 1][VEC];
 #pragma unroll
-        for (int i = 0; i < R + K - 1; ++i) unpack16<T>(tile[((row + ky) * D::IW + run * R + i) * PIXQ + cg], in[i]);
+        for (int i = 0; i < R + K - 1; ++i) tc_unpack16<T>(tile[((row + ky) * D::IW + run * R + i) * PIXQ + cg], in[i]);
 #pragma unroll
         for (int kx = 0; kx < K; ++kx) {
             float wr[VEC];
@@ -627,14 +536,14 @@ __device__ __forceinline__ void dw_tile_body(const T* __restrict__ src, int lds_
 #pragma unroll
         for (int r = 0; r < R; ++r) {
             float q[VEC];
-            unpack16<T>(old[r], q);
+            tc_unpack16<T>(old[r], q);
 #pragma unroll
             for (int e = 0; e < VEC; ++e) acc[r][e] += q[e];
         }
     }
 #pragma unroll
     for (int r = 0; r < R; ++r)
-        if (owb + r < W) *reinterpret_cast<uint4*>(dst0 + (long long)r * ldy) = pack16<T>(acc[r]);
+        if (owb + r < W) *reinterpret_cast<uint4*>(dst0 + (long long)r * ldy) = tc_pack16<T>(acc[r]);
 }
 
 // One workgroup per tile: tile indices l, l + 8, ... run on one XCD (whatever the grid offset of the chunk / group), so each XCD takes
@@ -751,7 +660,7 @@ __device__ __forceinline__ void dw_tile_wgrad_body(const T* __restrict__ x, int 
                                                    int* __restrict__ ws_cnt, const int bx, const int by, const int bz, const int gx,
                                                    const int gy, uint4* smem) {
     using D = DwTile<K, CG>;
-    constexpr int VEC = Vec16<T>::N, CH = CG * VEC, R = D::R, P = D::P, PIXQ = CG + 1, NT = K * K + 1;
+    constexpr int VEC = TcVec16<T>::N, CH = CG * VEC, R = D::R, P = D::P, PIXQ = CG + 1, NT = K * K + 1;
     constexpr int RG = D::PT / K, UNITS = D::TH * (D::TW / R);
     uint4* xt = smem;
     uint4* dt = xt + D::IH * D::IW * PIXQ;
@@ -809,9 +718,9 @@ __device__ __forceinline__ void dw_tile_wgrad_body(const T* __restrict__ x, int 
                 const int row = u / (D::TW / R), run = u % (D::TW / R);
                 float d[R][VEC], in[R + K - 1][VEC];
 #pragma unroll
-                for (int r = 0; r < R; ++r) unpack16<T>(dt[(row * D::TW + run * R + r) * PIXQ + cg], d[r]);
+                for (int r = 0; r < R; ++r) tc_unpack16<T>(dt[(row * D::TW + run * R + r) * PIXQ + cg], d[r]);
 #pragma unroll
-                for (int i = 0; i < R + K - 1; ++i) unpack16<T>(xt[((row + ky) * D::IW + run * R + i) * PIXQ + cg], in[i]);
+                for (int i = 0; i < R + K - 1; ++i) tc_unpack16<T>(xt[((row + ky) * D::IW + run * R + i) * PIXQ + cg], in[i]);
 #pragma unroll
                 for (int kx = 0; kx < K; ++kx)
 #pragma unroll
@@ -895,7 +804,7 @@ __global__ __launch_bounds__(256) void dw_tile_bwd_kernel(const T* __restrict__ 
 
 // 16-byte lanes per pixel that waste the fewest channels (ties: the widest)
 template <typename T> int dw_pick_cg(int C) {
-    constexpr int VEC = Vec16<T>::N;
+    constexpr int VEC = TcVec16<T>::N;
     int best = 8, waste = (C + 8 * VEC - 1) / (8 * VEC) * (8 * VEC) - C;
     for (int cg = 4; cg >= 2; cg >>= 1) {
         const int wst = (C + cg * VEC - 1) / (cg * VEC) * (cg * VEC) - C;
@@ -904,7 +813,7 @@ template <typename T> int dw_pick_cg(int C) {
     return best;
 }
 template <typename T> bool dw_tile_ok(const void* a, int lda, const void* b, int ldb, int C) {
-    constexpr int VEC = Vec16<T>::N;
+    constexpr int VEC = TcVec16<T>::N;
     return C % VEC == 0 && lda % VEC == 0 && ldb % VEC == 0 && (uintptr_t)a % 16 == 0 && (uintptr_t)b % 16 == 0;
 }
 
@@ -920,7 +829,7 @@ inline TileGeom tile_geom(int B, int H, int W, int C, int cg, int vec) {
     t.ntiles = (long long)B * t.tilesW * t.tilesH;
     return t;
 }
-template <typename T> TileGeom dw_tile_geom(int B, int H, int W, int C) { return tile_geom(B, H, W, C, dw_pick_cg<T>(C), Vec16<T>::N); }
+template <typename T> TileGeom dw_tile_geom(int B, int H, int W, int C) { return tile_geom(B, H, W, C, dw_pick_cg<T>(C), TcVec16<T>::N); }
 
 // Walker layout of a launch's weight-gradient sums.  Segment i runs gx walkers per (group, channel chunk); each leaves nt x ch floats at
 // [group * chunks + chunk][walker][tap][channel], from float part0 of the launch's buffer on, and (tail fold only) every DW_FOLD walkers share
@@ -1202,7 +1111,7 @@ constexpr int FFN_MULTI_MAX = WALK_SEGS;
 struct FfnMultiDev { FfnSegDev s[FFN_MULTI_MAX]; int n; int dbg_nofold; long long wstride; };
 
 template <typename T> struct FfnTile {
-    static constexpr int K = 3, CG = 8, VEC = Vec16<T>::N, CH = CG * VEC, R = 4, TW = 16, TH = 8, P = 1, IW = TW + 2, IH = TH + 2;
+    static constexpr int K = 3, CG = 8, VEC = TcVec16<T>::N, CH = CG * VEC, R = 4, TW = 16, TH = 8, P = 1, IW = TW + 2, IH = TH + 2;
     static constexpr int PIXQ = CG + 1, NT = K * K + 3;            // taps, conv bias, dgamma, dbeta
     static constexpr int smem_q = 2 * IH * IW * PIXQ + IH * IW + (K * K * CH + CH + NT * CH + 3) / 4;
 };
@@ -1351,8 +1260,8 @@ __device__ __forceinline__ void ffn_mid_bwd_body(const FfnSegDev& a, long long w
                 const int pix = v / CG, iy = pix / IW, ix = pix - iy * IW;
                 const float4 st = pst[pix];
                 tc_f32x2 g8[V2], d8[V2], o8[V2];
-                unpack16v<T>(gr[i], g8);
-                unpack16v<T>(dr[i], d8);
+                tc_unpack16v<T>(gr[i], g8);
+                tc_unpack16v<T>(dr[i], d8);
                 const bool inner = ok && iy >= 1 && iy <= D::TH && ix >= 1 && ix <= D::TW;
                 const float rs = ok ? st.y : 0.f, wi = inner ? 1.0f : 0.f;
 #pragma unroll
@@ -1363,7 +1272,7 @@ __device__ __forceinline__ void ffn_mid_bwd_body(const FfnSegDev& a, long long w
                     const tc_f32x2 gi = g8[e] * wi;
                     accg[e] += gi * xh; accbt[e] += gi;
                 }
-                ddt[pix * PIXQ + cgi] = pack16v<T>(o8);
+                ddt[pix * PIXQ + cgi] = tc_pack16v<T>(o8);
                 ht[pix * PIXQ + cgi] = ok ? hr[i] : make_uint4(0u, 0u, 0u, 0u);
             }
         }
@@ -1384,7 +1293,7 @@ __device__ __forceinline__ void ffn_mid_bwd_body(const FfnSegDev& a, long long w
                     tc_f32x2 in[R + K - 1][S2];
 #pragma unroll
                     for (int i = 0; i < R + K - 1; ++i)
-                        unpack_sv<T, SV>(ddb + (((row + ky) * IW + run * R + i) * PIXQ + cg) * 16 + hf * SVB, in[i]);
+                        tc_unpack_sv<T, SV>(ddb + (((row + ky) * IW + run * R + i) * PIXQ + cg) * 16 + hf * SVB, in[i]);
 #pragma unroll
                     for (int kx = 0; kx < K; ++kx) {
                         tc_f32x2 wr[S2];
@@ -1405,7 +1314,7 @@ __device__ __forceinline__ void ffn_mid_bwd_body(const FfnSegDev& a, long long w
                 T* dst0 = dh + ((ibase + (long long)oh * W + owb)) * a.lddh + c;
 #pragma unroll
                 for (int r = 0; r < R; ++r)
-                    if (owb + r < W) store_sv<T, SV>(dst0 + (long long)r * a.lddh, o[r]);
+                    if (owb + r < W) tc_store_sv<T, SV>(dst0 + (long long)r * a.lddh, o[r]);
             }
         }
         MSTAMP(5);
@@ -1414,9 +1323,9 @@ __device__ __forceinline__ void ffn_mid_bwd_body(const FfnSegDev& a, long long w
                 const int urow = u / (D::TW / R), urun = u % (D::TW / R);
                 tc_f32x2 d[R][S2], in[R + K - 1][S2];
 #pragma unroll
-                for (int r = 0; r < R; ++r) unpack_sv<T, SV>(ddb + (((urow + 1) * IW + urun * R + r + 1) * PIXQ + cg) * 16 + hf * SVB, d[r]);
+                for (int r = 0; r < R; ++r) tc_unpack_sv<T, SV>(ddb + (((urow + 1) * IW + urun * R + r + 1) * PIXQ + cg) * 16 + hf * SVB, d[r]);
 #pragma unroll
-                for (int i = 0; i < R + K - 1; ++i) unpack_sv<T, SV>(htb + (((urow + ky3) * IW + urun * R + i) * PIXQ + cg) * 16 + hf * SVB, in[i]);
+                for (int i = 0; i < R + K - 1; ++i) tc_unpack_sv<T, SV>(htb + (((urow + ky3) * IW + urun * R + i) * PIXQ + cg) * 16 + hf * SVB, in[i]);
 #pragma unroll
                 for (int kx = 0; kx < K; ++kx)
 #pragma unroll
@@ -1641,7 +1550,7 @@ __global__ __launch_bounds__(256) void dw_fold_kernel(const DwFoldDev q) {
 extern "C" long long tc_dwconv_bwd_plan(int B, int H, int W, int C, int k, int groups, int dtype, TcDwFold* site) {
     if (!site || groups < 1 || !dw_args_ok(B, H, W, C, k, 1, 0)) return 0;
     TC_DISPATCH_DTYPE(dtype, {
-        if (C % Vec16<T>::N) return 0;
+        if (C % TcVec16<T>::N) return 0;
         const WalkLayout l = dw_bwd_layout<T>(B, H, W, C, k, groups);
         walk_site(l.s[0], C, k, groups, site);
         return l.part_floats;
@@ -1654,7 +1563,7 @@ extern "C" long long tc_dwconv_multi_plan(const TcDwSeg* segs, int nseg, int gro
     if (!segs || !sites || !offs || nseg < 1 || nseg > DW_MULTI_MAX || groups < 1) return 0;
     TC_DISPATCH_DTYPE(dtype, {
         for (int i = 0; i < nseg; ++i)
-            if (segs[i].C % Vec16<T>::N || !dw_args_ok(segs[i].B, segs[i].H, segs[i].W, segs[i].C, segs[i].k, 1, 0)) return 0;
+            if (segs[i].C % TcVec16<T>::N || !dw_args_ok(segs[i].B, segs[i].H, segs[i].W, segs[i].C, segs[i].k, 1, 0)) return 0;
         const WalkLayout l = dw_multi_layout<T>(segs, nseg, groups);
         for (int i = 0; i < nseg; ++i) {
             walk_site(l.s[i], segs[i].C, segs[i].k, groups, &sites[i]);
@@ -1794,7 +1703,7 @@ extern "C" long long tc_ffn_mid_plan(const TcFfnSeg* segs, int nseg, int groups,
     if (!segs || !sites || !offs || nseg < 1 || nseg > FFN_MULTI_MAX || groups < 1) return 0;
     TC_DISPATCH_DTYPE(dtype, {
         for (int i = 0; i < nseg; ++i)
-            if (segs[i].C <= 0 || segs[i].C % Vec16<T>::N) return 0;
+            if (segs[i].C <= 0 || segs[i].C % TcVec16<T>::N) return 0;
         const WalkLayout l = ffn_mid_layout<T>(segs, nseg, groups);
         for (int i = 0; i < nseg; ++i) {
             walk_site(l.s[i], segs[i].C, 3, groups, &sites[i]);

@@ -23,10 +23,6 @@
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef short s16x4_t __attribute__((ext_vector_type(4)));
-typedef short s16x8_t __attribute__((ext_vector_type(8)));
-
 constexpr int C = 64, PT = C + 8, TPW = 256, NW = 4, RT = 32 * NW, NRD = TPW / RT;     // channels, LDS row pitch, tokens per workgroup, waves, tokens per round, rounds
 constexpr int TOUT = RT;                                                                    // tokens per workgroup of the forward's output launch
 constexpr int F_M = 0, F_S = C, F_P = 2 * C, F_N = 2 * C + C * C;                       // forward partial of a workgroup
@@ -43,14 +39,6 @@ struct EffDev {
     float eps;
 };
 
-template <typename V8> __device__ __forceinline__ V8 ld_tr(const bf16_t* lo, const bf16_t* hi) {
-    const s16x4_t a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4_t __attribute__((address_space(3)))*)(lo));
-    const s16x4_t b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4_t __attribute__((address_space(3)))*)(hi));
-    return __builtin_bit_cast(V8, (s16x8_t)__builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7));
-}
-template <typename H> __device__ __forceinline__ void up8s(const uint4& r, float* o) {
-    unpack2<H>(r.x, o[0], o[1]); unpack2<H>(r.y, o[2], o[3]); unpack2<H>(r.z, o[4], o[5]); unpack2<H>(r.w, o[6], o[7]);
-}
 // Lane geometry of a wave: D^T tiles put token l31 on the lane and channels cb * 32 + 8 gq + 4 hh + j in register 4 gq + j of acc[cb].
 struct Lane { int lane, l31, hh, gi, gq2, wv; };
 __device__ __forceinline__ Lane lane_of() {
@@ -58,14 +46,14 @@ __device__ __forceinline__ Lane lane_of() {
     return L;
 }
 
-__device__ __forceinline__ void zero2(f32x16 (&a)[2]) {
+__device__ __forceinline__ void zero2(tc_f32x16 (&a)[2]) {
 #pragma unroll
     for (int cb = 0; cb < 2; ++cb)
 #pragma unroll
         for (int r = 0; r < 16; ++r) a[cb][r] = 0.f;
 }
 // acc^T[o][tok] += sum_k W[o][k] X[tok][k]:  W rows = output channel (k contiguous), X rows = this wave's 32 tokens; 16-byte fragment reads
-template <typename H> __device__ __forceinline__ void mm_w(const bf16_t* W, const bf16_t* X, const Lane& L, f32x16 (&acc)[2]) {
+template <typename H> __device__ __forceinline__ void mm_w(const bf16_t* W, const bf16_t* X, const Lane& L, tc_f32x16 (&acc)[2]) {
     using V8 = typename TcHalf<H>::v8;
 #pragma unroll
     for (int kk = 0; kk < C / 16; ++kk) {
@@ -75,30 +63,30 @@ template <typename H> __device__ __forceinline__ void mm_w(const bf16_t* W, cons
     }
 }
 // acc^T[i][tok] += sum_k W[k][i] X[tok][k]:  the same weight matrix used transposed (rows = the reduction index): transpose reads
-template <typename H> __device__ __forceinline__ void mm_wt(const bf16_t* W, const bf16_t* X, const Lane& L, f32x16 (&acc)[2]) {
+template <typename H> __device__ __forceinline__ void mm_wt(const bf16_t* W, const bf16_t* X, const Lane& L, tc_f32x16 (&acc)[2]) {
     using V8 = typename TcHalf<H>::v8;
 #pragma unroll
     for (int kk = 0; kk < C / 16; ++kk) {
         const V8 xv = *reinterpret_cast<const V8*>(X + L.l31 * PT + kk * 16 + 8 * L.hh);
         const bf16_t* wp = W + (16 * kk + 8 * L.hh + (L.gi >> 2)) * PT + 16 * L.gq2 + 4 * (L.gi & 3);
 #pragma unroll
-        for (int cb = 0; cb < 2; ++cb) acc[cb] = TcHalf<H>::mfma(ld_tr<V8>(wp + cb * 32, wp + 4 * PT + cb * 32), xv, acc[cb]);
+        for (int cb = 0; cb < 2; ++cb) acc[cb] = TcHalf<H>::mfma(tc_lds_tr8<V8>(wp + cb * 32, wp + 4 * PT + cb * 32), xv, acc[cb]);
     }
 }
 // acc[i][j] += sum_tok X[tok][32 ib + i] Y[tok][32 jb + j] over the RT tokens of a round (both tiles in LDS, rows = tokens)
-template <typename H> __device__ __forceinline__ void mm_tok(const bf16_t* X, const bf16_t* Y, int ib, int jb, const Lane& L, f32x16& acc) {
+template <typename H> __device__ __forceinline__ void mm_tok(const bf16_t* X, const bf16_t* Y, int ib, int jb, const Lane& L, tc_f32x16& acc) {
     using V8 = typename TcHalf<H>::v8;
     const int col = 16 * L.gq2 + 4 * (L.gi & 3);
 #pragma unroll
     for (int ks = 0; ks < RT / 16; ++ks) {
         const int row = 16 * ks + 8 * L.hh + (L.gi >> 2);
-        const V8 a = ld_tr<V8>(X + row * PT + ib * 32 + col, X + (row + 4) * PT + ib * 32 + col);
-        const V8 b = ld_tr<V8>(Y + row * PT + jb * 32 + col, Y + (row + 4) * PT + jb * 32 + col);
+        const V8 a = tc_lds_tr8<V8>(X + row * PT + ib * 32 + col, X + (row + 4) * PT + ib * 32 + col);
+        const V8 b = tc_lds_tr8<V8>(Y + row * PT + jb * 32 + col, Y + (row + 4) * PT + jb * 32 + col);
         acc = TcHalf<H>::mfma(a, b, acc);
     }
 }
 // a D^T pair of tiles -> the wave's 32 rows of an LDS tile in the storage type
-template <typename H> __device__ __forceinline__ void put_T(bf16_t* X, const Lane& L, const f32x16 (&acc)[2]) {
+template <typename H> __device__ __forceinline__ void put_T(bf16_t* X, const Lane& L, const tc_f32x16 (&acc)[2]) {
 #pragma unroll
     for (int cb = 0; cb < 2; ++cb)
 #pragma unroll
@@ -107,7 +95,7 @@ template <typename H> __device__ __forceinline__ void put_T(bf16_t* X, const Lan
                 make_uint2(pack2<H>(acc[cb][4 * gq], acc[cb][4 * gq + 1]), pack2<H>(acc[cb][4 * gq + 2], acc[cb][4 * gq + 3]));
 }
 // the wave's 32 rows of an LDS tile, added to a D^T pair of tiles
-template <typename H> __device__ __forceinline__ void add_T(const bf16_t* X, const Lane& L, f32x16 (&acc)[2]) {
+template <typename H> __device__ __forceinline__ void add_T(const bf16_t* X, const Lane& L, tc_f32x16 (&acc)[2]) {
 #pragma unroll
     for (int cb = 0; cb < 2; ++cb)
 #pragma unroll
@@ -119,7 +107,7 @@ template <typename H> __device__ __forceinline__ void add_T(const bf16_t* X, con
         }
 }
 // per-channel vector (bias, ...) in the D^T register order, from an fp32 LDS array
-__device__ __forceinline__ void get_vecT(const float* v, const Lane& L, f32x16 (&o)[2]) {
+__device__ __forceinline__ void get_vecT(const float* v, const Lane& L, tc_f32x16 (&o)[2]) {
 #pragma unroll
     for (int cb = 0; cb < 2; ++cb)
 #pragma unroll
@@ -130,7 +118,7 @@ __device__ __forceinline__ void get_vecT(const float* v, const Lane& L, f32x16 (
 }
 // Column reductions over the 32 token lanes through the wave's scratch: every lane parks its 32 per-channel values, then lane j
 // gathers channel j.  D^T order: value e = 16 cb + r of lane (l31, hh) is channel cb * 32 + 8 (r >> 2) + 4 hh + (r & 3).
-template <bool MAX> __device__ __forceinline__ float colred_T(float* sc, const f32x16 (&a)[2], const Lane& L) {
+template <bool MAX> __device__ __forceinline__ float colred_T(float* sc, const tc_f32x16 (&a)[2], const Lane& L) {
 #pragma unroll
     for (int cb = 0; cb < 2; ++cb)
 #pragma unroll
@@ -156,7 +144,7 @@ __device__ __forceinline__ float colsum_row(float* sc, const float* v, const Lan
     return s;
 }
 // one D tile (rows i, columns j) -> dst[i * C + j]
-__device__ __forceinline__ void put_tile(float* dst, int ib, int jb, const f32x16& a, const Lane& L) {
+__device__ __forceinline__ void put_tile(float* dst, int ib, int jb, const tc_f32x16& a, const Lane& L) {
 #pragma unroll
     for (int r = 0; r < 16; ++r) dst[(ib * 32 + (r & 3) + 8 * (r >> 2) + 4 * L.hh) * C + jb * 32 + L.l31] = a[r];
 }
@@ -208,7 +196,7 @@ template <typename H> __device__ __forceinline__ void load_ctx(bf16_t* W, const 
 template <typename H, bool KEEP> __device__ __forceinline__ void ln_tile(bf16_t* X, const float* gam, const float* bet, float eps, const Lane& L, float& rstd, float* xh) {
     float v[32];
 #pragma unroll
-    for (int q = 0; q < 4; ++q) up8s<H>(*reinterpret_cast<const uint4*>(X + L.l31 * PT + L.hh * 32 + q * 8), v + 8 * q);
+    for (int q = 0; q < 4; ++q) tc_unpack16<H>(*reinterpret_cast<const uint4*>(X + L.l31 * PT + L.hh * 32 + q * 8), v + 8 * q);
     float s = 0.f;
 #pragma unroll
     for (int e = 0; e < 32; ++e) s += v[e];
@@ -229,14 +217,14 @@ template <typename H, bool KEEP> __device__ __forceinline__ void ln_tile(bf16_t*
             if (KEEP) xh[8 * q + e] = xhat;
             o[e] = xhat * gam[ch] + bet[ch];
         }
-        *reinterpret_cast<uint4*>(X + L.l31 * PT + L.hh * 32 + q * 8) = make_uint4(pack2<H>(o[0], o[1]), pack2<H>(o[2], o[3]), pack2<H>(o[4], o[5]), pack2<H>(o[6], o[7]));
+        *reinterpret_cast<uint4*>(X + L.l31 * PT + L.hh * 32 + q * 8) = tc_pack16<H>(o);
     }
 }
 // (a wave's LDS accesses execute in order; the compiler must not move them across each other: one fence where rows change hands)
 __device__ __forceinline__ void lds_fence() { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); }
 
 // row softmax of a D^T pair of tiles over the 64 channels of each token (in lane + the partner half-wave)
-__device__ __forceinline__ void row_softmax(f32x16 (&a)[2]) {
+__device__ __forceinline__ void row_softmax(tc_f32x16 (&a)[2]) {
     float m = a[0][0];
 #pragma unroll
     for (int cb = 0; cb < 2; ++cb)
@@ -283,7 +271,7 @@ __global__ __launch_bounds__(64 * NW) void effatt_kv_kernel(const EffDev p) {
     load_v<H>(vec, p.gamma); load_v<H>(vec + C, p.beta); load_v<H>(vec + 2 * C, p.bk); load_v<H>(vec + 3 * C, p.bv);
     __syncthreads();
     // pass 1: LN of the wave's blocks (kept in LDS), their K^T (kept in registers), the column maximum
-    f32x16 kk[NRD][2], mx[2];
+    tc_f32x16 kk[NRD][2], mx[2];
 #pragma unroll
     for (int cb = 0; cb < 2; ++cb)
 #pragma unroll
@@ -311,7 +299,7 @@ __global__ __launch_bounds__(64 * NW) void effatt_kv_kernel(const EffDev p) {
     __syncthreads();
     get_vecT(mall, L, mx);
     // pass 2: E = exp(K - m), S += E, P += E^T V (wave = one 32 x 32 tile of P over the round's tokens)
-    f32x16 ss[2], pp;
+    tc_f32x16 ss[2], pp;
     zero2(ss);
 #pragma unroll
     for (int r = 0; r < 16; ++r) pp[r] = 0.f;
@@ -321,7 +309,7 @@ __global__ __launch_bounds__(64 * NW) void effatt_kv_kernel(const EffDev p) {
         const int blk = rd * NW + L.wv, nv = q.ntok - blk * 32;
         const bf16_t* X = xt + blk * 32 * PT;
         const bool ok = L.l31 < nv;
-        f32x16 vv[2];
+        tc_f32x16 vv[2];
         get_vecT(vec + 3 * C, L, vv);
         mm_w<H>(wv, X, L, vv);
 #pragma unroll
@@ -402,7 +390,7 @@ __global__ __launch_bounds__(64 * NW) void effatt_out_kernel(const EffDev p) {
     float rstd;
     ln_tile<H, false>(nt, vec, vec + C, p.eps, L, rstd, nullptr);
     lds_fence();
-    f32x16 a[2];
+    tc_f32x16 a[2];
     get_vecT(vec + 2 * C, L, a);
     mm_w<H>(wq, nt, L, a);
     row_softmax(a);
@@ -431,10 +419,10 @@ __global__ __launch_bounds__(64 * NW) void effatt_out_kernel(const EffDev p) {
         const float* src = reinterpret_cast<const float*>((cg >> 2) ? nt : st) + r * (PT / 2) + (cg & 3) * 8;
         const float4 o0 = *reinterpret_cast<const float4*>(src), o1 = *reinterpret_cast<const float4*>(src + 4);
         float o[8] = {o0.x, o0.y, o0.z, o0.w, o1.x, o1.y, o1.z, o1.w}, x[8];
-        up8s<H>(tf[i], x);
+        tc_unpack16<H>(tf[i], x);
 #pragma unroll
         for (int e = 0; e < 8; ++e) o[e] += x[e];
-        if (r < nv) *reinterpret_cast<uint4*>(O + (row + r) * p.ldo + cg * 8) = make_uint4(pack2<H>(o[0], o[1]), pack2<H>(o[2], o[3]), pack2<H>(o[4], o[5]), pack2<H>(o[6], o[7]));
+        if (r < nv) *reinterpret_cast<uint4*>(O + (row + r) * p.ldo + cg * 8) = tc_pack16<H>(o);
     }
 }
 
@@ -459,7 +447,7 @@ __global__ __launch_bounds__(64 * NW) void effatt_bq_kernel(const EffDev p) {
     const int wo = L.wv * 32 * PT;
     bf16_t* nt = nts + wo; bf16_t* qt = qts + wo; bf16_t* at = ats + wo; bf16_t* yt = yts + wo; bf16_t* dat = dats + wo; bf16_t* dqt = dqts + wo;
     __syncthreads();
-    f32x16 dctx, dwr, dwq, dbr[2], dbq[2];
+    tc_f32x16 dctx, dwr, dwq, dbr[2], dbq[2];
 #pragma unroll
     for (int r = 0; r < 16; ++r) { dctx[r] = 0.f; dwr[r] = 0.f; dwq[r] = 0.f; }
     zero2(dbr); zero2(dbq);
@@ -478,7 +466,7 @@ __global__ __launch_bounds__(64 * NW) void effatt_bq_kernel(const EffDev p) {
         float rstd;
         ln_tile<H, false>(nt, vec, vec + C, p.eps, L, rstd, nullptr);
         lds_fence();
-        f32x16 qs[2], a[2];
+        tc_f32x16 qs[2], a[2];
         get_vecT(vec + 2 * C, L, qs);
         mm_w<H>(wq, nt, L, qs);
         row_softmax(qs);
@@ -574,7 +562,7 @@ __global__ __launch_bounds__(64 * NW) void effatt_bkv_kernel(const EffDev p) {
     const int wo = L.wv * 32 * PT;
     bf16_t* nt = tl + wo; bf16_t* kt = tl + RT * PT + wo; bf16_t* vt = tl + 2 * RT * PT + wo; bf16_t* dkt = dkts + wo; bf16_t* dvt = dvts + wo; bf16_t* gt = tl + 5 * RT * PT + wo;
     __syncthreads();
-    f32x16 dwk, dwv, dbk[2], dbv[2];
+    tc_f32x16 dwk, dwv, dbk[2], dbv[2];
     float dgr[32], dbr[32];                                        // dgamma / dbeta of the lane's token, row order (channels hh * 32 + e)
 #pragma unroll
     for (int r = 0; r < 16; ++r) { dwk[r] = 0.f; dwv[r] = 0.f; }
@@ -596,7 +584,7 @@ __global__ __launch_bounds__(64 * NW) void effatt_bkv_kernel(const EffDev p) {
         float rstd, xh[32];
         ln_tile<H, true>(nt, vec, vec + C, p.eps, L, rstd, xh);
         lds_fence();
-        f32x16 ks[2], a[2], b2[2];
+        tc_f32x16 ks[2], a[2], b2[2];
         get_vecT(vec + 2 * C, L, ks);
         mm_w<H>(wk, nt, L, ks);
         get_vecT(vec + 3 * C, L, a);
@@ -614,7 +602,7 @@ __global__ __launch_bounds__(64 * NW) void effatt_bkv_kernel(const EffDev p) {
         zero2(b2);
         mm_w<H>(dcx, vt, L, b2);                                   // dKsm^T[c][tok] = sum_c' d_ctx[c][c'] V[tok][c']
         {
-            f32x16 rv[2];
+            tc_f32x16 rv[2];
             get_vecT(vec + 6 * C, L, rv);
 #pragma unroll
             for (int cb = 0; cb < 2; ++cb)
@@ -640,8 +628,8 @@ __global__ __launch_bounds__(64 * NW) void effatt_bkv_kernel(const EffDev p) {
 #pragma unroll
         for (int qq = 0; qq < 4; ++qq) {
             float x[8], y[8];
-            up8s<H>(*reinterpret_cast<const uint4*>(kt + L.l31 * PT + L.hh * 32 + qq * 8), x);
-            up8s<H>(*reinterpret_cast<const uint4*>(gt + L.l31 * PT + L.hh * 32 + qq * 8), y);
+            tc_unpack16<H>(*reinterpret_cast<const uint4*>(kt + L.l31 * PT + L.hh * 32 + qq * 8), x);
+            tc_unpack16<H>(*reinterpret_cast<const uint4*>(gt + L.l31 * PT + L.hh * 32 + qq * 8), y);
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
                 const float d = ok ? x[e] + y[e] : 0.f;             // d_n1
@@ -659,7 +647,7 @@ __global__ __launch_bounds__(64 * NW) void effatt_bkv_kernel(const EffDev p) {
             float o[8];
 #pragma unroll
             for (int e = 0; e < 8; ++e) o[e] = rstd * (dn[qq * 8 + e] - k1 - xh[qq * 8 + e] * k2);
-            *reinterpret_cast<uint4*>(vt + L.l31 * PT + L.hh * 32 + qq * 8) = make_uint4(pack2<H>(o[0], o[1]), pack2<H>(o[2], o[3]), pack2<H>(o[4], o[5]), pack2<H>(o[6], o[7]));
+            *reinterpret_cast<uint4*>(vt + L.l31 * PT + L.hh * 32 + qq * 8) = tc_pack16<H>(o);
         }
         // dt = LayerNorm backward + the residual's gradient (dout) [+ what dt holds]
         stash_tile(kt, yf, L.lane);
@@ -669,17 +657,16 @@ __global__ __launch_bounds__(64 * NW) void effatt_bkv_kernel(const EffDev p) {
         for (int i = 0; i < 4; ++i) {
             const int r = 8 * i + (L.lane >> 3), cg = L.lane & 7;
             float x[8], y[8];
-            up8s<H>(*reinterpret_cast<const uint4*>(vt + r * PT + cg * 8), x);
-            up8s<H>(*reinterpret_cast<const uint4*>(kt + r * PT + cg * 8), y);
+            tc_unpack16<H>(*reinterpret_cast<const uint4*>(vt + r * PT + cg * 8), x);
+            tc_unpack16<H>(*reinterpret_cast<const uint4*>(kt + r * PT + cg * 8), y);
 #pragma unroll
             for (int e = 0; e < 8; ++e) x[e] += y[e];
             if (p.acc_dt) {
-                up8s<H>(*reinterpret_cast<const uint4*>(gt + r * PT + cg * 8), y);
+                tc_unpack16<H>(*reinterpret_cast<const uint4*>(gt + r * PT + cg * 8), y);
 #pragma unroll
                 for (int e = 0; e < 8; ++e) x[e] += y[e];
             }
-            if (r < nv) *reinterpret_cast<uint4*>(DT + (row + r) * p.lddt + cg * 8) =
-                make_uint4(pack2<H>(x[0], x[1]), pack2<H>(x[2], x[3]), pack2<H>(x[4], x[5]), pack2<H>(x[6], x[7]));
+            if (r < nv) *reinterpret_cast<uint4*>(DT + (row + r) * p.lddt + cg * 8) = tc_pack16<H>(x);
         }
         __syncthreads();
         mm_tok<H>(dkts, nts, ib, jb, L, dwk);                      // dWk[c][cin] += sum_tok dK[tok][c] n1[tok][cin]

@@ -13,43 +13,17 @@ namespace {
 
 constexpr int FA_MAXCH = 64;
 
-template <typename T> struct V16;
-template <> struct V16<float> { static constexpr int N = 4; };
-template <> struct V16<bf16_t> { static constexpr int N = 8; };
-template <> struct V16<f16_t> { static constexpr int N = 8; };
-template <typename T> __device__ __forceinline__ void unpack16(const uint4& r, float* o);
-template <> __device__ __forceinline__ void unpack16<float>(const uint4& r, float* o) {
-    o[0] = __uint_as_float(r.x); o[1] = __uint_as_float(r.y); o[2] = __uint_as_float(r.z); o[3] = __uint_as_float(r.w);
-}
-template <> __device__ __forceinline__ void unpack16<bf16_t>(const uint4& r, float* o) {
-    o[0] = __uint_as_float(r.x << 16); o[1] = __uint_as_float(r.x & 0xffff0000u); o[2] = __uint_as_float(r.y << 16);
-    o[3] = __uint_as_float(r.y & 0xffff0000u); o[4] = __uint_as_float(r.z << 16); o[5] = __uint_as_float(r.z & 0xffff0000u);
-    o[6] = __uint_as_float(r.w << 16); o[7] = __uint_as_float(r.w & 0xffff0000u);
-}
-template <> __device__ __forceinline__ void unpack16<f16_t>(const uint4& r, float* o) {
-    unpack2<f16_t>(r.x, o[0], o[1]); unpack2<f16_t>(r.y, o[2], o[3]); unpack2<f16_t>(r.z, o[4], o[5]); unpack2<f16_t>(r.w, o[6], o[7]);
-}
-template <typename T> __device__ __forceinline__ uint4 pack16(const float* o);
-template <> __device__ __forceinline__ uint4 pack16<float>(const float* o) {
-    return make_uint4(__float_as_uint(o[0]), __float_as_uint(o[1]), __float_as_uint(o[2]), __float_as_uint(o[3]));
-}
-template <> __device__ __forceinline__ uint4 pack16<bf16_t>(const float* o) {
-    return make_uint4(pack2bf(o[0], o[1]), pack2bf(o[2], o[3]), pack2bf(o[4], o[5]), pack2bf(o[6], o[7]));
-}
-template <> __device__ __forceinline__ uint4 pack16<f16_t>(const float* o) {
-    return make_uint4(pack2h(o[0], o[1]), pack2h(o[2], o[3]), pack2h(o[4], o[5]), pack2h(o[6], o[7]));
-}
 // head tile [N][Ch] of a row-strided matrix -> fp32 LDS, 16-byte loads, four in flight per thread (a scalar copy loop keeps ONE
 // load in flight and made the first version of this kernel 50 us for 6272 elements)
 template <typename T>
 __device__ __forceinline__ void fa_load_tile(float* dst, const T* src, int ld, int N, int Ch) {
-    constexpr int VEC = V16<T>::N;
+    constexpr int VEC = TcVec16<T>::N;
     const int nv = Ch / VEC, total = N * nv;
 #pragma unroll 4
     for (int i = threadIdx.x; i < total; i += 256) {
         const int n = i / nv, cv = i - n * nv;
         const uint4 r = *reinterpret_cast<const uint4*>(src + (long long)n * ld + cv * VEC);
-        unpack16<T>(r, dst + n * Ch + cv * VEC);
+        tc_unpack16<T>(r, dst + n * Ch + cv * VEC);
     }
 }
 
@@ -77,7 +51,7 @@ __device__ __forceinline__ void fa_softmax_cols(float* e, float* cmax, float* ci
 // workgroups per CU at N = 784 instead of one)
 template <typename T>
 __device__ __forceinline__ void fa_load_tile_raw(T* dst, const T* src, int ld, int N, int Ch) {
-    constexpr int VEC = V16<T>::N;
+    constexpr int VEC = TcVec16<T>::N;
     const int nv = Ch / VEC, total = N * nv;
 #pragma unroll 4
     for (int i = threadIdx.x; i < total; i += 256) {
@@ -92,8 +66,8 @@ __device__ __forceinline__ void fa_get8(const float* p, float* o) {
     const float4 a = *reinterpret_cast<const float4*>(p), b = *reinterpret_cast<const float4*>(p + 4);
     o[0] = a.x; o[1] = a.y; o[2] = a.z; o[3] = a.w; o[4] = b.x; o[5] = b.y; o[6] = b.z; o[7] = b.w;
 }
-__device__ __forceinline__ void fa_get8(const bf16_t* p, float* o) { unpack16<bf16_t>(*reinterpret_cast<const uint4*>(p), o); }
-__device__ __forceinline__ void fa_get8(const f16_t* p, float* o) { unpack16<f16_t>(*reinterpret_cast<const uint4*>(p), o); }
+__device__ __forceinline__ void fa_get8(const bf16_t* p, float* o) { tc_unpack16<bf16_t>(*reinterpret_cast<const uint4*>(p), o); }
+__device__ __forceinline__ void fa_get8(const f16_t* p, float* o) { tc_unpack16<f16_t>(*reinterpret_cast<const uint4*>(p), o); }
 
 // out[i][j] = sum_n a[n,i] * b[n,j]   (Ch x Ch, Ch a multiple of 8).  A thread owns (row i, 8 consecutive j) for the rows
 // n = rl, rl + RL, ...: one read of a[n,i], two 16-byte reads of b[n, j0..j0+7], 8 FMAs; the RL row lanes of an output sit next to
@@ -140,7 +114,7 @@ template <typename T>
 __global__ __launch_bounds__(256) void factor_att_fwd_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* __restrict__ v, int ld,
                                                              const T* __restrict__ convv, int ldc, T* __restrict__ o, int ldo,
                                                              float* __restrict__ stats, int N, int Ch, int heads, float scale) {
-    constexpr int VEC = V16<T>::N;
+    constexpr int VEC = TcVec16<T>::N;
     extern __shared__ float sm[];
     float* e = sm;                       // [N][Ch]  k, then exp(k - max)
     float* ctx = e + N * Ch;             // [Ch][Ch]
@@ -168,7 +142,7 @@ __global__ __launch_bounds__(256) void factor_att_fwd_kernel(const T* __restrict
     for (int i = tid; i < N * nv; i += 256) {
         const int n = i / nv, j0 = (i - n * nv) * VEC;
         float cv[VEC], acc[VEC];
-        unpack16<T>(*reinterpret_cast<const uint4*>(convv + (row0 + n) * ldc + col0 + j0), cv);
+        tc_unpack16<T>(*reinterpret_cast<const uint4*>(convv + (row0 + n) * ldc + col0 + j0), cv);
 #pragma unroll
         for (int u = 0; u < VEC; ++u) acc[u] = 0.f;
         const T* qr = qs + n * Ch;
@@ -187,7 +161,7 @@ __global__ __launch_bounds__(256) void factor_att_fwd_kernel(const T* __restrict
         }
 #pragma unroll
         for (int u = 0; u < VEC; ++u) acc[u] = scale * acc[u] + fa_get(qr, j0 + u) * cv[u];
-        *reinterpret_cast<uint4*>(o + (row0 + n) * ldo + col0 + j0) = pack16<T>(acc);
+        *reinterpret_cast<uint4*>(o + (row0 + n) * ldo + col0 + j0) = tc_pack16<T>(acc);
     }
 }
 
@@ -197,7 +171,7 @@ __global__ __launch_bounds__(256) void factor_att_bwd_kernel(const T* __restrict
                                                              const float* __restrict__ stats, T* __restrict__ dq, T* __restrict__ dk,
                                                              T* __restrict__ dv, int ldd, int acc_q, int acc_k, int acc_v,
                                                              T* __restrict__ dconvv, int lddc, int N, int Ch, int heads, float scale) {
-    constexpr int VEC = V16<T>::N;
+    constexpr int VEC = TcVec16<T>::N;
     extern __shared__ float sm[];
     float* e = sm;                       // softmax(k) (normalised), fp32
     float* ctx = e + N * Ch;
@@ -266,7 +240,7 @@ __global__ __launch_bounds__(256) void factor_att_bwd_kernel(const T* __restrict
                 }
             }
         }
-        unpack16<T>(*reinterpret_cast<const uint4*>(convv + r * ldc + col0 + c0), cv);
+        tc_unpack16<T>(*reinterpret_cast<const uint4*>(convv + r * ldc + col0 + c0), cv);
         T* pq = dq + r * ldd + col0 + c0; T* pk = dk + r * ldd + col0 + c0; T* pv = dv + r * ldd + col0 + c0;
         float old[VEC];
 #pragma unroll
@@ -274,19 +248,19 @@ __global__ __launch_bounds__(256) void factor_att_bwd_kernel(const T* __restrict
             const float gc = fa_get(gr, c0 + u);
             oc[u] = gc * fa_get(qs, n * Ch + c0 + u); a_q[u] = scale * a_q[u] + gc * cv[u]; a_ks[u] = er[c0 + u] * (a_ks[u] - tcol[c0 + u]);
         }
-        if (acc_q) { unpack16<T>(*reinterpret_cast<const uint4*>(pq), old);
+        if (acc_q) { tc_unpack16<T>(*reinterpret_cast<const uint4*>(pq), old);
 #pragma unroll
             for (int u = 0; u < VEC; ++u) a_q[u] += old[u]; }
-        if (acc_k) { unpack16<T>(*reinterpret_cast<const uint4*>(pk), old);
+        if (acc_k) { tc_unpack16<T>(*reinterpret_cast<const uint4*>(pk), old);
 #pragma unroll
             for (int u = 0; u < VEC; ++u) a_ks[u] += old[u]; }
-        if (acc_v) { unpack16<T>(*reinterpret_cast<const uint4*>(pv), old);
+        if (acc_v) { tc_unpack16<T>(*reinterpret_cast<const uint4*>(pv), old);
 #pragma unroll
             for (int u = 0; u < VEC; ++u) a_v[u] += old[u]; }
-        *reinterpret_cast<uint4*>(pq) = pack16<T>(a_q);
-        *reinterpret_cast<uint4*>(pk) = pack16<T>(a_ks);
-        *reinterpret_cast<uint4*>(pv) = pack16<T>(a_v);
-        *reinterpret_cast<uint4*>(dconvv + r * lddc + col0 + c0) = pack16<T>(oc);
+        *reinterpret_cast<uint4*>(pq) = tc_pack16<T>(a_q);
+        *reinterpret_cast<uint4*>(pk) = tc_pack16<T>(a_ks);
+        *reinterpret_cast<uint4*>(pv) = tc_pack16<T>(a_v);
+        *reinterpret_cast<uint4*>(dconvv + r * lddc + col0 + c0) = tc_pack16<T>(oc);
     }
 }
 
@@ -346,7 +320,7 @@ __device__ __forceinline__ void mhca_conv_tile(T* cvs, const T* vs, const float*
                 const int xc = (unsigned)xx < (unsigned)W ? xx : x0;
                 uint4 r = *reinterpret_cast<const uint4*>(vs + tc_mul24(tc_mad24(yc, W, xc), CH) + c0);
                 if (!ok) r = make_uint4(0u, 0u, 0u, 0u);
-                unpack16<T>(r, vin[j]);
+                tc_unpack16<T>(r, vin[j]);
             }
 #pragma unroll
             for (int kx = 0; kx < K; ++kx) {
@@ -360,7 +334,7 @@ __device__ __forceinline__ void mhca_conv_tile(T* cvs, const T* vs, const float*
         }
 #pragma unroll
         for (int o = 0; o < XB; ++o)
-            if (x0 + o < W) *reinterpret_cast<uint4*>(cvs + tc_mul24(tc_mad24(y, W, x0 + o), CH) + c0) = pack16<T>(acc[o]);
+            if (x0 + o < W) *reinterpret_cast<uint4*>(cvs + tc_mul24(tc_mad24(y, W, x0 + o), CH) + c0) = tc_pack16<T>(acc[o]);
     }
 }
 template <int K, int CH, typename T>
@@ -596,7 +570,7 @@ __global__ __launch_bounds__(256, 2) void mhca_att_fwd_kernel(MhcaAttDev p) {
             const int n = i / NV, c0 = (i - n * NV) * 8;
             T* dst = qo + tc_mul24(n, p.ldq) + c0;
             *reinterpret_cast<uint4*>(dst) = *reinterpret_cast<const uint4*>(qs + n * CH + c0);
-            *reinterpret_cast<uint4*>(dst + C) = pack16<T>(e + n * CH + c0);
+            *reinterpret_cast<uint4*>(dst + C) = tc_pack16<T>(e + n * CH + c0);
             *reinterpret_cast<uint4*>(dst + 2 * C) = *reinterpret_cast<const uint4*>(vs + n * CH + c0);
         }
     }
@@ -623,7 +597,7 @@ __global__ __launch_bounds__(256, 2) void mhca_att_fwd_kernel(MhcaAttDev p) {
             float cv[8], acc[8];
             const uint4 craw = *reinterpret_cast<const uint4*>(cvs + n * CH + j0);
             *reinterpret_cast<uint4*>(co + tc_mul24(n, p.ldc) + j0) = craw;
-            unpack16<T>(craw, cv);
+            tc_unpack16<T>(craw, cv);
 #pragma unroll
             for (int u = 0; u < 8; ++u) acc[u] = 0.f;
             const T* qr = qs + n * CH;
@@ -643,7 +617,7 @@ __global__ __launch_bounds__(256, 2) void mhca_att_fwd_kernel(MhcaAttDev p) {
             fa_get8(qr + j0, qj);
 #pragma unroll
             for (int u = 0; u < 8; ++u) acc[u] = scale * acc[u] + qj[u] * cv[u];
-            *reinterpret_cast<uint4*>(oo + tc_mul24(n, p.ldo) + j0) = pack16<T>(acc);
+            *reinterpret_cast<uint4*>(oo + tc_mul24(n, p.ldo) + j0) = tc_pack16<T>(acc);
         }
     }
 #ifdef TC_MHCA_TIMING
@@ -714,7 +688,7 @@ __device__ __forceinline__ void mhca_conv_wgrad(const T* dc, const T* vs, float*
             const int xx = i - P;
             uint4 raw = *reinterpret_cast<const uint4*>(vr + (xx > 0 && xx < W ? xx : 0) * CH);
             if (!(rv && xx >= 0 && xx < W)) raw = make_uint4(0u, 0u, 0u, 0u);
-            unpack16<T>(raw, win[i]);
+            tc_unpack16<T>(raw, win[i]);
         }
         for (int xb = 0; xb < W; xb += K) {
 #pragma unroll
@@ -725,12 +699,12 @@ __device__ __forceinline__ void mhca_conv_wgrad(const T* dc, const T* vs, float*
                     const int xx = x + P;
                     uint4 raw = *reinterpret_cast<const uint4*>(vr + (xx < W ? xx : 0) * CH);
                     if (!(rv && xx < W)) raw = make_uint4(0u, 0u, 0u, 0u);
-                    unpack16<T>(raw, win[(j + K - 1) % K]);
+                    tc_unpack16<T>(raw, win[(j + K - 1) % K]);
                 }
                 uint4 draw = *reinterpret_cast<const uint4*>(dr + (x < W ? x : 0) * CH);
                 if (!(live && x < W)) draw = make_uint4(0u, 0u, 0u, 0u);
                 float d8[8];
-                unpack16<T>(draw, d8);
+                tc_unpack16<T>(draw, d8);
 #pragma unroll
                 for (int u = 0; u < 8; ++u) accb[u] += d8[u];
 #pragma unroll
@@ -867,7 +841,7 @@ __global__ __launch_bounds__(256, 2) void mhca_att_bwd_kernel(MhcaAttBwdDev p) {
                     *reinterpret_cast<u32x4*>(vs + n * CH + c8) = rv[j];
                     *reinterpret_cast<u32x4*>(gs_ + n * CH + c8) = rg[j];
                     float k8[8];
-                    unpack16<T>(make_uint4(rk[j].x, rk[j].y, rk[j].z, rk[j].w), k8);
+                    tc_unpack16<T>(make_uint4(rk[j].x, rk[j].y, rk[j].z, rk[j].w), k8);
 #pragma unroll
                     for (int u = 0; u < 8; ++u) k8[u] = __expf(k8[u] - cmaxp[c8 + u]) * cmaxp[CH + c8 + u];
                     *reinterpret_cast<float4*>(e + n * CH + c8) = make_float4(k8[0], k8[1], k8[2], k8[3]);
@@ -890,7 +864,7 @@ __global__ __launch_bounds__(256, 2) void mhca_att_bwd_kernel(MhcaAttBwdDev p) {
         fa_get8(qs + i * 8, a); fa_get8(gs_ + i * 8, b);
 #pragma unroll
         for (int u = 0; u < 8; ++u) a[u] *= b[u];
-        *reinterpret_cast<uint4*>(qs + i * 8) = pack16<T>(a);
+        *reinterpret_cast<uint4*>(qs + i * 8) = tc_pack16<T>(a);
     }
     __syncthreads();
     if (tid < CH) { float t = 0.f; for (int j = 0; j < CH; ++j) t += ctx[tid * CH + j] * dctx[tid * CH + j]; tcol[tid] = t; }
@@ -946,7 +920,7 @@ __global__ __launch_bounds__(256, 2) void mhca_att_bwd_kernel(MhcaAttBwdDev p) {
                 }
             }
         }
-        unpack16<T>(cvraw, cv);
+        tc_unpack16<T>(cvraw, cv);
         float dvc8[8], g0[8];
         fa_get8(dvc + n * CH + c0, dvc8);
         fa_get8(gr + c0, g0);
@@ -958,18 +932,18 @@ __global__ __launch_bounds__(256, 2) void mhca_att_bwd_kernel(MhcaAttBwdDev p) {
             a_ks[u] = er[c0 + u] * (a_ks[u] - tcol[c0 + u]);
             a_v[u] += dvc8[u];
         }
-        if (p.acc_q) { unpack16<T>(*reinterpret_cast<const uint4*>(pq), old);
+        if (p.acc_q) { tc_unpack16<T>(*reinterpret_cast<const uint4*>(pq), old);
 #pragma unroll
             for (int u = 0; u < VEC; ++u) a_q[u] += old[u]; }
-        if (p.acc_k) { unpack16<T>(*reinterpret_cast<const uint4*>(pq + C), old);
+        if (p.acc_k) { tc_unpack16<T>(*reinterpret_cast<const uint4*>(pq + C), old);
 #pragma unroll
             for (int u = 0; u < VEC; ++u) a_ks[u] += old[u]; }
-        if (p.acc_v) { unpack16<T>(*reinterpret_cast<const uint4*>(pq + 2 * C), old);
+        if (p.acc_v) { tc_unpack16<T>(*reinterpret_cast<const uint4*>(pq + 2 * C), old);
 #pragma unroll
             for (int u = 0; u < VEC; ++u) a_v[u] += old[u]; }
-        *reinterpret_cast<uint4*>(pq) = pack16<T>(a_q);
-        *reinterpret_cast<uint4*>(pq + C) = pack16<T>(a_ks);
-        *reinterpret_cast<uint4*>(pq + 2 * C) = pack16<T>(a_v);
+        *reinterpret_cast<uint4*>(pq) = tc_pack16<T>(a_q);
+        *reinterpret_cast<uint4*>(pq + C) = tc_pack16<T>(a_ks);
+        *reinterpret_cast<uint4*>(pq + 2 * C) = tc_pack16<T>(a_v);
     };
 #pragma unroll
     for (int jt = 0; jt < 4; ++jt) {
@@ -1116,22 +1090,22 @@ __global__ __launch_bounds__(256) void dw_ln_fwd_kernel(DwLnDev p) {
     for (int v = 0; v < NVL; ++v) {
         const int c0 = v * 64 + sub * 8;
         float acc[8], ctr[8];
-        unpack16<T>(raw[4][v], ctr);
+        tc_unpack16<T>(raw[4][v], ctr);
 #pragma unroll
         for (int u = 0; u < 8; ++u) acc[u] = bs[c0 + u];
 #pragma unroll
         for (int tap = 0; tap < 9; ++tap) {
             float xv[8], w8[8];
-            unpack16<T>(raw[tap][v], xv);
+            tc_unpack16<T>(raw[tap][v], xv);
             fa_get8(wt + tap * C + c0, w8);
 #pragma unroll
             for (int u = 0; u < 8; ++u) acc[u] = fmaf(xv[u], w8[u], acc[u]);
         }
 #pragma unroll
         for (int u = 0; u < 8; ++u) acc[u] += ctr[u];
-        const uint4 pk = pack16<T>(acc);
+        const uint4 pk = tc_pack16<T>(acc);
         if (live) *reinterpret_cast<uint4*>(reinterpret_cast<T*>(p.t1) + (grow + r) * p.ldt + c0) = pk;
-        unpack16<T>(pk, t1v[v]);                                 // (the statistics see what the next reader of t1 will see)
+        tc_unpack16<T>(pk, t1v[v]);                                 // (the statistics see what the next reader of t1 will see)
 #pragma unroll
         for (int u = 0; u < 8; ++u) s1 += t1v[v][u];
     }
@@ -1149,7 +1123,7 @@ __global__ __launch_bounds__(256) void dw_ln_fwd_kernel(DwLnDev p) {
             float o[8];
 #pragma unroll
             for (int u = 0; u < 8; ++u) o[u] = (t1v[v][u] - mean) * rstd * gm[c0 + u] + bt[c0 + u];
-            *reinterpret_cast<uint4*>(reinterpret_cast<T*>(p.xn) + (grow + r) * p.ldn + c0) = pack16<T>(o);
+            *reinterpret_cast<uint4*>(reinterpret_cast<T*>(p.xn) + (grow + r) * p.ldn + c0) = tc_pack16<T>(o);
         }
         if (sub == 0) { p.mean[grow + r] = mean; p.rstd[grow + r] = rstd; }
     }

@@ -14,7 +14,6 @@
 #include <type_traits>
 #include <cstdlib>
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
@@ -23,11 +22,11 @@ typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 template <typename H> struct HalfOps;
 template <> struct HalfOps<bf16_t> {
     typedef bf16x8 v8;
-    static __device__ __forceinline__ f32x16 mfma(v8 a, v8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); }
+    static __device__ __forceinline__ tc_f32x16 mfma(v8 a, v8 b, tc_f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); }
 };
 template <> struct HalfOps<f16_t> {
     typedef f16x8 v8;
-    static __device__ __forceinline__ f32x16 mfma(v8 a, v8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
+    static __device__ __forceinline__ tc_f32x16 mfma(v8 a, v8 b, tc_f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
 };
 
 namespace {
@@ -68,22 +67,16 @@ struct GemmDev {
 constexpr int GEMM_BN_STATS = 4;
 
 // GELU(LayerNorm(.)) on raw 8 x bf16 / 4 x fp32 operand strips (the A rows of fc2's forward, the B rows of its weight gradient)
-template <typename H> __device__ __forceinline__ void bf8_unpack(const uint4& r, float* o) {
-    unpack2<H>(r.x, o[0], o[1]); unpack2<H>(r.y, o[2], o[3]); unpack2<H>(r.z, o[4], o[5]); unpack2<H>(r.w, o[6], o[7]);
-}
-template <typename H> __device__ __forceinline__ uint4 bf8_pack(const float* o) {
-    return make_uint4(pack2<H>(o[0], o[1]), pack2<H>(o[2], o[3]), pack2<H>(o[4], o[5]), pack2<H>(o[6], o[7]));
-}
 template <typename H> __device__ __forceinline__ uint4 ffn_ln_gelu8(const uint4& v, float mean, float rstd, const float* g, const float* b) {
     float x[8];
-    bf8_unpack<H>(v, x);
+    tc_unpack16<H>(v, x);
 #pragma unroll
     for (int e = 0; e < 8; e += 2) {                          // pairs on the packed fp32 pipe
         const tc_f32x2 xv = {x[e], x[e + 1]}, gv = {g[e], g[e + 1]}, bv = {b[e], b[e + 1]};
         const tc_f32x2 u = gelu_poly2((xv - mean) * rstd * gv + bv);             // (16-bit storage: the polynomial CDF, tc_common.h)
         x[e] = u.x; x[e + 1] = u.y;
     }
-    return bf8_pack<H>(x);
+    return tc_pack16<H>(x);
 }
 __device__ __forceinline__ float4 ffn_ln_gelu4(const float4& v, float mean, float rstd, const float4& g, const float4& b) {
     return make_float4(gelu_f((v.x - mean) * rstd * g.x + b.x), gelu_f((v.y - mean) * rstd * g.y + b.y),
@@ -146,7 +139,7 @@ template <typename T> __device__ __forceinline__ float ffn_ep1(float v, float d,
 // the counter is an agent-scope atomic; an agent-scope fence here would write back and invalidate the whole L2 per workgroup
 // (measured 4x slower than no split at all).
 template <int TM, int TN>
-__device__ __forceinline__ bool splitk_fixup(const GemmDev& p, f32x16 (&acc)[TM][TN], int tile, int ks, int& grp) {
+__device__ __forceinline__ bool splitk_fixup(const GemmDev& p, tc_f32x16 (&acc)[TM][TN], int tile, int ks, int& grp) {
     const int G = p.fix_group, tid = threadIdx.x;
     grp = ks / G;
     const int g0 = grp * G, gm = min(G, p.splitk - g0);
@@ -197,7 +190,7 @@ __device__ __forceinline__ bool splitk_fixup(const GemmDev& p, f32x16 (&acc)[TM]
 // block and register r holds column n = (r&3) + 8*(r>>2) + 4*(lane>>5): four consecutive columns per register group,
 // i.e. 8-byte (bf16) / 16-byte (fp32) row-major stores instead of 2-byte ones.
 template <typename T, typename TC, int TM, int TN>
-__device__ __forceinline__ void epilogue_rows(const GemmDev& p, f32x16 (&acc)[TM][TN], int b1, int b2, bool first_split, bool atomic, int mbase, int nbase, int lane) {
+__device__ __forceinline__ void epilogue_rows(const GemmDev& p, tc_f32x16 (&acc)[TM][TN], int b1, int b2, bool first_split, bool atomic, int mbase, int nbase, int lane) {
     TC* C = reinterpret_cast<TC*>(p.C) + b1 * p.sC1 + b2 * p.sC2;
     const T* R = p.R ? reinterpret_cast<const T*>(p.R) + b1 * p.sR1 + b2 * p.sR2 : nullptr;
     const T* bias = p.bias ? reinterpret_cast<const T*>(p.bias) + b1 * p.sBias1 : nullptr;
@@ -265,7 +258,7 @@ __device__ __forceinline__ void epilogue_rows(const GemmDev& p, f32x16 (&acc)[TM
 // workgroup's 64 columns go to ffn.part2[row][ntile]; srow = LDS float2 [2][64] (the two column halves of the tile), mloc0 = first
 // tile row of this wave.
 template <typename T, typename TC, int TM, int TN, bool EP = false>
-__device__ __forceinline__ void epilogue_cols(const GemmDev& p, f32x16 (&acc)[TM][TN], int b1, int b2, bool first_split, bool atomic, int mbase, int nbase, int lane,
+__device__ __forceinline__ void epilogue_cols(const GemmDev& p, tc_f32x16 (&acc)[TM][TN], int b1, int b2, bool first_split, bool atomic, int mbase, int nbase, int lane,
                                               float2* srow = nullptr, int mloc0 = 0, int wc = 0, int m0 = 0, int ntile = 0, int ntiles = 0) {
     TC* C = reinterpret_cast<TC*>(p.C) + b1 * p.sC1 + b2 * p.sC2;
     const T* R = p.R ? reinterpret_cast<const T*>(p.R) + b1 * p.sR1 + b2 * p.sR2 : nullptr;
@@ -336,7 +329,7 @@ __device__ __forceinline__ void epilogue_cols(const GemmDev& p, f32x16 (&acc)[TM
 // lanes cover one 256-byte row of a 128-wide tile.  (epilogue_rows' direct 8-byte stores touch 32 different lines per
 // instruction; most GEMMs of this model have K <= 512, so the epilogue is a large part of their time.)
 template <typename H, int BM, int BN, int TM, int TN>
-__device__ __forceinline__ void epilogue_rows_lds(const GemmDev& p, f32x16 (&acc)[TM][TN], int b1, int b2, int m0, int n0, int wr, int wc,
+__device__ __forceinline__ void epilogue_rows_lds(const GemmDev& p, tc_f32x16 (&acc)[TM][TN], int b1, int b2, int m0, int n0, int wr, int wc,
                                                   int lane, bf16_t* stage_raw) {
     // (requesting the residual tile and the bias before the K loop and parking them in the staging tile was tried: the sampled
     //  workgroups' epilogue got shorter, the step did not -- 14.64 ms either way: other resident workgroups already cover the wait)
@@ -418,7 +411,7 @@ __device__ __forceinline__ void epilogue_rows_lds(const GemmDev& p, f32x16 (&acc
 // TC_FFN_EP form of the epilogue above: the d tile (prefetched before the K loop, rd) is parked beside the C staging tile, every
 // value becomes gp = v * GELU'(u) and the row sums for the LayerNorm backward leave through ffn.part2[row][bx].
 template <typename H, int BM, int BN, int TM, int TN>
-__device__ __forceinline__ void epilogue_rows_lds_ep(const GemmDev& p, f32x16 (&acc)[TM][TN], int b1, int m0, int n0, int wr, int wc, int lane,
+__device__ __forceinline__ void epilogue_rows_lds_ep(const GemmDev& p, tc_f32x16 (&acc)[TM][TN], int b1, int m0, int n0, int wr, int wc, int lane,
                                                      bf16_t* stage_raw, const uint4 rd0, const uint4 rd1, int bx, int gx) {
     constexpr int LDS_ = BN + 8, WM = BM / 2, WN = BN / 2, CPR = BN / 8;
     H* stage = reinterpret_cast<H*>(stage_raw);
@@ -541,7 +534,7 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmDev p) {
     const float* bet = FFN ? reinterpret_cast<const float*>(p.ffn.beta) + (long long)b1 * p.ffn.sPar1 : nullptr;
     const float2* fstat = FFN ? reinterpret_cast<const float2*>(p.ffn.stat) + (long long)b1 * p.ffn.sRow1 : nullptr;
 
-    f32x16 acc[TM][TN];
+    tc_f32x16 acc[TM][TN];
 #pragma unroll
     for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -704,16 +697,8 @@ __device__ __forceinline__ uint4 load_strip8(const bf16_t* base, int ld, int x, 
 // LDS as they come, [64][X+8], one 16-byte store per strip, and their MFMA fragments are gathered with the hardware transpose
 // read (ds_read_b64_tr_b16: lane i of a 16-lane group hands in the address of row i>>2 of a 4-row k block, columns 4(i&3).., and
 // receives column i of the block).  A transpose read touches 4 k-rows x 32 columns per 32 lanes; with 144-byte rows (36 banks)
-// rows p, p+4, p+8, p+12 start 16 banks apart, so the k-rows of every 16-k chunk are stored 4x4-transposed (gemm_krow) and each
-// read is conflict-free at the LDS footprint of the K-contiguous layout.  (Before: eight 2-byte LDS stores per strip.)
-__device__ __forceinline__ int gemm_krow(int k) { return (k & ~15) | ((k & 3) << 2) | ((k >> 2) & 3); }
-typedef short s16x4_t __attribute__((ext_vector_type(4)));
-typedef short s16x8_t __attribute__((ext_vector_type(8)));
-template <typename V8> __device__ __forceinline__ V8 ld_frag_tr(const bf16_t* lo, const bf16_t* hi) {
-    const s16x4_t a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4_t __attribute__((address_space(3)))*)(lo));
-    const s16x4_t b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4_t __attribute__((address_space(3)))*)(hi));
-    return __builtin_bit_cast(V8, (s16x8_t)__builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7));
-}
+// rows p, p+4, p+8, p+12 start 16 banks apart, so the k-rows of every 16-k chunk are stored 4x4-transposed (tc_krow) and each
+// read is conflict-free at the LDS footprint of the K-contiguous layout.  (Before: eight 2-byte LDS stores per strip.)  The read is tc_lds_tr8.
 
 // Body of one workgroup of the bf16 GEMM: (bx, by, bz) of a (gx, gy, *) grid.  The LDS buffers come from the caller so that the
 // two problems of a paired launch (gemm_pair_kernel) share one allocation.
@@ -763,7 +748,7 @@ __device__ __forceinline__ void gemm_bf16_body(const GemmDev& p, const int bx, c
     const bf16_t* A = reinterpret_cast<const bf16_t*>(p.A) + b1 * p.sA1 + b2 * p.sA2;
     const bf16_t* B = reinterpret_cast<const bf16_t*>(p.B) + b1 * p.sB1 + b2 * p.sB2;
 
-    f32x16 acc[TM][TN];
+    tc_f32x16 acc[TM][TN];
 #pragma unroll
     for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -804,8 +789,8 @@ __device__ __forceinline__ void gemm_bf16_body(const GemmDev& p, const int bx, c
     if constexpr (FFN == TC_FFN_LN_B) {
         const int col = n0 + (tid % (BN / 8)) * 8;
         const int cc = col + 7 < p.N ? col : 0;
-        bf8_unpack<H>(*reinterpret_cast<const uint4*>(gam + cc), fg);
-        bf8_unpack<H>(*reinterpret_cast<const uint4*>(bet + cc), fb);
+        tc_unpack16<H>(*reinterpret_cast<const uint4*>(gam + cc), fg);
+        tc_unpack16<H>(*reinterpret_cast<const uint4*>(bet + cc), fb);
     }
     if constexpr (FFN == TC_FFN_EP) {
         const bf16_t* dmap = reinterpret_cast<const bf16_t*>(p.ffn.d) + (long long)b1 * p.ffn.sRow1 * p.ffn.ldd;
@@ -849,7 +834,7 @@ __device__ __forceinline__ void gemm_bf16_body(const GemmDev& p, const int bx, c
         constexpr bool FAST = decltype(FT)::value;
         int x, k;
         float hg[8], hb[8];
-        if constexpr (FFN == TC_FFN_LN_A) { bf8_unpack<H>(rh[0], hg); bf8_unpack<H>(rh[1], hb); }
+        if constexpr (FFN == TC_FFN_LN_A) { tc_unpack16<H>(rh[0], hg); tc_unpack16<H>(rh[1], hb); }
 #pragma unroll
         for (int i = 0; i < SA; ++i) {
             const int f = tid + i * 256;
@@ -862,7 +847,7 @@ __device__ __forceinline__ void gemm_bf16_body(const GemmDev& p, const int bx, c
             if constexpr (FAST) { if (!strip_whole(x, k, p.M, kend, TA)) v = make_uint4(0u, 0u, 0u, 0u); }
             else if constexpr (FFN == TC_FFN_LN_A) { if (!strip_whole(x, k, p.M, kend, TA)) v = make_uint4(0u, 0u, 0u, 0u); }
             if (!TA) { const int row = f / (BK / 8), kq = f % (BK / 8); *reinterpret_cast<uint4*>(&as[row * LDT + kq * 8]) = v; }
-            else { const int kl = f / (BM / 8), mq = f % (BM / 8); *reinterpret_cast<uint4*>(&as[gemm_krow(kl) * PA + mq * 8]) = v; }
+            else { const int kl = f / (BM / 8), mq = f % (BM / 8); *reinterpret_cast<uint4*>(&as[tc_krow(kl) * PA + mq * 8]) = v; }
         }
         const bf16_t* Bk = b_base(k0);
 #pragma unroll
@@ -877,7 +862,7 @@ __device__ __forceinline__ void gemm_bf16_body(const GemmDev& p, const int bx, c
             if constexpr (FAST) { if (!strip_whole(x, k, p.N, kend, !TB)) v = make_uint4(0u, 0u, 0u, 0u); }
             else if constexpr (FFN == TC_FFN_LN_B) { if (!strip_whole(x, k, p.N, kend, !TB)) v = make_uint4(0u, 0u, 0u, 0u); }
             if (TB) { const int row = f / (BK / 8), kq = f % (BK / 8); *reinterpret_cast<uint4*>(&bs[row * LDT + kq * 8]) = v; }
-            else { const int kl = f / (BN / 8), nq = f % (BN / 8); *reinterpret_cast<uint4*>(&bs[gemm_krow(kl) * PB + nq * 8]) = v; }
+            else { const int kl = f / (BN / 8), nq = f % (BN / 8); *reinterpret_cast<uint4*>(&bs[tc_krow(kl) * PB + nq * 8]) = v; }
         }
     };
     float rsum = 0.f;
@@ -898,12 +883,12 @@ __device__ __forceinline__ void gemm_bf16_body(const GemmDev& p, const int bx, c
             V8 a[TM], b[TN];
 #pragma unroll
             for (int i = 0; i < TM; ++i) {
-                if constexpr (TA) a[i] = ld_frag_tr<V8>(ap + kk * PA + i * 32, ap + (kk + 1) * PA + i * 32);
+                if constexpr (TA) a[i] = tc_lds_tr8<V8>(ap + kk * PA + i * 32, ap + (kk + 1) * PA + i * 32);
                 else a[i] = *reinterpret_cast<const V8*>(ap + i * 32 * LDT + kk);
             }
 #pragma unroll
             for (int j = 0; j < TN; ++j) {
-                if constexpr (!TB) b[j] = ld_frag_tr<V8>(bp + kk * PB + j * 32, bp + (kk + 1) * PB + j * 32);
+                if constexpr (!TB) b[j] = tc_lds_tr8<V8>(bp + kk * PB + j * 32, bp + (kk + 1) * PB + j * 32);
                 else b[j] = *reinterpret_cast<const V8*>(bp + j * 32 * LDT + kk);
             }
 #pragma unroll

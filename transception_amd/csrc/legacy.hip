@@ -7,26 +7,8 @@ namespace {
 
 #define TC_GRID_STRIDE(i, n) for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < (unsigned)(n); i += gridDim.x * blockDim.x)
 
-// elements of T in one 16-byte piece
-template <typename T> struct Piece { static constexpr int N = 16 / (int)sizeof(T); };
-
-template <typename T> __device__ __forceinline__ void ld_piece(const T* p, float* v) {
-    const uint4 r = *reinterpret_cast<const uint4*>(p);
-    if constexpr (std::is_same<T, float>::value) {
-        v[0] = __uint_as_float(r.x); v[1] = __uint_as_float(r.y); v[2] = __uint_as_float(r.z); v[3] = __uint_as_float(r.w);
-    } else {
-        unpack2<T>(r.x, v[0], v[1]); unpack2<T>(r.y, v[2], v[3]); unpack2<T>(r.z, v[4], v[5]); unpack2<T>(r.w, v[6], v[7]);
-    }
-}
-template <typename T> __device__ __forceinline__ void st_piece(T* p, const float* v) {
-    uint4 r;
-    if constexpr (std::is_same<T, float>::value) {
-        r.x = __float_as_uint(v[0]); r.y = __float_as_uint(v[1]); r.z = __float_as_uint(v[2]); r.w = __float_as_uint(v[3]);
-    } else {
-        r.x = pack2<T>(v[0], v[1]); r.y = pack2<T>(v[2], v[3]); r.z = pack2<T>(v[4], v[5]); r.w = pack2<T>(v[6], v[7]);
-    }
-    *reinterpret_cast<uint4*>(p) = r;
-}
+template <typename T> __device__ __forceinline__ void ld_piece(const T* p, float* v) { tc_unpack16<T>(*reinterpret_cast<const uint4*>(p), v); }
+template <typename T> __device__ __forceinline__ void st_piece(T* p, const float* v) { *reinterpret_cast<uint4*>(p) = tc_pack16<T>(v); }
 
 // im2col of a k x k convolution (stride s, padding p, dilation d) over a token-major map x [B*H*W, Cin] (row stride ldx):
 // cols[(b, oy, ox), (ky*k + kx)*Cin + c] = x(b, oy*s - p + ky*d, ox*s - p + kx*d, c), zero outside the map.  Tap-major columns keep
@@ -34,7 +16,7 @@ template <typename T> __device__ __forceinline__ void st_piece(T* p, const float
 template <typename T>
 __global__ void im2col_dil_kernel(const T* __restrict__ x, int ldx, T* __restrict__ cols, int ldc, int B, int Cin, int H, int W, int Ho, int Wo,
                                   int k, int s, int p, int d) {
-    constexpr int V = Piece<T>::N;
+    constexpr int V = TcVec16<T>::N;
     const int cp = Cin / V, taps = k * k;
     const long long n = (long long)B * Ho * Wo * taps * cp;
     TC_GRID_STRIDE(i, n) {
@@ -55,7 +37,7 @@ __global__ void im2col_dil_kernel(const T* __restrict__ x, int ldx, T* __restric
 template <typename T>
 __global__ void col2im_dil_kernel(const T* __restrict__ dcols, int ldc, T* __restrict__ dx, int lddx, int B, int Cin, int H, int W, int Ho, int Wo,
                                   int k, int s, int p, int d, int accumulate) {
-    constexpr int V = Piece<T>::N;
+    constexpr int V = TcVec16<T>::N;
     const int cp = Cin / V;
     const long long n = (long long)B * H * W * cp;
     TC_GRID_STRIDE(i, n) {
@@ -96,7 +78,7 @@ __device__ __forceinline__ int nearest_src(int dst, float scale, int in) { retur
 template <typename T>
 __global__ void nearest_concat_fwd_kernel(const T* __restrict__ x1, long long sb1, const T* __restrict__ x2, long long sb2, int ldx,
                                           T* __restrict__ y, int ldy, int B, int H1, int W1, int Ho, int Wo, int C, float sy, float sx) {
-    constexpr int V = Piece<T>::N;
+    constexpr int V = TcVec16<T>::N;
     const int cp = C / V, cp2 = 2 * cp;
     const long long n = (long long)B * Ho * Wo * cp2;
     TC_GRID_STRIDE(i, n) {
@@ -113,7 +95,7 @@ __global__ void nearest_concat_fwd_kernel(const T* __restrict__ x1, long long sb
 template <typename T>
 __global__ void nearest_concat_bwd_kernel(const T* __restrict__ dy, int ldy, T* __restrict__ dx1, long long sb1, T* __restrict__ dx2, long long sb2,
                                           int lddx, int B, int H1, int W1, int Ho, int Wo, int C, float sy, float sx, int accumulate) {
-    constexpr int V = Piece<T>::N;
+    constexpr int V = TcVec16<T>::N;
     const int cp = C / V, n1 = H1 * W1, nt = n1 + Ho * Wo;
     const long long n = (long long)B * nt * cp;
     TC_GRID_STRIDE(i, n) {
@@ -171,7 +153,7 @@ extern "C" int tc_im2col_dil(const void* x, int ldx, void* cols, int ldc, int B,
     if (!x || !cols || B <= 0 || Cin <= 0 || (Cin & 7) || H <= 0 || W <= 0 || !dil_geometry(H, W, k, stride, pad, dil, Ho, Wo) || ldx < Cin
         || (ldx & 7) || ldc < k * k * Cin || (ldc & 7) || !al16(x) || !al16(cols))
         return TC_ERR_ARG;
-    TC_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((im2col_dil_kernel<T>), g1((long long)B * Ho * Wo * k * k * (Cin / Piece<T>::N)), dim3(256), 0, TC_S,
+    TC_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((im2col_dil_kernel<T>), g1((long long)B * Ho * Wo * k * k * (Cin / TcVec16<T>::N)), dim3(256), 0, TC_S,
                                                 (const T*)x, ldx, (T*)cols, ldc, B, Cin, H, W, Ho, Wo, k, stride, pad, dil));
     return tc_launch_status();
 }
@@ -182,7 +164,7 @@ extern "C" int tc_col2im_dil(const void* dcols, int ldc, void* dx, int lddx, int
     if (!dcols || !dx || B <= 0 || Cin <= 0 || (Cin & 7) || H <= 0 || W <= 0 || !dil_geometry(H, W, k, stride, pad, dil, Ho, Wo) || lddx < Cin
         || (lddx & 7) || ldc < k * k * Cin || (ldc & 7) || !al16(dcols) || !al16(dx))
         return TC_ERR_ARG;
-    TC_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((col2im_dil_kernel<T>), g1((long long)B * H * W * (Cin / Piece<T>::N)), dim3(256), 0, TC_S,
+    TC_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((col2im_dil_kernel<T>), g1((long long)B * H * W * (Cin / TcVec16<T>::N)), dim3(256), 0, TC_S,
                                                 (const T*)dcols, ldc, (T*)dx, lddx, B, Cin, H, W, Ho, Wo, k, stride, pad, dil, accumulate));
     return tc_launch_status();
 }
@@ -193,7 +175,7 @@ extern "C" int tc_nearest_concat_fwd(const void* x1, long long sb1, const void* 
         || (ldy & 7) || (sb1 & 7) || (sb2 & 7) || !al16(x1) || !al16(x2) || !al16(y))
         return TC_ERR_ARG;
     const float sy = (float)H1 / (float)Ho, sx = (float)W1 / (float)Wo;
-    TC_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((nearest_concat_fwd_kernel<T>), g1((long long)B * Ho * Wo * 2 * (C / Piece<T>::N)), dim3(256), 0, TC_S,
+    TC_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((nearest_concat_fwd_kernel<T>), g1((long long)B * Ho * Wo * 2 * (C / TcVec16<T>::N)), dim3(256), 0, TC_S,
                                                 (const T*)x1, sb1, (const T*)x2, sb2, ldx, (T*)y, ldy, B, H1, W1, Ho, Wo, C, sy, sx));
     return tc_launch_status();
 }
@@ -204,7 +186,7 @@ extern "C" int tc_nearest_concat_bwd(const void* dy, int ldy, void* dx1, long lo
         || (ldy & 7) || (sb1 & 7) || (sb2 & 7) || !al16(dy) || !al16(dx1) || !al16(dx2))
         return TC_ERR_ARG;
     const float sy = (float)H1 / (float)Ho, sx = (float)W1 / (float)Wo;
-    TC_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((nearest_concat_bwd_kernel<T>), g1((long long)B * (H1 * W1 + Ho * Wo) * (C / Piece<T>::N)), dim3(256),
+    TC_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((nearest_concat_bwd_kernel<T>), g1((long long)B * (H1 * W1 + Ho * Wo) * (C / TcVec16<T>::N)), dim3(256),
                                                 0, TC_S, (const T*)dy, ldy, (T*)dx1, sb1, (T*)dx2, sb2, lddx, B, H1, W1, Ho, Wo, C, sy, sx, accumulate));
     return tc_launch_status();
 }

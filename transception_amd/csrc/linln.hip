@@ -27,7 +27,6 @@ struct LinLnDev {
 
 #define LL_GLOAD128(dst, ptr) asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(dst) : "v"(ptr))
 #define LL_KEEP128(r) asm volatile("" : "+v"(r))
-#define LL_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
 template <int N> __device__ __forceinline__ void ll_wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N)); }
 
 template <typename T, int C, int RT, int NW>
@@ -88,7 +87,7 @@ __global__ __launch_bounds__(NW * 64) void lin_res_ln_kernel(LinLnDev p) {
         const int i = tid + NTH * j, n = i / CV, c8 = i - n * CV;
         *reinterpret_cast<u32x4*>(xs + n * PT + c8 * 8) = xr[j];
     }
-    LL_BARRIER();
+    TC_LDS_BARRIER();
     ll_wait_vm<(KS - KH) * NT + 1 + NXP>();                                     // first half of the weight panel
 #pragma unroll
     for (int i = 0; i < KH * NT; ++i) LL_KEEP128(wr[i]);
@@ -116,7 +115,7 @@ __global__ __launch_bounds__(NW * 64) void lin_res_ln_kernel(LinLnDev p) {
         const int i = tid + NTH * j, n = i / CV, c8 = i - n * CV;
         *reinterpret_cast<u32x4*>(rs + n * PT + c8 * 8) = rr[j];
     }
-    LL_BARRIER();                                              // (also: every wave is done reading x -- the tile takes t)
+    TC_LDS_BARRIER();                                              // (also: every wave is done reading x -- the tile takes t)
     // t = acc + bias + residual, rounded; the lane's channels: tile t_, register group gq -> ch0 + t_ * 32 + 8 gq + 4 hh + (0..3)
     const bool has_res = p.res != nullptr;
     float s1 = 0.f;
@@ -140,7 +139,7 @@ __global__ __launch_bounds__(NW * 64) void lin_res_ln_kernel(LinLnDev p) {
     // row statistics: the lane's values + its partner half (same row, other 16 channels of every tile) + the other channel blocks (other waves)
     s1 += __shfl_xor(s1, 32, 64);
     if (hh == 0) st[cb * RT + tok] = s1;
-    LL_BARRIER();
+    TC_LDS_BARRIER();
     float mean = 0.f;
 #pragma unroll
     for (int q = 0; q < CB; ++q) mean += st[q * RT + tok];
@@ -158,7 +157,7 @@ __global__ __launch_bounds__(NW * 64) void lin_res_ln_kernel(LinLnDev p) {
         const int i = tid + NTH * j, n = i / CV, c8 = i - n * CV;
         if (n < nrow) *reinterpret_cast<u32x4*>(reinterpret_cast<T*>(p.t) + (row0 + n) * p.ldt + c8 * 8) = *reinterpret_cast<const u32x4*>(xs + n * PT + c8 * 8);
     }
-    LL_BARRIER();
+    TC_LDS_BARRIER();
     float var = 0.f;
 #pragma unroll
     for (int q = 0; q < CB; ++q) var += st[(CB + q) * RT + tok];
@@ -175,7 +174,7 @@ __global__ __launch_bounds__(NW * 64) void lin_res_ln_kernel(LinLnDev p) {
             const float o2 = (acc[t][4 * gq + 2] - mean) * rstd * gm.z + bt.z, o3 = (acc[t][4 * gq + 3] - mean) * rstd * gm.w + bt.w;
             *reinterpret_cast<uint2*>(rs + tok * PT + c) = make_uint2(pack2<T>(o0, o1), pack2<T>(o2, o3));
         }
-    LL_BARRIER();
+    TC_LDS_BARRIER();
 #pragma unroll
     for (int j = 0; j < NXP; ++j) {
         const int i = tid + NTH * j, n = i / CV, c8 = i - n * CV;

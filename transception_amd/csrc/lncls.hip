@@ -38,9 +38,6 @@ inline bool ps_map(PsMap& m, int p, int H, int W, long long rows) {
     return true;
 }
 
-template <typename T> __device__ __forceinline__ void up8(const uint4& r, float* o) {
-    unpack2<T>(r.x, o[0], o[1]); unpack2<T>(r.y, o[2], o[3]); unpack2<T>(r.z, o[4], o[5]); unpack2<T>(r.w, o[6], o[7]);
-}
 
 constexpr int LC_C = 64, LC_GS = 8, LC_RPB = 256 / LC_GS;      // channels; lanes per row; rows per workgroup pass
 
@@ -59,8 +56,8 @@ __global__ __launch_bounds__(256) void ln_cls_fwd_kernel(const T* __restrict__ x
     float* wsh = reinterpret_cast<float*>(wsh4);
     for (int i = threadIdx.x; i < NC * LC_C; i += 256) wsh[i] = ldf<T>(Wc + i);
     float g[8], b[8], bias[NC];
-    up8<T>(*reinterpret_cast<const uint4*>(gamma + gl * 8), g);
-    up8<T>(*reinterpret_cast<const uint4*>(beta + gl * 8), b);
+    tc_unpack16<T>(*reinterpret_cast<const uint4*>(gamma + gl * 8), g);
+    tc_unpack16<T>(*reinterpret_cast<const uint4*>(beta + gl * 8), b);
 #pragma unroll
     for (int c = 0; c < NC; ++c) bias[c] = ldf<T>(bc + c);
     __syncthreads();
@@ -75,7 +72,7 @@ __global__ __launch_bounds__(256) void ln_cls_fwd_kernel(const T* __restrict__ x
         for (int q = 0; q < RP; ++q) {
             const long long r = r0 + q * LC_RPB + gi;
             float v[8];
-            up8<T>(raw[q], v);
+            tc_unpack16<T>(raw[q], v);
             float s = ((v[0] + v[1]) + (v[2] + v[3])) + ((v[4] + v[5]) + (v[6] + v[7]));
             s = tc_group_sum<LC_GS>(s);
             const float mu = s * (1.0f / LC_C);
@@ -109,7 +106,7 @@ __global__ __launch_bounds__(256) void ln_cls_fwd_kernel(const T* __restrict__ x
                             float o[8];
 #pragma unroll
                             for (int e = 0; e < 8; ++e) o[e] = 8 * q + e < NC ? acc[(8 * q + e) < NC ? 8 * q + e : 0] : 0.f;
-                            *reinterpret_cast<uint4*>(lp + 8 * q) = make_uint4(pack2<T>(o[0], o[1]), pack2<T>(o[2], o[3]), pack2<T>(o[4], o[5]), pack2<T>(o[6], o[7]));
+                            *reinterpret_cast<uint4*>(lp + 8 * q) = tc_pack16<T>(o);
                         }
                 } else {
 #pragma unroll
@@ -141,8 +138,8 @@ __global__ __launch_bounds__(256, 2) void ln_cls_bwd_kernel(const T* __restrict_
     const int gl = threadIdx.x % LC_GS, gi = threadIdx.x / LC_GS, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     for (int i = threadIdx.x; i < NC * LC_C; i += 256) wsh[i] = ldf<T>(Wc + i);
     float g[8], b[8];
-    up8<T>(*reinterpret_cast<const uint4*>(gamma + gl * 8), g);
-    up8<T>(*reinterpret_cast<const uint4*>(beta + gl * 8), b);
+    tc_unpack16<T>(*reinterpret_cast<const uint4*>(gamma + gl * 8), g);
+    tc_unpack16<T>(*reinterpret_cast<const uint4*>(beta + gl * 8), b);
     float dg[8], db[8], dw[NC][8], dc[NC];
 #pragma unroll
     for (int e = 0; e < 8; ++e) { dg[e] = 0.f; db[e] = 0.f; }
@@ -178,11 +175,11 @@ __global__ __launch_bounds__(256, 2) void ln_cls_bwd_kernel(const T* __restrict_
         const bool ok = r < rows;
         float v[8], d[NC];
         const float mu_ = nx0.mu, rs_ = nx0.rs;
-        up8<T>(nx0.raw, v);
+        tc_unpack16<T>(nx0.raw, v);
         if constexpr (AL) {
             float t8[8 * NQ];
 #pragma unroll
-            for (int q = 0; q < NQ; ++q) up8<T>(nx0.dq[q], t8 + 8 * q);
+            for (int q = 0; q < NQ; ++q) tc_unpack16<T>(nx0.dq[q], t8 + 8 * q);
 #pragma unroll
             for (int c = 0; c < NC; ++c) d[c] = ok ? t8[c] : 0.f;
         } else {
@@ -222,7 +219,7 @@ __global__ __launch_bounds__(256, 2) void ln_cls_bwd_kernel(const T* __restrict_
 #pragma unroll
             for (int e = 0; e < 8; ++e) o[e] = rs_ * (dxn[e] - s1 - xh[e] * s2);
             const long long dxo = ps_row_off((int)r, map, lddx, LC_C) + gl * 8;
-            *reinterpret_cast<uint4*>(dx + dxo) = make_uint4(pack2<T>(o[0], o[1]), pack2<T>(o[2], o[3]), pack2<T>(o[4], o[5]), pack2<T>(o[6], o[7]));
+            *reinterpret_cast<uint4*>(dx + dxo) = tc_pack16<T>(o);
         }
     }
     // fold the lanes that own the same eight channels (lane bits 3..5), then the four waves through LDS; one partial per workgroup

@@ -12,8 +12,6 @@
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
 struct FfnFwdDev {
     const void* x; const void* w1; const void* b1; const void* wd; const void* bd; const void* gamma; const void* beta;
     const void* w2; const void* b2; const void* res; void* out; void* h; void* d; void* a; float* stat;
@@ -38,13 +36,6 @@ template <int C> struct FfnCfg {
     static_assert((size_t)IPMAX * PO * 4 <= (size_t)MPMAX * PH * 2, "the fp32 output stage aliases the hidden tile");
     static_assert(smem <= 160 * 1024, "LDS");
 };
-
-template <typename H> __device__ __forceinline__ void up8(const uint4& r, float* o) {
-    unpack2<H>(r.x, o[0], o[1]); unpack2<H>(r.y, o[2], o[3]); unpack2<H>(r.z, o[4], o[5]); unpack2<H>(r.w, o[6], o[7]);
-}
-template <typename H> __device__ __forceinline__ uint4 pk8(const float* o) {
-    return make_uint4(pack2<H>(o[0], o[1]), pack2<H>(o[2], o[3]), pack2<H>(o[4], o[5]), pack2<H>(o[6], o[7]));
-}
 
 #ifdef TC_FFNF_TIMING
 // phase stamps (experiment builds only, scripts/exp/ffnb_timing.py --fwd): thread 0 of the first 16 workgroups of weight group 0
@@ -169,7 +160,7 @@ __global__ __launch_bounds__(512, 2) void ffn_fused_fwd_kernel(const FfnFwdDev p
             uint4 v = ok ? xr[i] : make_uint4(0u, 0u, 0u, 0u);
             if constexpr (PRE) {                                   // LayerNorm over the pixel's C channels: XC consecutive lanes hold one pixel
                 float f[8], gm[8], bt[8];
-                up8<H>(v, f);
+                tc_unpack16<H>(v, f);
 #pragma unroll
                 for (int e = 0; e < 8; ++e) {                      // (parameter vectors sit at any 2-byte offset of the flat buffer)
                     gm[e] = ldf<H>(reinterpret_cast<const H*>(p.pre_g) + wo + cg * 8 + e);
@@ -187,7 +178,7 @@ __global__ __launch_bounds__(512, 2) void ffn_fused_fwd_kernel(const FfnFwdDev p
                 const float rstd = rsqrtf(q2 * (1.0f / C) + p.pre_eps);
 #pragma unroll
                 for (int e = 0; e < 8; ++e) f[e] = f[e] * rstd * gm[e] + bt[e];
-                v = pk8<H>(f);
+                v = tc_pack16<H>(f);
             }
             if (s < MT * 32 * XC) *reinterpret_cast<uint4*>(xs + tc_mul24(pix, PX) + cg * 8) = v;
         }
@@ -222,7 +213,7 @@ __global__ __launch_bounds__(512, 2) void ffn_fused_fwd_kernel(const FfnFwdDev p
         if (more) xfetch(tidx + gridDim.x);                      // lands under this tile's arithmetic
         // ---- fc1 on the haloed tile, this wave's CW hidden channels; rows outside the image are the convolution's zero padding
         for (int mi = 0; mi < MT; ++mi) {
-            f32x16 acc[NT1];
+            tc_f32x16 acc[NT1];
 #pragma unroll
             for (int nt = 0; nt < NT1; ++nt)
 #pragma unroll
@@ -265,11 +256,6 @@ __global__ __launch_bounds__(512, 2) void ffn_fused_fwd_kernel(const FfnFwdDev p
             const int nitems = min(nitems_all - it00, NRD * 64);
             int yq[NRD], xq[NRD];
             tc_f32x2 o[NRD][2][4];                               // packed fp32 pairs: two channels per issue slot
-            auto up8p = [&](const uint4& r, tc_f32x2* v) __attribute__((always_inline)) {
-                float a, b;
-                unpack2<H>(r.x, a, b); v[0] = tc_f32x2{a, b}; unpack2<H>(r.y, a, b); v[1] = tc_f32x2{a, b};
-                unpack2<H>(r.z, a, b); v[2] = tc_f32x2{a, b}; unpack2<H>(r.w, a, b); v[3] = tc_f32x2{a, b};
-            };
             {
                 const float4 ba = *reinterpret_cast<const float4*>(wtap + 9 * C4 + chw), bb = *reinterpret_cast<const float4*>(wtap + 9 * C4 + chw + 4);
 #pragma unroll
@@ -294,7 +280,7 @@ __global__ __launch_bounds__(512, 2) void ffn_fused_fwd_kernel(const FfnFwdDev p
                     if (q * 64 >= nitems) break;
                     tc_f32x2 in[4][4];
 #pragma unroll
-                    for (int dx = 0; dx < 4; ++dx) up8p(*reinterpret_cast<const uint4*>(hs + tc_mul24(tc_mad24(yq[q] + dy, HW2, xq[q] + dx), PH) + chw), in[dx]);
+                    for (int dx = 0; dx < 4; ++dx) tc_unpack16v<H>(*reinterpret_cast<const uint4*>(hs + tc_mul24(tc_mad24(yq[q] + dy, HW2, xq[q] + dx), PH) + chw), in[dx]);
 #pragma unroll
                     for (int dx = 0; dx < 3; ++dx)
 #pragma unroll
@@ -330,8 +316,7 @@ __global__ __launch_bounds__(512, 2) void ffn_fused_fwd_kernel(const FfnFwdDev p
 #pragma unroll
                 for (int r = 0; r < 2; ++r)
                     if (live && x0 + r < TW)
-                        *reinterpret_cast<uint4*>(hs + tc_mul24(tc_mad24(y, HW2, x0 + r), PH) + chw) =
-                            make_uint4(pack2<H>(o[q][r][0].x, o[q][r][0].y), pack2<H>(o[q][r][1].x, o[q][r][1].y), pack2<H>(o[q][r][2].x, o[q][r][2].y), pack2<H>(o[q][r][3].x, o[q][r][3].y));
+                        *reinterpret_cast<uint4*>(hs + tc_mul24(tc_mad24(y, HW2, x0 + r), PH) + chw) = tc_pack16v<H>(o[q][r]);
             }
             }
         }
@@ -370,14 +355,14 @@ __global__ __launch_bounds__(512, 2) void ffn_fused_fwd_kernel(const FfnFwdDev p
                 const uint4 dv = *reinterpret_cast<const uint4*>(cell);
                 const float2 st = fst[q];
                 float v[8];
-                up8<H>(dv, v);
+                tc_unpack16<H>(dv, v);
 #pragma unroll
                 for (int e = 0; e < 8; e += 2) {
                     const tc_f32x2 xv = {v[e], v[e + 1]}, gv = {gm[e], gm[e + 1]}, bv = {bt[e], bt[e + 1]};
                     const tc_f32x2 u = gelu_poly2((xv - st.x) * st.y * gv + bv);
                     v[e] = u.x; v[e + 1] = u.y;
                 }
-                const uint4 av = pk8<H>(v);
+                const uint4 av = tc_pack16<H>(v);
                 *reinterpret_cast<uint4*>(cell) = av;
                 if (oh0 + y < Himg && ow0 + x < Wimg) {
                     const long long ro = (ibase + (long long)(oh0 + y) * Wimg + ow0 + x) * C4 + cgx * 8;
@@ -390,7 +375,7 @@ __global__ __launch_bounds__(512, 2) void ffn_fused_fwd_kernel(const FfnFwdDev p
         __syncthreads();
         FSTAMP(6);
         // ---- fc2: this wave's 32 pixels x 32 output channels over K = 4C
-        f32x16 oacc;
+        tc_f32x16 oacc;
 #pragma unroll
         for (int r = 0; r < 16; ++r) oacc[r] = 0.f;
         if (mt2 < p.MT2) {
@@ -440,11 +425,11 @@ __global__ __launch_bounds__(512, 2) void ffn_fused_fwd_kernel(const FfnFwdDev p
                 float v[8] = {v0.x + b2v[0], v0.y + b2v[1], v0.z + b2v[2], v0.w + b2v[3], v1.x + b2v[4], v1.y + b2v[5], v1.z + b2v[6], v1.w + b2v[7]};
                 if (RES) {
                     float rv[8];
-                    up8<H>(*reinterpret_cast<const uint4*>(RES + rg * p.ldr + cg * 8), rv);
+                    tc_unpack16<H>(*reinterpret_cast<const uint4*>(RES + rg * p.ldr + cg * 8), rv);
 #pragma unroll
                     for (int e = 0; e < 8; ++e) v[e] += rv[e];
                 }
-                *reinterpret_cast<uint4*>(OUT + rg * p.ldo + cg * 8) = pk8<H>(v);
+                *reinterpret_cast<uint4*>(OUT + rg * p.ldo + cg * 8) = tc_pack16<H>(v);
             }
         }
         FSTAMP(10);

@@ -13,24 +13,6 @@
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef short s16x4_t __attribute__((ext_vector_type(4)));
-typedef short s16x8_t __attribute__((ext_vector_type(8)));
-
-// k-row permutation of the LDS tiles whose rows are the reduction index of a transpose-read operand (gemm.hip, gemm_krow)
-__device__ __forceinline__ int krow(int k) { return (k & ~15) | ((k & 3) << 2) | ((k >> 2) & 3); }
-template <typename V8> __device__ __forceinline__ V8 ld_tr(const bf16_t* lo, const bf16_t* hi) {
-    const s16x4_t a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4_t __attribute__((address_space(3)))*)(lo));
-    const s16x4_t b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4_t __attribute__((address_space(3)))*)(hi));
-    return __builtin_bit_cast(V8, (s16x8_t)__builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7));
-}
-template <typename H> __device__ __forceinline__ void up8(const uint4& r, float* o) {
-    unpack2<H>(r.x, o[0], o[1]); unpack2<H>(r.y, o[2], o[3]); unpack2<H>(r.z, o[4], o[5]); unpack2<H>(r.w, o[6], o[7]);
-}
-template <typename H> __device__ __forceinline__ uint4 pk8(const float* o) {
-    return make_uint4(pack2<H>(o[0], o[1]), pack2<H>(o[2], o[3]), pack2<H>(o[4], o[5]), pack2<H>(o[6], o[7]));
-}
-
 // per-(weight group, workgroup) partial sums, fp32: launch 1 [dW2 C x 4C][db2 C][dgamma 4C][dbeta 4C], launch 2 [dW1 4C x C][db1 4C][dwd 4C x 9][dbd 4C]
 template <int C> struct BwdPart {
     static constexpr int C4 = 4 * C;
@@ -148,14 +130,14 @@ __global__ __launch_bounds__(512, 2) void ffn_bwd_ln_kernel(const FfnBwdDev p) {
 #pragma unroll
         for (int i = 0; i < ND; ++i) {
             const int s = tid + i * NTH, px = s / HC, cg = s - px * HC;
-            *reinterpret_cast<uint4*>(dt + krow(px) * PH + cg * 8) = (r0 + px < M) ? dr[i] : make_uint4(0u, 0u, 0u, 0u);
+            *reinterpret_cast<uint4*>(dt + tc_krow(px) * PH + cg * 8) = (r0 + px < M) ? dr[i] : make_uint4(0u, 0u, 0u, 0u);
         }
 #pragma unroll
         for (int i = 0; i < NY; ++i) {
             const int s = tid + i * NTH, px = s / XC, cg = s - px * XC;
             if (s < P * XC) {
                 const uint4 v = (r0 + px < M) ? yr[i] : make_uint4(0u, 0u, 0u, 0u);
-                *reinterpret_cast<uint4*>(yt + krow(px) * PX + cg * 8) = v;
+                *reinterpret_cast<uint4*>(yt + tc_krow(px) * PX + cg * 8) = v;
             }
         }
         if (tid < P) fst[tid] = (r0 + tid < M) ? sr : make_float2(0.f, 0.f);
@@ -166,7 +148,7 @@ __global__ __launch_bounds__(512, 2) void ffn_bwd_ln_kernel(const FfnBwdDev p) {
     for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
         for (int r = 0; r < 16; ++r) { dgam[nt][r] = 0.f; dbet[nt][r] = 0.f; }
-    f32x16 acc2[OB][NT];
+    tc_f32x16 acc2[OB][NT];
 #pragma unroll
     for (int ob = 0; ob < OB; ++ob)
 #pragma unroll
@@ -191,13 +173,13 @@ __global__ __launch_bounds__(512, 2) void ffn_bwd_ln_kernel(const FfnBwdDev p) {
 #pragma unroll
         for (int pb = 0; pb < P / 32; ++pb) {
             const int px = pb * 32 + l31;
-            f32x16 acc[NT];
+            tc_f32x16 acc[NT];
 #pragma unroll
             for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) acc[nt][r] = 0.f;
             {
-                const bf16_t* yp = yt + krow(px) * PX + 8 * hh;
+                const bf16_t* yp = yt + tc_krow(px) * PX + 8 * hh;
 #pragma unroll
                 for (int kk = 0; kk < KK; ++kk) {
                     const V8 yv = *reinterpret_cast<const V8*>(yp + kk * 16);
@@ -206,7 +188,7 @@ __global__ __launch_bounds__(512, 2) void ffn_bwd_ln_kernel(const FfnBwdDev p) {
                         acc[nt] = TcHalf<H>::mfma(*reinterpret_cast<const V8*>(w2t + (wave * CW + nt * 32 + l31) * PX + kk * 16 + 8 * hh), yv, acc[nt]);
                 }
             }
-            bf16_t* rowp = dt + krow(px) * PH;
+            bf16_t* rowp = dt + tc_krow(px) * PH;
             float* ggp = ggs + px * PGG;
             const float2 st = fst[px];
             float s1 = 0.f, s2 = 0.f;
@@ -227,7 +209,7 @@ __global__ __launch_bounds__(512, 2) void ffn_bwd_ln_kernel(const FfnBwdDev p) {
                         const tc_f32x2 xh = (x2 - st.x) * st.y;
                         const tc_f32x2 u = xh * g2 + be2;
                         tc_f32x2 pdf;
-                        const tc_f32x2 cdf = gelu_cdf_pdf2_fast(u, pdf);
+                        const tc_f32x2 cdf = gelu_cdf_pdf2<true>(u, pdf);
                         const tc_f32x2 a2 = u * cdf, gpr = cdf + u * pdf;
                         const tc_f32x2 gpre = {acc[nt][4 * gq + e], acc[nt][4 * gq + e + 1]};
                         const tc_f32x2 gp = gpre * gpr;
@@ -257,15 +239,15 @@ __global__ __launch_bounds__(512, 2) void ffn_bwd_ln_kernel(const FfnBwdDev p) {
             const int rr = 16 * ks + 2 * hh + 4 * (gi >> 2), cc = 16 * gq2 + 4 * (gi & 3);
             V8 bfr[NT], afr[OB];
 #pragma unroll
-            for (int nt = 0; nt < NT; ++nt) bfr[nt] = ld_tr<V8>(dt + rr * PH + wave * CW + nt * 32 + cc, dt + (rr + 1) * PH + wave * CW + nt * 32 + cc);
+            for (int nt = 0; nt < NT; ++nt) bfr[nt] = tc_lds_tr8<V8>(dt + rr * PH + wave * CW + nt * 32 + cc, dt + (rr + 1) * PH + wave * CW + nt * 32 + cc);
 #pragma unroll
-            for (int ob = 0; ob < OB; ++ob) afr[ob] = ld_tr<V8>(yt + rr * PX + ob * 32 + cc, yt + (rr + 1) * PX + ob * 32 + cc);
+            for (int ob = 0; ob < OB; ++ob) afr[ob] = tc_lds_tr8<V8>(yt + rr * PX + ob * 32 + cc, yt + (rr + 1) * PX + ob * 32 + cc);
             if (wave == 0) {
 #pragma unroll
                 for (int ob = 0; ob < OB; ++ob) {
                     const uint4 q = __builtin_bit_cast(uint4, afr[ob]);
                     float f[8];
-                    up8<H>(q, f);
+                    tc_unpack16<H>(q, f);
                     db2p[ob] += ((f[0] + f[1]) + (f[2] + f[3])) + ((f[4] + f[5]) + (f[6] + f[7]));
                 }
             }
@@ -279,7 +261,7 @@ __global__ __launch_bounds__(512, 2) void ffn_bwd_ln_kernel(const FfnBwdDev p) {
 #pragma unroll
         for (int pb = 0; pb < P / 32; ++pb) {
             const int px = pb * 32 + l31;
-            bf16_t* rowp = dt + krow(px) * PH;
+            bf16_t* rowp = dt + tc_krow(px) * PH;
             const float2 st = fst[px];
             float S1 = 0.f, S2 = 0.f;
 #pragma unroll
@@ -309,7 +291,7 @@ __global__ __launch_bounds__(512, 2) void ffn_bwd_ln_kernel(const FfnBwdDev p) {
 #pragma unroll
         for (int i = 0; i < ND; ++i) {
             const int s = tid + i * NTH, px = s / HC, cg = s - px * HC;
-            if (r0 + px < M) *reinterpret_cast<uint4*>(GD + (r0 + px) * C4 + cg * 8) = *reinterpret_cast<const uint4*>(dt + krow(px) * PH + cg * 8);
+            if (r0 + px < M) *reinterpret_cast<uint4*>(GD + (r0 + px) * C4 + cg * 8) = *reinterpret_cast<const uint4*>(dt + tc_krow(px) * PH + cg * 8);
         }
         BSTAMP(9);
         __syncthreads();
@@ -430,7 +412,7 @@ __global__ __launch_bounds__(512, 2) void ffn_bwd_dw_kernel(const FfnBwdDev p) {
 #pragma unroll
         for (int k = 0; k < NW1; ++k) {                            // W1 stays in LDS for the whole launch
             const int s = tid + k * NTH, r = s / XC, cg = s - r * XC;
-            if (s < C4 * XC) *reinterpret_cast<uint4*>(w1s + krow(r) * PX + cg * 8) = w1v[k];
+            if (s < C4 * XC) *reinterpret_cast<uint4*>(w1s + tc_krow(r) * PX + cg * 8) = w1v[k];
         }
     };
 
@@ -470,7 +452,7 @@ __global__ __launch_bounds__(512, 2) void ffn_bwd_dw_kernel(const FfnBwdDev p) {
             uint4 v = ok ? xr[i] : make_uint4(0u, 0u, 0u, 0u);
             if constexpr (PRE) {                                    // n2 = LayerNorm(x): XC consecutive lanes hold one pixel
                 float f[8];
-                up8<H>(v, f);
+                tc_unpack16<H>(v, f);
                 float sm = 0.f;
 #pragma unroll
                 for (int e = 0; e < 8; ++e) sm += f[e];
@@ -483,7 +465,7 @@ __global__ __launch_bounds__(512, 2) void ffn_bwd_dw_kernel(const FfnBwdDev p) {
                 const float rstd = rsqrtf(q2 * (1.0f / C) + p.pre_eps);
 #pragma unroll
                 for (int e = 0; e < 8; ++e) f[e] = f[e] * rstd * pre[cg * 8 + e] + pre[C + cg * 8 + e];
-                v = pk8<H>(f);
+                v = tc_pack16<H>(f);
             }
             if (pix < HP) *reinterpret_cast<uint4*>(xs + tc_mul24(pix, PX) + cg * 8) = v;
         }
@@ -514,7 +496,7 @@ __global__ __launch_bounds__(512, 2) void ffn_bwd_dw_kernel(const FfnBwdDev p) {
     // halo-tile row of inner pixel q (row-major over the TH x TW inner pixels)
     auto hrow = [&](int q) __attribute__((always_inline)) { q = tc_opaque(q); const int y = sdiv(q, dTW); return tc_mad24(y + 1, HW2, smod(q, y, dTW) + 1); };
 
-    f32x16 accw[NCH];
+    tc_f32x16 accw[NCH];
     tc_f32x2 aw[NCH][11];                                            // this thread's sums over (its row of every tile) x (its channel pair of chunk c): dwd taps, dbd, db1
 #pragma unroll
     for (int c = 0; c < NCH; ++c) {
@@ -535,7 +517,7 @@ __global__ __launch_bounds__(512, 2) void ffn_bwd_dw_kernel(const FfnBwdDev p) {
         tile_org(tidx, b, oh0, ow0);
         const bool more = tidx + (int)gridDim.x < p.ntiles;
         xput(tidx);
-        f32x16 accx;
+        tc_f32x16 accx;
 #pragma unroll
         for (int r = 0; r < 16; ++r) accx[r] = 0.f;
 #pragma unroll
@@ -549,9 +531,9 @@ __global__ __launch_bounds__(512, 2) void ffn_bwd_dw_kernel(const FfnBwdDev p) {
             {
                 V8 af[KK1];
 #pragma unroll
-                for (int kk = 0; kk < KK1; ++kk) af[kk] = *reinterpret_cast<const V8*>(w1s + krow(c * CH + cb * 32 + l31) * PX + kk * 16 + 8 * hh);
+                for (int kk = 0; kk < KK1; ++kk) af[kk] = *reinterpret_cast<const V8*>(w1s + tc_krow(c * CH + cb * 32 + l31) * PX + kk * 16 + 8 * hh);
                 for (int mi = nb; mi < MT; mi += 2) {               // (one block at a time: three interleaved chains cost 36 spilled registers)
-                    f32x16 acc;
+                    tc_f32x16 acc;
 #pragma unroll
                     for (int gq = 0; gq < 4; ++gq) {
                         const float4 bv = *reinterpret_cast<const float4*>(b1s + c * CH + cb * 32 + 8 * gq + 4 * hh);
@@ -654,15 +636,15 @@ __global__ __launch_bounds__(512, 2) void ffn_bwd_dw_kernel(const FfnBwdDev p) {
 #pragma unroll
                 for (int kk = 0; kk < KKC; ++kk) {
                     const bf16_t* wp = w1s + (c * CH + 16 * kk + 2 * hh + 4 * (gi >> 2)) * PX + nb * 32 + 16 * gq2 + 4 * (gi & 3);
-                    accx = TcHalf<H>::mfma(ld_tr<V8>(wp, wp + PX), *reinterpret_cast<const V8*>(dp + kk * 16), accx);
+                    accx = TcHalf<H>::mfma(tc_lds_tr8<V8>(wp, wp + PX), *reinterpret_cast<const V8*>(dp + kk * 16), accx);
                 }
             }
 #pragma unroll
             for (int ks = 0; ks < K::IPMAX / 16; ++ks) {                // (steps beyond the tile's pixels multiply the zero row)
                 const int qlo = 16 * ks + 8 * hh + (gi >> 2), qhi = qlo + 4, cc = 16 * gq2 + 4 * (gi & 3);
                 const int rlo = qlo < IP ? hrow(qlo) : -1, rhi = qhi < IP ? hrow(qhi) : -1;
-                const V8 av = ld_tr<V8>(hs + tc_mul24(rlo < 0 ? MPMAX : rlo, PG) + cb * 32 + cc, hs + tc_mul24(rhi < 0 ? MPMAX : rhi, PG) + cb * 32 + cc);
-                const V8 bv = ld_tr<V8>(xs + tc_mul24(rlo < 0 ? 0 : rlo, PX) + nb * 32 + cc, xs + tc_mul24(rhi < 0 ? 0 : rhi, PX) + nb * 32 + cc);
+                const V8 av = tc_lds_tr8<V8>(hs + tc_mul24(rlo < 0 ? MPMAX : rlo, PG) + cb * 32 + cc, hs + tc_mul24(rhi < 0 ? MPMAX : rhi, PG) + cb * 32 + cc);
+                const V8 bv = tc_lds_tr8<V8>(xs + tc_mul24(rlo < 0 ? 0 : rlo, PX) + nb * 32 + cc, xs + tc_mul24(rhi < 0 ? 0 : rhi, PX) + nb * 32 + cc);
                 accw[c] = TcHalf<H>::mfma(av, bv, accw[c]);
             }
             BSTAMP(9);
@@ -699,11 +681,11 @@ __global__ __launch_bounds__(512, 2) void ffn_bwd_dw_kernel(const FfnBwdDev p) {
                 H* dst = dxb + (long long)((oh0 + y) * Wimg + ow0 + x) * p.lddx + cg * 8;
                 if (p.acc_dx) {
                     float o[8];
-                    up8<H>(*reinterpret_cast<const uint4*>(dst), o);
+                    tc_unpack16<H>(*reinterpret_cast<const uint4*>(dst), o);
 #pragma unroll
                     for (int e = 0; e < 8; ++e) v[e] += o[e];
                 }
-                *reinterpret_cast<uint4*>(dst) = pk8<H>(v);
+                *reinterpret_cast<uint4*>(dst) = tc_pack16<H>(v);
             }
         } else {
             H* dxb = DX + (long long)b * imgpix * p.lddx;
@@ -722,7 +704,7 @@ __global__ __launch_bounds__(512, 2) void ffn_bwd_dw_kernel(const FfnBwdDev p) {
                 if constexpr (PRE) {
                     // v = d(n2); the gradient of x = LayerNorm backward of it, from the raw row (still in L2) -- statistics recomputed
                     float f[8];
-                    up8<H>(xraw[k], f);
+                    tc_unpack16<H>(xraw[k], f);
                     float sm = 0.f;
 #pragma unroll
                     for (int e = 0; e < 8; ++e) sm += f[e];
@@ -750,11 +732,11 @@ __global__ __launch_bounds__(512, 2) void ffn_bwd_dw_kernel(const FfnBwdDev p) {
                     H* dst = dxb + pix * p.lddx + cg * 8;
                     if (p.acc_dx) {
                         float o[8];
-                        up8<H>(*reinterpret_cast<const uint4*>(dst), o);
+                        tc_unpack16<H>(*reinterpret_cast<const uint4*>(dst), o);
 #pragma unroll
                         for (int e = 0; e < 8; ++e) v[e] += o[e];
                     }
-                    *reinterpret_cast<uint4*>(dst) = pk8<H>(v);
+                    *reinterpret_cast<uint4*>(dst) = tc_pack16<H>(v);
                 }
             }
             if constexpr (PRE) {                                    // lanes of one channel group (stride XC) fold, then one LDS add per wave and channel

@@ -34,7 +34,6 @@ __device__ __forceinline__ long long ln_row_off(int row, const LnMap& m, int ld,
     return ((long long)(b * m.H + oh / m.p) * m.W + ow / m.p) * ld + ((oh % m.p) * m.p + ow % m.p) * C;
 }
 
-template <int GS> __device__ __forceinline__ float group_sum(float v) { return tc_group_sum<GS>(v); }
 
 // RPT consecutive rows per lane group and iteration: their loads are all issued before the first reduction (narrow rows are
 // 128-256 bytes: one row per group per iteration left a single 8-byte load per lane in flight and ran at ~2 TB/s).
@@ -76,7 +75,7 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const T* __restrict__ x, in
             float s = 0.f;
 #pragma unroll
             for (int i = 0; i < NV; ++i) s += v[r][i].x + v[r][i].y + v[r][i].z + v[r][i].w;
-            mu[r] = group_sum<GS>(s) * invC;
+            mu[r] = tc_group_sum<GS>(s) * invC;
             float s2 = 0.f;
 #pragma unroll
             for (int i = 0; i < NV; ++i) {
@@ -86,7 +85,7 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const T* __restrict__ x, in
                     s2 += a * a + bb * bb + c * c + d * d;
                 }
             }
-            rs[r] = rsqrtf(group_sum<GS>(s2) * invC + eps);
+            rs[r] = rsqrtf(tc_group_sum<GS>(s2) * invC + eps);
         }
 #pragma unroll
         for (int r = 0; r < RPT; ++r) {
@@ -247,7 +246,7 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const T* __restrict__ dy, i
                     xh[r][i] = xv; gg[r][i] = d;
                 }
             }
-            s1 = group_sum<GS>(s1) * invC; s2 = group_sum<GS>(s2) * invC;
+            s1 = tc_group_sum<GS>(s1) * invC; s2 = tc_group_sum<GS>(s2) * invC;
             if (!live) continue;
             T* dxr = dx + ln_row_off(row0 + r, map, lddx, C);
 #pragma unroll
@@ -282,9 +281,6 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const T* __restrict__ dy, i
 // stage at 1.4 TB/s (56 us a launch).  The raw pieces of all RPT rows are requested before the first one is unpacked.  Same arithmetic in the
 // same order per row as ln_bwd_kernel (statistics over the group by the same shuffles), same parameter-gradient tail.
 typedef unsigned lnu4 __attribute__((ext_vector_type(4)));
-template <typename T> __device__ __forceinline__ void ln_unpack8(const lnu4& r, float* o) {
-    unpack2<T>(r.x, o[0], o[1]); unpack2<T>(r.y, o[2], o[3]); unpack2<T>(r.z, o[4], o[5]); unpack2<T>(r.w, o[6], o[7]);
-}
 template <typename T, int GS, int RPT>
 __global__ __launch_bounds__(256) void ln_bwd_v8_kernel(const T* __restrict__ dy, int lddy, const T* __restrict__ x, int ldx,
                                                         const T* __restrict__ gamma, const T* __restrict__ beta,
@@ -303,7 +299,7 @@ __global__ __launch_bounds__(256) void ln_bwd_v8_kernel(const T* __restrict__ dy
         if (dgamma) { dgamma += g * pstride; dbeta += g * pstride; }
     }
     float g[8], ag[8], ab[8];
-    ln_unpack8<T>(*reinterpret_cast<const lnu4*>(gamma + gl * 8), g);
+    tc_unpack16<T>(*reinterpret_cast<const lnu4*>(gamma + gl * 8), g);
 #pragma unroll
     for (int j = 0; j < 8; ++j) ag[j] = ab[j] = 0.f;
     constexpr float invC = 1.0f / (float)C;
@@ -323,7 +319,7 @@ __global__ __launch_bounds__(256) void ln_bwd_v8_kernel(const T* __restrict__ dy
         for (int r = 0; r < RPT; ++r) {
             const bool live = row0 + r < rows;
             float xv[8], d[8];
-            ln_unpack8<T>(rx[r], xv); ln_unpack8<T>(rd[r], d);
+            tc_unpack16<T>(rx[r], xv); tc_unpack16<T>(rd[r], d);
             float s1 = 0.f, s2 = 0.f;
 #pragma unroll
             for (int j = 0; j < 8; ++j) xv[j] = (xv[j] - mu[r]) * rs[r];
@@ -336,19 +332,18 @@ __global__ __launch_bounds__(256) void ln_bwd_v8_kernel(const T* __restrict__ dy
             // (the 4-wide kernel's order: a lane adds its four values of a piece, pieces in turn)
             s1 = ((d[0] + d[1]) + d[2]) + d[3]; s1 += ((d[4] + d[5]) + d[6]) + d[7];
             s2 = ((d[0] * xv[0] + d[1] * xv[1]) + d[2] * xv[2]) + d[3] * xv[3]; s2 += ((d[4] * xv[4] + d[5] * xv[5]) + d[6] * xv[6]) + d[7] * xv[7];
-            s1 = group_sum<GS>(s1) * invC; s2 = group_sum<GS>(s2) * invC;
+            s1 = tc_group_sum<GS>(s1) * invC; s2 = tc_group_sum<GS>(s2) * invC;
             if (!live) continue;
             float o[8];
 #pragma unroll
             for (int j = 0; j < 8; ++j) o[j] = rs[r] * (d[j] - s1 - xv[j] * s2);
             if (has_res) {
                 float q[8];
-                ln_unpack8<T>(rr[r], q);
+                tc_unpack16<T>(rr[r], q);
 #pragma unroll
                 for (int j = 0; j < 8; ++j) o[j] += q[j];
             }
-            lnu4 w;
-            w.x = pack2<T>(o[0], o[1]); w.y = pack2<T>(o[2], o[3]); w.z = pack2<T>(o[4], o[5]); w.w = pack2<T>(o[6], o[7]);
+            const lnu4 w = tc_pack16<T, lnu4>(o);
             *reinterpret_cast<lnu4*>(dx + ln_row_off(row0 + r, map, lddx, C) + gl * 8) = w;
         }
     }
@@ -375,8 +370,8 @@ __global__ __launch_bounds__(256) void ln_fwd_v8_kernel(const T* __restrict__ x,
         x += g * rows * ldx; y += g * rows * ldy; mean += g * rows * sst; rstd += g * rows * sst; gamma += g * pstride; beta += g * pstride;
     }
     float gm[8], bt[8];
-    ln_unpack8<T>(*reinterpret_cast<const lnu4*>(gamma + gl * 8), gm);
-    ln_unpack8<T>(*reinterpret_cast<const lnu4*>(beta + gl * 8), bt);
+    tc_unpack16<T>(*reinterpret_cast<const lnu4*>(gamma + gl * 8), gm);
+    tc_unpack16<T>(*reinterpret_cast<const lnu4*>(beta + gl * 8), bt);
     constexpr float invC = 1.0f / (float)C;
     for (int row0 = (blockIdx.x * RPB + gi) * RPT; row0 < rows; row0 += gridDim.x * RPB * RPT) {
         lnu4 raw[RPT];
@@ -385,22 +380,21 @@ __global__ __launch_bounds__(256) void ln_fwd_v8_kernel(const T* __restrict__ x,
 #pragma unroll
         for (int r = 0; r < RPT; ++r) {
             float v[8];
-            ln_unpack8<T>(raw[r], v);
+            tc_unpack16<T>(raw[r], v);
             float s = ((v[0] + v[1]) + v[2]) + v[3];
             s += ((v[4] + v[5]) + v[6]) + v[7];
-            const float mu = group_sum<GS>(s) * invC;
+            const float mu = tc_group_sum<GS>(s) * invC;
             float s2 = 0.f;
 #pragma unroll
             for (int j = 0; j < 8; ++j) { const float d = v[j] - mu; s2 += d * d; }
-            const float rs = rsqrtf(group_sum<GS>(s2) * invC + eps);
+            const float rs = rsqrtf(tc_group_sum<GS>(s2) * invC + eps);
             const int row = row0 + r;
             if (row >= rows) continue;
             if (gl == 0) { mean[(long long)row * sst] = mu; rstd[(long long)row * sst] = rs; }
             float o[8];
 #pragma unroll
             for (int j = 0; j < 8; ++j) o[j] = (v[j] - mu) * rs * gm[j] + bt[j];
-            lnu4 w;
-            w.x = pack2<T>(o[0], o[1]); w.y = pack2<T>(o[2], o[3]); w.z = pack2<T>(o[4], o[5]); w.w = pack2<T>(o[6], o[7]);
+            const lnu4 w = tc_pack16<T, lnu4>(o);
             *reinterpret_cast<lnu4*>(y + (long long)row * ldy + gl * 8) = w;
         }
     }

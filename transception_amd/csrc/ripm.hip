@@ -32,18 +32,6 @@ struct RipmFwdDev {
 template <typename T> __device__ __forceinline__ float rp_cvt16(unsigned r);
 template <> __device__ __forceinline__ float rp_cvt16<bf16_t>(unsigned r) { return __uint_as_float(r << 16); }
 template <> __device__ __forceinline__ float rp_cvt16<f16_t>(unsigned r) { f16_t h; h.v = (unsigned short)r; return h2f(h); }
-template <typename T> __device__ __forceinline__ void rp_unpack(const u32x4& r, float* o) {
-    unpack2<T>(r.x, o[0], o[1]); unpack2<T>(r.y, o[2], o[3]); unpack2<T>(r.z, o[4], o[5]); unpack2<T>(r.w, o[6], o[7]);
-}
-template <typename T> __device__ __forceinline__ u32x4 rp_pack(const float* o) {
-    u32x4 r;
-    r.x = pack2<T>(o[0], o[1]); r.y = pack2<T>(o[2], o[3]); r.z = pack2<T>(o[4], o[5]); r.w = pack2<T>(o[6], o[7]);
-    return r;
-}
-
-// workgroup barrier that waits for this wave's LDS traffic only: __syncthreads() also waits for every global load in flight, i.e. for the
-// NEXT chunk's rows -- the prefetch then hides nothing and every chunk costs a memory round trip (18.7 us per step at C = 320)
-#define RP_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
 
 template <typename T, int C, int S>
 __global__ __launch_bounds__(256) void ripm_fwd_kernel(RipmFwdDev p) {
@@ -149,7 +137,7 @@ __global__ __launch_bounds__(256) void ripm_fwd_kernel(RipmFwdDev p) {
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[r] = 0.f;
     for (int kc = 0; kc < NC; ++kc) {
-        if (kc) RP_BARRIER();                             // the previous chunk's MFMAs have read a_t, its depthwise pass in_t
+        if (kc) TC_LDS_BARRIER();                             // the previous chunk's MFMAs have read a_t, its depthwise pass in_t
         // park the chunk: input pieces (normalised + activated when bn_in, zero outside the image), taps
         v8 wcur[4];
 #pragma unroll
@@ -163,11 +151,11 @@ __global__ __launch_bounds__(256) void ripm_fwd_kernel(RipmFwdDev p) {
             u32x4 r = raw[j];
             if (p.bn_in) {
                 float f[8];
-                rp_unpack<T>(r, f);
+                tc_unpack16<T>(r, f);
                 const int c0 = kc * 64 + v * 8;
 #pragma unroll
                 for (int u = 0; u < 8; ++u) f[u] = hswish_f(f[u] * sc[c0 + u] + sh[c0 + u]);
-                r = rp_pack<T>(f);
+                r = tc_pack16<T, u32x4>(f);
                 // the normalised map leaves from the workgroup that owns the pixel (the tile's interior; S = 1 on this path) and this chunk
                 if (ok && S == 1 && py >= 1 && py <= 8 && pxx >= 1 && pxx <= 8 && (kc % (int)gridDim.y) == js)
                     *reinterpret_cast<u32x4*>(reinterpret_cast<T*>(p.xnorm) + ((long long)(b * p.Hi + iy) * p.Wi + ix) * p.ldn + c0) = r;
@@ -181,7 +169,7 @@ __global__ __launch_bounds__(256) void ripm_fwd_kernel(RipmFwdDev p) {
             if (i < 576) { const int ch = i / 9, tap = i - ch * 9; wt[tap * 64 + ch] = rp_cvt16<T>(tapr[j]); }
         }
         if (kc + 1 < NC) RIPM_FETCH(kc + 1);
-        RP_BARRIER();
+        TC_LDS_BARRIER();
         // depthwise 3x3 on the chunk: thread = (output pixel, 8 channels) x 2
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
@@ -194,25 +182,25 @@ __global__ __launch_bounds__(256) void ripm_fwd_kernel(RipmFwdDev p) {
 #pragma unroll
                 for (int kx = 0; kx < 3; ++kx) {
                     float x8[8];
-                    rp_unpack<T>(*reinterpret_cast<const u32x4*>(in_t + ((oy * S + ky) * TWI + ox * S + kx) * PT + v * 8), x8);
+                    tc_unpack16<T>(*reinterpret_cast<const u32x4*>(in_t + ((oy * S + ky) * TWI + ox * S + kx) * PT + v * 8), x8);
                     const float* w = wt + (ky * 3 + kx) * 64 + v * 8;
                     const float4 w0 = *reinterpret_cast<const float4*>(w), w1 = *reinterpret_cast<const float4*>(w + 4);
                     a8[0] = fmaf(x8[0], w0.x, a8[0]); a8[1] = fmaf(x8[1], w0.y, a8[1]); a8[2] = fmaf(x8[2], w0.z, a8[2]); a8[3] = fmaf(x8[3], w0.w, a8[3]);
                     a8[4] = fmaf(x8[4], w1.x, a8[4]); a8[5] = fmaf(x8[5], w1.y, a8[5]); a8[6] = fmaf(x8[6], w1.z, a8[6]); a8[7] = fmaf(x8[7], w1.w, a8[7]);
                 }
-            const u32x4 yv = rp_pack<T>(a8);
+            const u32x4 yv = tc_pack16<T, u32x4>(a8);
             *reinterpret_cast<u32x4*>(a_t + opx * PT + v * 8) = yv;
             const int gy = oy0 + oy, gx = ox0 + ox;
             if (gy < p.Ho && gx < p.Wo && (kc % (int)gridDim.y) == js)
                 *reinterpret_cast<u32x4*>(reinterpret_cast<T*>(p.y) + ((long long)(b * p.Ho + gy) * p.Wo + gx) * p.ldy + kc * 64 + v * 8) = yv;
         }
-        RP_BARRIER();
+        TC_LDS_BARRIER();
         // 1x1: D^T[32 output channels x 32 pixels] += W[.., chunk] y^T
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks)
             acc = TcHalf<T>::mfma(wcur[ks], *reinterpret_cast<const v8*>(a_t + ((wave & 1) * 32 + l31) * PT + ks * 16 + hh * 8), acc);
     }
-    RP_BARRIER();
+    TC_LDS_BARRIER();
     // ---- z tile through LDS (rounded to the storage type first: the statistics are those of the values the next reader sees)
     {
         const int tok = (wave & 1) * 32 + l31;

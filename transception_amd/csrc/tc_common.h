@@ -57,6 +57,76 @@ template <> struct TcHalf<f16_t> {
     static __device__ __forceinline__ tc_f32x16 mfma(v8 a, v8 b, tc_f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
 };
 
+// ---- Shared vector pack / unpack / LDS helpers: the ONE copy of the storage-format facts that producer and consumer kernels in different
+// files must agree on (how 16-bit pairs sit in a word, how the transposing LDS read maps lanes, how its k-rows are permuted). ----
+// 16-byte piece <-> floats.  T = storage type: 4 fp32 lanes, or 8 lanes of a 16-bit type through unpack2 / pack2.  V4 = the caller's four-word
+// vector type (uint4, or a clang ext_vector of unsigned), so every caller keeps the load / store instruction type it chose.
+template <typename T> struct TcVec16 { static constexpr int N = 16 / sizeof(T); };       // elements per 16 bytes
+template <typename T, typename V4> __device__ __forceinline__ void tc_unpack16(const V4& r, float* o) {
+    if constexpr (std::is_same<T, float>::value) {
+        o[0] = __uint_as_float(r.x); o[1] = __uint_as_float(r.y); o[2] = __uint_as_float(r.z); o[3] = __uint_as_float(r.w);
+    } else {
+        unpack2<T>(r.x, o[0], o[1]); unpack2<T>(r.y, o[2], o[3]); unpack2<T>(r.z, o[4], o[5]); unpack2<T>(r.w, o[6], o[7]);
+    }
+}
+template <typename T, typename V4 = uint4> __device__ __forceinline__ V4 tc_pack16(const float* o) {
+    V4 r;
+    if constexpr (std::is_same<T, float>::value) {
+        r.x = __float_as_uint(o[0]); r.y = __float_as_uint(o[1]); r.z = __float_as_uint(o[2]); r.w = __float_as_uint(o[3]);
+    } else {
+        r.x = pack2<T>(o[0], o[1]); r.y = pack2<T>(o[2], o[3]); r.z = pack2<T>(o[4], o[5]); r.w = pack2<T>(o[6], o[7]);
+    }
+    return r;
+}
+// the same vectors as pairs for the packed fp32 pipe (v_pk_fma_f32: two multiply-adds per issue slot)
+template <typename T> __device__ __forceinline__ void tc_unpack16v(const uint4& r, tc_f32x2* o) {
+    if constexpr (std::is_same<T, float>::value) {
+        o[0] = tc_f32x2{__uint_as_float(r.x), __uint_as_float(r.y)}; o[1] = tc_f32x2{__uint_as_float(r.z), __uint_as_float(r.w)};
+    } else {
+        float a, b;
+        unpack2<T>(r.x, a, b); o[0] = tc_f32x2{a, b}; unpack2<T>(r.y, a, b); o[1] = tc_f32x2{a, b};
+        unpack2<T>(r.z, a, b); o[2] = tc_f32x2{a, b}; unpack2<T>(r.w, a, b); o[3] = tc_f32x2{a, b};
+    }
+}
+template <typename T> __device__ __forceinline__ uint4 tc_pack16v(const tc_f32x2* o) {
+    if constexpr (std::is_same<T, float>::value)
+        return make_uint4(__float_as_uint(o[0].x), __float_as_uint(o[0].y), __float_as_uint(o[1].x), __float_as_uint(o[1].y));
+    else return make_uint4(pack2<T>(o[0].x, o[0].y), pack2<T>(o[1].x, o[1].y), pack2<T>(o[2].x, o[2].y), pack2<T>(o[3].x, o[3].y));
+}
+// SV consecutive channels (a whole 16-byte vector or half of one) from LDS / to global memory, as packed pairs
+template <typename T, int SV> __device__ __forceinline__ void tc_unpack_sv(const void* p, tc_f32x2* o) {
+    static_assert(SV == TcVec16<T>::N || 2 * SV == TcVec16<T>::N, "a whole 16-byte vector or half of one");
+    if constexpr (SV == TcVec16<T>::N) tc_unpack16v<T>(*reinterpret_cast<const uint4*>(p), o);
+    else if constexpr (std::is_same<T, float>::value) { const float2 v = *reinterpret_cast<const float2*>(p); o[0] = tc_f32x2{v.x, v.y}; }
+    else {
+        const uint2 r = *reinterpret_cast<const uint2*>(p);
+        float a, b;
+        unpack2<T>(r.x, a, b); o[0] = tc_f32x2{a, b}; unpack2<T>(r.y, a, b); o[1] = tc_f32x2{a, b};
+    }
+}
+template <typename T, int SV> __device__ __forceinline__ void tc_store_sv(T* p, const tc_f32x2* o) {
+    static_assert(SV == TcVec16<T>::N || 2 * SV == TcVec16<T>::N, "a whole 16-byte vector or half of one");
+    if constexpr (SV == TcVec16<T>::N) *reinterpret_cast<uint4*>(p) = tc_pack16v<T>(o);
+    else if constexpr (std::is_same<T, float>::value) *reinterpret_cast<float2*>(p) = make_float2(o[0].x, o[0].y);
+    else *reinterpret_cast<uint2*>(p) = make_uint2(pack2<T>(o[0].x, o[0].y), pack2<T>(o[1].x, o[1].y));
+}
+// Transposing LDS read of an MFMA operand whose LDS rows are its reduction index: two ds_read_tr16_b64 (k-rows lo and hi) make the lane's eight
+// 16-bit elements.  tc_krow is the row permutation that goes with it: rows p, p+4, p+8, p+12 of a 16-k chunk start 16 banks apart, so the
+// chunk's k-rows are stored 4x4-transposed.  Stored so: the GEMM's transposed-operand tiles (gemm.hip has the bank arithmetic), the MixFFN
+// backward tiles yt / dt / w1s, and the K, V, Q and dO tiles of the segmented attention.
+typedef short tc_s16x4 __attribute__((ext_vector_type(4)));
+typedef short tc_s16x8 __attribute__((ext_vector_type(8)));
+template <typename V8> __device__ __forceinline__ V8 tc_lds_tr8(const bf16_t* lo, const bf16_t* hi) {
+    const tc_s16x4 a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((tc_s16x4 __attribute__((address_space(3)))*)(lo));
+    const tc_s16x4 b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((tc_s16x4 __attribute__((address_space(3)))*)(hi));
+    return __builtin_bit_cast(V8, (tc_s16x8)__builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7));
+}
+__device__ __forceinline__ int tc_krow(int k) { return (k & ~15) | ((k & 3) << 2) | ((k >> 2) & 3); }
+// Workgroup barrier that waits for this wave's LDS traffic only: __syncthreads() also waits for every global load in flight, i.e. for the
+// rows a software pipeline has prefetched for its NEXT chunk -- the prefetch then hides nothing and every chunk costs a memory round trip
+// (ripm_fwd_kernel: 18.7 us per step at C = 320).
+#define TC_LDS_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
+
 template <typename T> __device__ __forceinline__ float ldf(const T* p);
 template <> __device__ __forceinline__ float ldf<float>(const float* p) { return *p; }
 template <> __device__ __forceinline__ float ldf<bf16_t>(const bf16_t* p) { return bf2f(*p); }
@@ -170,13 +240,14 @@ template <typename T> __device__ __forceinline__ float gelu_grad_fT(float x) {
 template <typename T> __device__ __forceinline__ float sigmoid_fT(float x) { return tc_rcp<!std::is_same<T, float>::value>(1.0f + __expf(-x)); }
 // Two elements at a time on the packed fp32 pipe (v_pk_mul / v_pk_fma / v_pk_add: two lanes of arithmetic per issue slot; only
 // the two exp and the two reciprocals stay scalar transcendental issues) -- same formula, same rounding per element.
-__device__ __forceinline__ tc_f32x2 gelu_cdf_pdf2(tc_f32x2 x, tc_f32x2& pdf) {
+// FAST as above: the hardware reciprocal, for the 16-bit storage kernels.
+template <bool FAST = false> __device__ __forceinline__ tc_f32x2 gelu_cdf_pdf2(tc_f32x2 x, tc_f32x2& pdf) {
     const tc_f32x2 ax = {fabsf(x.x), fabsf(x.y)};
     const tc_f32x2 z = ax * 0.70710678118654752440f;
     const tc_f32x2 nz2 = -z * z;
     const tc_f32x2 g = {__expf(nz2.x), __expf(nz2.y)};
     const tc_f32x2 den = z * 0.3275911f + 1.0f;
-    const tc_f32x2 t = {__frcp_rn(den.x), __frcp_rn(den.y)};
+    const tc_f32x2 t = {tc_rcp<FAST>(den.x), tc_rcp<FAST>(den.y)};
     tc_f32x2 poly = t * 1.061405429f + (-1.453152027f);
     poly = poly * t + 1.421413741f;
     poly = poly * t + (-0.284496736f);
@@ -186,25 +257,7 @@ __device__ __forceinline__ tc_f32x2 gelu_cdf_pdf2(tc_f32x2 x, tc_f32x2& pdf) {
     const tc_f32x2 one_m = 1.0f - half_erfc;
     return tc_f32x2{x.x >= 0.f ? one_m.x : half_erfc.x, x.y >= 0.f ? one_m.y : half_erfc.y};
 }
-// The same with the hardware reciprocal (v_rcp_f32, 1 ulp) instead of the correctly rounded one (__frcp_rn expands to the IEEE division
-// sequence, ~10 instructions per element): for the 16-bit storage kernels, where the difference is far below the storage rounding.
-__device__ __forceinline__ tc_f32x2 gelu_cdf_pdf2_fast(tc_f32x2 x, tc_f32x2& pdf) {
-    const tc_f32x2 ax = {fabsf(x.x), fabsf(x.y)};
-    const tc_f32x2 z = ax * 0.70710678118654752440f;
-    const tc_f32x2 nz2 = -z * z;
-    const tc_f32x2 g = {__expf(nz2.x), __expf(nz2.y)};
-    const tc_f32x2 den = z * 0.3275911f + 1.0f;
-    const tc_f32x2 t = {__builtin_amdgcn_rcpf(den.x), __builtin_amdgcn_rcpf(den.y)};
-    tc_f32x2 poly = t * 1.061405429f + (-1.453152027f);
-    poly = poly * t + 1.421413741f;
-    poly = poly * t + (-0.284496736f);
-    poly = poly * t + 0.254829592f;
-    const tc_f32x2 half_erfc = poly * t * g * 0.5f;
-    pdf = g * 0.39894228040143267794f;
-    const tc_f32x2 one_m = 1.0f - half_erfc;
-    return tc_f32x2{x.x >= 0.f ? one_m.x : half_erfc.x, x.y >= 0.f ? one_m.y : half_erfc.y};
-}
-__device__ __forceinline__ tc_f32x2 gelu_f2_fast(tc_f32x2 x) { tc_f32x2 pdf; return x * gelu_cdf_pdf2_fast(x, pdf); }
+__device__ __forceinline__ tc_f32x2 gelu_f2_fast(tc_f32x2 x) { tc_f32x2 pdf; return x * gelu_cdf_pdf2<true>(x, pdf); }
 // Forward-only GELU of the 16-bit storage kernels (round 6).  Where only the VALUE is needed the Gaussian is not, and the normal CDF is smooth
 // enough for a polynomial:  Phi(x) ~ 0.5 + t P(t^2), t = clamp(x, -4.2, 4.2), P of degree 8 in t^2 fitted for the smallest maximum ABSOLUTE error
 // (scripts/exp/fit_phi_poly.py: 1.02e-5 over the whole line in fp32 Horner arithmetic; Phi(-4.2) = 1.3e-5 is the clamp's share).  Twelve full-rate
@@ -239,7 +292,7 @@ __device__ __forceinline__ tc_f32x2 gelu_poly2(tc_f32x2 x) {
 }
 __device__ __forceinline__ tc_f32x2 gelu_f2(tc_f32x2 x) { tc_f32x2 pdf; return x * gelu_cdf_pdf2(x, pdf); }
 __device__ __forceinline__ tc_f32x2 gelu_grad_f2(tc_f32x2 x) { tc_f32x2 pdf; const tc_f32x2 cdf = gelu_cdf_pdf2(x, pdf); return cdf + x * pdf; }
-__device__ __forceinline__ tc_f32x2 gelu_grad_f2_fast(tc_f32x2 x) { tc_f32x2 pdf; const tc_f32x2 cdf = gelu_cdf_pdf2_fast(x, pdf); return cdf + x * pdf; }
+__device__ __forceinline__ tc_f32x2 gelu_grad_f2_fast(tc_f32x2 x) { tc_f32x2 pdf; const tc_f32x2 cdf = gelu_cdf_pdf2<true>(x, pdf); return cdf + x * pdf; }
 __device__ __forceinline__ float gelu_grad_f(float x) {
     float pdf;
     const float cdf = gelu_cdf_pdf(x, pdf);

@@ -26,17 +26,17 @@ constexpr int MAXCLS = 16;
 template <typename T> __device__ __forceinline__ void tok_row_load(const T* lp, int ncls, float* v) {
     if constexpr (sizeof(T) == 2) {
         const uint4 a = *reinterpret_cast<const uint4*>(lp);
-        unpack2<T>(a.x, v[0], v[1]); unpack2<T>(a.y, v[2], v[3]); unpack2<T>(a.z, v[4], v[5]); unpack2<T>(a.w, v[6], v[7]);
+        tc_unpack16<T>(a, v);
         if (ncls > 8) {
             const uint4 b = *reinterpret_cast<const uint4*>(lp + 8);
-            unpack2<T>(b.x, v[8], v[9]); unpack2<T>(b.y, v[10], v[11]); unpack2<T>(b.z, v[12], v[13]); unpack2<T>(b.w, v[14], v[15]);
+            tc_unpack16<T>(b, v + 8);
         }
     }
 }
 template <typename T> __device__ __forceinline__ void tok_row_store(T* dp, int ncls, const float* v) {
     if constexpr (sizeof(T) == 2) {
-        *reinterpret_cast<uint4*>(dp) = make_uint4(pack2<T>(v[0], v[1]), pack2<T>(v[2], v[3]), pack2<T>(v[4], v[5]), pack2<T>(v[6], v[7]));
-        if (ncls > 8) *reinterpret_cast<uint4*>(dp + 8) = make_uint4(pack2<T>(v[8], v[9]), pack2<T>(v[10], v[11]), pack2<T>(v[12], v[13]), pack2<T>(v[14], v[15]));
+        *reinterpret_cast<uint4*>(dp) = tc_pack16<T>(v);
+        if (ncls > 8) *reinterpret_cast<uint4*>(dp + 8) = tc_pack16<T>(v + 8);
     }
 }
 
