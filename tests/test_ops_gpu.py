@@ -2,6 +2,8 @@
 against a plain fp32 PyTorch-CPU evaluation of the same math on the same seeded inputs.
 
 Tolerances are for the fp32 path: 2e-5 abs + 2e-5 rel on activations, 1e-4 rel on reductions over >1e4 terms.
+The exact 16-bit, strided and tie coverage of the gate, pooling and aggregate kernels (SE, CBAM, CAM, CoordAtt, fma3, pixel shuffle,
+transpose), called on the C ABI directly, lives in tests/test_gate_kernels_gpu.py.
 """
 import math
 
