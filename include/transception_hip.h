@@ -810,6 +810,34 @@ int tc_sgd_step_multi_scaled(float* p, const float* grad, float* buf, const long
  * growth >= 1, 0 < backoff < 1, interval >= 1, 0 < min_scale <= max_scale, all finite (TC_ERR_ARG otherwise). */
 int tc_loss_scale_update(float* state, const float* sumsq, float growth, float backoff, int interval, float min_scale,
                          float max_scale, void* stream);
+/* ---- Fused Adam / AdamW over the flat arenas, with its step count on the device (a captured kernel's scalar arguments are frozen at
+ * capture, and the bias correction depends on the step number).
+ * An ADAM STATE is four 32-bit words in device memory, owned by the caller (all zero before the first update):
+ *     [0] int32  t: updates applied so far; skipped updates are not counted
+ *     [1] fp32   1 - beta1^t
+ *     [2] fp32   sqrt(1 - beta2^t)
+ *     [3] int32  reserved, written as 0
+ *
+ * tc_adam_advance, launched BEFORE the update kernel of the same step: sumsq == NULL or *sumsq finite: t += 1 and words 1, 2 recomputed
+ * in double from the double betas, each rounded once to fp32; *sumsq inf or NaN: the state stays exactly as it was (tc_adam_step_multi
+ * skips the same step).  0 <= beta < 1 (TC_ERR_ARG otherwise). */
+int tc_adam_advance(float* state, const float* sumsq, double beta1, double beta2, void* stream);
+/* One launch over the (offset, length) segment table of tc_sgd_step_multi.  With c = gscale x the clip coefficient x (scale_state[1] if
+ * given), formed exactly as in tc_sgd_step_multi(_scaled), and wd_s = wd_dev[segment] when wd_dev is given, else wd:
+ *     decoupled != 0 (torch.optim.AdamW):  w1 = w * (1 - lr*wd_s) ;  gh = g*c
+ *     decoupled == 0 (torch.optim.Adam):   w1 = w ;                  gh = g*c + wd_s*w
+ *     m' = beta1*m + (1-beta1)*gh ;  v' = beta2*v + (1-beta2)*gh*gh
+ *     w' = w1 - (lr / adam_state[1]) * m' / (sqrt(v') / adam_state[2] + eps)
+ * float(beta) and float(1 - beta) are each rounded once from the double arguments; division and square root are correctly rounded.
+ * adam_state must have been advanced at least once (word 1 is 0 before).  lr_dev overrides lr; a non-finite *clip_sumsq returns before
+ * touching p, m, v or lp; scale_state (a loss-scale state) requires clip_sumsq, and clip_norm * scale_state[0] then bounds the norm of the
+ * TRUE gradient; lp (TC_BF16 / TC_F16) receives the rounded w'; elements outside the segments are never read or written.
+ * TC_ERR_ARG: a beta outside [0, 1), eps <= 0, nseg <= 0, an unknown lp_dtype with lp set, adam_state == NULL, scale_state without
+ * clip_sumsq. */
+int tc_adam_step_multi(float* p, const float* grad, float* m, float* v, const long long* segs_dev, const float* wd_dev, int nseg,
+                       long long max_len, float lr, const float* lr_dev, double beta1, double beta2, float eps, float wd, int decoupled,
+                       float gscale, const float* clip_sumsq, float clip_norm, void* lp, int lp_dtype, const float* scale_state,
+                       const float* adam_state, void* stream);
 /* *out += sum_i g[i]^2 over a flat fp32 buffer (n a multiple of 4, 16-byte aligned): the squared total gradient norm. */
 int tc_grad_sumsq(const float* g, long long n, float* out, void* stream);
 /* p[0..n) = v (fp32): resets device accumulators inside a captured step */

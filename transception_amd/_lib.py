@@ -226,6 +226,8 @@ SIGNATURES = {
     "tc_sgd_step_multi": [vp, vp, vp, vp, i32, i64, f32, vp, f32, f32, f32, i32, vp, f32, vp, i32, vp],
     "tc_sgd_step_multi_scaled": [vp, vp, vp, vp, i32, i64, f32, vp, f32, f32, f32, i32, vp, f32, vp, i32, vp, vp],
     "tc_loss_scale_update": [vp, vp, f32, f32, i32, f32, f32, vp],
+    "tc_adam_advance": [vp, vp, f64, f64, vp],
+    "tc_adam_step_multi": [vp, vp, vp, vp, vp, vp, i32, i64, f32, vp, f64, f64, f32, f32, i32, f32, vp, f32, vp, i32, vp, vp, vp],
     "tc_grad_sumsq": [vp, i64, vp, vp],
     "tc_fill_f32": [vp, i64, f32, vp],
     "tc_cast": [vp, vp, i64, i32, i32, vp],

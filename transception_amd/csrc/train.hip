@@ -297,6 +297,91 @@ __global__ void sgd_multi_kernel(float* __restrict__ p, const float* __restrict_
     }
 }
 
+// The step count of an Adam state (include/transception_hip.h) and the two bias terms derived from it.  One thread: ordinary loads and
+// stores.  beta^t by repeated squaring in double (at most 62 multiplications, each within 2^-53: far inside one float32 rounding of
+// 1 - beta^t even at t = 1, where 1 - 0.999 cancels three digits), every word rounded once.  A non-finite *sumsq leaves all four words
+// alone: adam_multi_kernel skips the same step.
+__global__ void adam_advance_kernel(float* __restrict__ state, const float* __restrict__ sumsq, double beta1, double beta2) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    if (sumsq && !(*sumsq < __builtin_inff())) return;
+    int* istate = reinterpret_cast<int*>(state);
+    const int t = istate[0] + 1;
+    double p1 = 1.0, p2 = 1.0, s1 = beta1, s2 = beta2;
+    for (unsigned k = (unsigned)t; k; k >>= 1) {
+        if (k & 1) { p1 *= s1; p2 *= s2; }
+        s1 *= s1;
+        s2 *= s2;
+    }
+    istate[0] = t;
+    state[1] = (float)(1.0 - p1);
+    state[2] = (float)sqrt(1.0 - p2);
+    istate[3] = 0;
+}
+
+// torch.optim.AdamW (decoupled) / torch.optim.Adam (coupled decay) on one element.  dk = 1 - lr wd (decoupled) or 1; wc = wd (coupled) or 0;
+// step = lr / state[1]; rbc2 is state[2] itself: sqrt(v') is DIVIDED by it, as torch does.  Division and sqrtf are the correctly rounded ones.
+__device__ __forceinline__ float adam_elem(float w, float g, float& m, float& v, float c, float dk, float wc, float b1, float omb1, float b2,
+                                           float omb2, float step, float bc2, float eps) {
+    const float gh = g * c + wc * w;
+    m = b1 * m + omb1 * gh;
+    v = b2 * v + (omb2 * gh) * gh;
+    return w * dk - step * (m / (sqrtf(v) / bc2 + eps));
+}
+
+// The segment table, the clip / skip / loss-scale prologue, the alignment test and the two element paths are sgd_multi_kernel's.
+// 30 bytes per weight with a 16-bit copy: p, g, m, v read, p, m, v and lp written.
+__global__ __launch_bounds__(256) void adam_multi_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                         float* __restrict__ v, const long long* __restrict__ segs,
+                                                         const float* __restrict__ wd_dev, float lr, const float* __restrict__ lr_dev, float b1,
+                                                         float omb1, float b2, float omb2, float eps, float wd, int decoupled, float gscale,
+                                                         const float* __restrict__ clip_sumsq, float clip_norm, void* __restrict__ lp,
+                                                         int lp_dtype, const float* __restrict__ scale_state,
+                                                         const float* __restrict__ adam_state) {
+    if (lr_dev) lr = *lr_dev;
+    if (clip_sumsq) {
+        const float ss = *clip_sumsq;
+        if (!(ss < __builtin_inff())) return;     // skipped: weights, both moments and the 16-bit copy stay; adam_advance_kernel did not count it
+        if (scale_state) {
+            gscale *= scale_state[1];
+            clip_norm *= scale_state[0];
+        }
+        gscale *= fminf(clip_norm / (sqrtf(ss) + 1e-6f), 1.0f);
+    }
+    if (wd_dev) wd = wd_dev[blockIdx.y];
+    const float dk = decoupled ? 1.f - lr * wd : 1.f, wc = decoupled ? 0.f : wd;
+    const float step = lr / adam_state[1], bc2 = adam_state[2];
+    const long long off = segs[2 * blockIdx.y], n = segs[2 * blockIdx.y + 1];
+    if (!((off | n) & 3) && !(((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) && !((uintptr_t)lp & 7)) {
+        const long long n4 = n >> 2;
+        for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long long)gridDim.x * 256) {
+            const long long j = off + 4 * i;
+            const float4 w = *reinterpret_cast<const float4*>(p + j), gv = *reinterpret_cast<const float4*>(g + j);
+            float4 mv = *reinterpret_cast<const float4*>(m + j), vv = *reinterpret_cast<const float4*>(v + j);
+            float4 wn;
+            wn.x = adam_elem(w.x, gv.x, mv.x, vv.x, gscale, dk, wc, b1, omb1, b2, omb2, step, bc2, eps);
+            wn.y = adam_elem(w.y, gv.y, mv.y, vv.y, gscale, dk, wc, b1, omb1, b2, omb2, step, bc2, eps);
+            wn.z = adam_elem(w.z, gv.z, mv.z, vv.z, gscale, dk, wc, b1, omb1, b2, omb2, step, bc2, eps);
+            wn.w = adam_elem(w.w, gv.w, mv.w, vv.w, gscale, dk, wc, b1, omb1, b2, omb2, step, bc2, eps);
+            *reinterpret_cast<float4*>(m + j) = mv;
+            *reinterpret_cast<float4*>(v + j) = vv;
+            *reinterpret_cast<float4*>(p + j) = wn;
+            if (lp_dtype == TC_BF16) *reinterpret_cast<uint2*>(reinterpret_cast<bf16_t*>(lp) + j) = make_uint2(pack2<bf16_t>(wn.x, wn.y), pack2<bf16_t>(wn.z, wn.w));
+            else if (lp_dtype == TC_F16) *reinterpret_cast<uint2*>(reinterpret_cast<f16_t*>(lp) + j) = make_uint2(pack2<f16_t>(wn.x, wn.y), pack2<f16_t>(wn.z, wn.w));
+        }
+        return;
+    }
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
+        const long long j = off + i;
+        float mj = m[j], vj = v[j];
+        const float wn = adam_elem(p[j], g[j], mj, vj, gscale, dk, wc, b1, omb1, b2, omb2, step, bc2, eps);
+        m[j] = mj;
+        v[j] = vj;
+        p[j] = wn;
+        if (lp_dtype == TC_BF16) reinterpret_cast<bf16_t*>(lp)[j] = f2bf(wn);
+        else if (lp_dtype == TC_F16) reinterpret_cast<f16_t*>(lp)[j] = f2h(wn);
+    }
+}
+
 // Evaluation (utils.py:72-76,96-97): pred = argmax_k logits[b,k,p] (softmax is monotone; first maximum wins like torch.argmax) and,
 // when labels are given, per-class voxel counts  counts[3k..3k+2] += (|pred==k & gt==k|, |pred==k|, |gt==k|)  for the Dice of
 // calculate_metric_percase (utils.py:50-60).  Counts are exact in fp32 up to 2^24 per launch; the host accumulates in float64.
@@ -528,6 +613,27 @@ extern "C" int tc_sgd_step_multi_scaled(float* p, const float* grad, float* buf,
         return TC_ERR_ARG;
     hipLaunchKernelGGL(sgd_multi_kernel, dim3(tc_blocks(max_len, 256 * 8, 256), nseg), dim3(256), 0, (hipStream_t)stream, p, grad, buf, segs_dev,
                        lr, momentum, wd, gscale, first, lr_dev, clip_sumsq, clip_norm, lp, lp ? lp_dtype : -1, scale_state);
+    return tc_launch_status();
+}
+
+extern "C" int tc_adam_advance(float* state, const float* sumsq, double beta1, double beta2, void* stream) {
+    if (!state || !(beta1 >= 0.0) || !(beta1 < 1.0) || !(beta2 >= 0.0) || !(beta2 < 1.0)) return TC_ERR_ARG;
+    hipLaunchKernelGGL(adam_advance_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, state, sumsq, beta1, beta2);
+    return tc_launch_status();
+}
+
+extern "C" int tc_adam_step_multi(float* p, const float* grad, float* m, float* v, const long long* segs_dev, const float* wd_dev, int nseg,
+                                  long long max_len, float lr, const float* lr_dev, double beta1, double beta2, float eps, float wd,
+                                  int decoupled, float gscale, const float* clip_sumsq, float clip_norm, void* lp, int lp_dtype,
+                                  const float* scale_state, const float* adam_state, void* stream) {
+    if (!p || !grad || !m || !v || !segs_dev || !adam_state || nseg <= 0 || nseg > 65535 || max_len <= 0 || !(beta1 >= 0.0) || !(beta1 < 1.0) ||
+        !(beta2 >= 0.0) || !(beta2 < 1.0) || !(eps > 0.f) || (clip_sumsq && !(clip_norm > 0.f)) || (scale_state && !clip_sumsq) ||
+        (lp && lp_dtype != TC_BF16 && lp_dtype != TC_F16))
+        return TC_ERR_ARG;
+    // float(beta) and float(1 - beta): each rounded once from double, here on the host side of the launch
+    hipLaunchKernelGGL(adam_multi_kernel, dim3(tc_blocks(max_len, 256 * 8, 256), nseg), dim3(256), 0, (hipStream_t)stream, p, grad, m, v, segs_dev,
+                       wd_dev, lr, lr_dev, (float)beta1, (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), eps, wd, decoupled ? 1 : 0,
+                       gscale, clip_sumsq, clip_norm, lp, lp ? lp_dtype : -1, scale_state, adam_state);
     return tc_launch_status();
 }
 

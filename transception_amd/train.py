@@ -2,6 +2,7 @@
 
   loss = 0.4 * CrossEntropy + 0.6 * Dice(softmax=True)           trainer.py:141-143, utils.py:11-47
   SGD(momentum 0.9, weight_decay 1e-4), per-iteration cosine LR   trainer.py:125-127, 151-153
+  (FusedAdamW: torch.optim.AdamW / Adam in its place, with the step count of the bias corrections on the device)
   batch-dim sharding: one process per GPU, gradients all-reduced over RCCL (the reference uses
   nn.DataParallel, trainer.py:110-111); the Dice sums are all-reduced so the loss equals the
   single-process global-batch loss.
@@ -324,19 +325,42 @@ def cosine_lr(base_lr: float, step: int, t_max: int) -> float:
     return 0.5 * base_lr * (1.0 + math.cos(math.pi * step / t_max))
 
 
-class FusedSGD:
-    """torch.optim.SGD(momentum, weight_decay) semantics as one kernel over the model's flat arenas.
+def build_segments(views):
+    """The update kernels' segment table from the sorted (offset, numel, decay) views of the parameters that receive a gradient: every view
+    is padded to a multiple of 8 elements (the arena's own padding, model._ensure_flat) and adjacent views of the same decay are merged.
+    Returns [(offset, length, decay)].  Pure host code."""
+    segs = []
+    for off, n, wd in views:
+        n8 = (n + 7) // 8 * 8
+        if segs and segs[-1][0] + segs[-1][1] == off and segs[-1][2] == wd:
+            segs[-1][1] += n8
+        else:
+            segs.append([off, n8, wd])
+    return [(o, n, wd) for o, n, wd in segs]
 
-    Parameters that never receive a gradient (332 tensors in the reference) are left untouched, exactly as
-    torch.optim.SGD skips `p.grad is None`: the update runs over the used segments only."""
 
-    def __init__(self, model, lr: float = 0.05, momentum: float = 0.9, weight_decay: float = 1e-4, clip_norm: Optional[float] = None):
-        self.model, self.lr, self.momentum, self.wd = model, lr, momentum, weight_decay
+def check_no_decay(no_decay):
+    """None, a predicate (name, shape) -> bool, or "norm_bias" (every tensor with ndim <= 1: LayerNorm / BatchNorm affine parameters
+    and all biases).  Returns the predicate or None; anything else is a ValueError."""
+    if no_decay is None or callable(no_decay):
+        return no_decay
+    if no_decay == "norm_bias":
+        return lambda name, shape: len(shape) <= 1
+    raise ValueError(f'no_decay must be None, "norm_bias" or a predicate (name, shape) -> bool, got {no_decay!r}')
+
+
+class _FusedOptimizer:
+    """What the fused optimisers share: the segment table over the parameters that receive a gradient (the 332 grad-less tensors of
+    the reference are left untouched, as torch.optim skips `p.grad is None`), the device learning rate, the squared-norm launches of
+    clipping and of the overflow guard, the choice of the 16-bit working copy the update refreshes, and the skip read-back."""
+
+    def __init__(self, model, lr: float, weight_decay: float, clip_norm: Optional[float]):
+        self.model, self.lr, self.wd = model, lr, weight_decay
         self.clip_norm = clip_norm                       # nn.utils.clip_grad_norm_(max_norm, 2) before the update (trainer.py:147-148)
-        self.buf: Optional[torch.Tensor] = None
         self.steps = 0
         self._segments = None
         self._segs_dev: Optional[torch.Tensor] = None
+        self._wd_dev: Optional[torch.Tensor] = None      # per-segment decay (FusedAdamW(no_decay=...)); None: one decay for all
         self.lr_dev: Optional[torch.Tensor] = None       # device scalar read by the kernel (hipGraph-friendly schedule)
         self._sumsq: Optional[torch.Tensor] = None       # squared gradient norm (clip_norm)
         self.grad_scale = 1.0                            # gradients in the arena are this many times too small (1 / loss scale)
@@ -347,7 +371,7 @@ class FusedSGD:
 
     def last_step_skipped(self) -> bool:
         """True when the last update was skipped because the gradient norm was not finite (float16 overflow under a loss scale:
-        sgd_multi_kernel returns without touching the weights).  Reads one float back (a host sync): call it where the loop already
+        the update kernel returns without touching the weights).  Reads one float back (a host sync): call it where the loop already
         reads its loss scalars; a run whose every step overflows would otherwise look like a plateau."""
         if self._sumsq is None:
             return False
@@ -360,22 +384,65 @@ class FusedSGD:
         if self.lr_dev is not None:
             self.lr_dev.fill_(lr)
 
-    def _segs(self):
+    def _decay_of(self, name: str, shape) -> float:
+        return self.wd
+
+    def _segs3(self):
         if self._segments is None:
-            views = sorted((off, math.prod(shape)) for off, shape in self.model._used_views.values())
-            segs = []
-            for off, n in views:
-                n8 = (n + 7) // 8 * 8
-                if segs and segs[-1][0] + segs[-1][1] == off:
-                    segs[-1][1] += n8
-                else:
-                    segs.append([off, n8])
-            self._segments = [(o, n) for o, n in segs]
+            M = self.model
+            names = {}
+            for name, pid in getattr(M, "_pid", {}).items():
+                names.setdefault(pid, name)
+            views = sorted((off, math.prod(shape), self._decay_of(names.get(pid, ""), shape)) for pid, (off, shape) in M._used_views.items())
+            self._segments = build_segments(views)
         return self._segments
+
+    def _segs(self):
+        return [(o, n) for o, n, _ in self._segs3()]
 
     def zero_grad(self):
         if self.model._gflat is not None:
             self.model._gflat.zero_()
+
+    def _tables(self, flat):
+        """The device learning rate and the device segment table, created on first use and never replaced."""
+        if self.lr_dev is None:
+            self.lr_dev = torch.full((1,), float(self.lr), dtype=torch.float32, device=flat.device)
+        if self._segs_dev is None:
+            segs = [(off, min(n, flat.numel() - off)) for off, n in self._segs()]
+            self._segs_dev = torch.tensor([v for s in segs for v in s], dtype=torch.int64, device=flat.device)
+            self._nseg, self._maxlen = len(segs), max(n for _, n in segs)
+
+    def _norm_launches(self, L, g, stream):
+        """tc_fill_f32 + tc_grad_sumsq when clipping or guarding; returns the device address of the squared norm, or None."""
+        M = self.model
+        guard = self.loss_scaler is not None or (self.guard_overflow if self.guard_overflow is not None else M.compute_dtype == torch.float16)
+        if not (self.clip_norm or guard):
+            return None
+        # clip_grad_norm_(max_norm, 2): one reduction kernel for the squared norm (grad-less parameters hold zeros, so the arena's
+        # norm is the model's), the coefficient min(1, max_norm / (norm + 1e-6)) is applied inside the update kernel
+        if self._sumsq is None:
+            self._sumsq = torch.zeros(1, dtype=torch.float32, device=g.device)
+        L.tc_fill_f32(self._sumsq.data_ptr(), 1, 0.0, stream)
+        L.tc_grad_sumsq(g.data_ptr(), g.numel(), self._sumsq.data_ptr(), stream)
+        return self._sumsq.data_ptr()
+
+    def _working_copy(self):
+        """The 16-bit working copy of the weights that the update kernel refreshes (the forward then skips its cast pass over the arena)."""
+        M = self.model
+        return M._flat_lp if (M.compute_dtype != torch.float32 and M._flat_lp is not None and M._flat_lp.dtype == M.compute_dtype) else None
+
+
+class FusedSGD(_FusedOptimizer):
+    """torch.optim.SGD(momentum, weight_decay) semantics as one kernel over the model's flat arenas.
+
+    Parameters that never receive a gradient (332 tensors in the reference) are left untouched, exactly as
+    torch.optim.SGD skips `p.grad is None`: the update runs over the used segments only."""
+
+    def __init__(self, model, lr: float = 0.05, momentum: float = 0.9, weight_decay: float = 1e-4, clip_norm: Optional[float] = None):
+        super().__init__(model, lr, weight_decay, clip_norm)
+        self.momentum = momentum
+        self.buf: Optional[torch.Tensor] = None
 
     def step(self, grad_scale: Optional[float] = None):
         grad_scale = self.grad_scale if grad_scale is None else grad_scale
@@ -383,27 +450,12 @@ class FusedSGD:
         flat, g = M._flat, M._gflat
         if self.buf is None:
             self.buf = torch.zeros_like(flat)
-        if self.lr_dev is None:
-            self.lr_dev = torch.full((1,), float(self.lr), dtype=torch.float32, device=flat.device)
+        self._tables(flat)
         L = lib()
         stream = torch.cuda.current_stream(flat.device).cuda_stream
-        if self._segs_dev is None:
-            segs = [(off, min(n, flat.numel() - off)) for off, n in self._segs()]
-            self._segs_dev = torch.tensor([v for s in segs for v in s], dtype=torch.int64, device=flat.device)
-            self._nseg, self._maxlen = len(segs), max(n for _, n in segs)
-        sumsq = None
         scaler = self.loss_scaler
-        guard = scaler is not None or (self.guard_overflow if self.guard_overflow is not None else M.compute_dtype == torch.float16)
-        if self.clip_norm or guard:
-            # clip_grad_norm_(max_norm, 2): one reduction kernel for the squared norm (grad-less parameters hold zeros, so the arena's
-            # norm is the model's), the coefficient min(1, max_norm / (norm + 1e-6)) is applied inside the update kernel
-            if self._sumsq is None:
-                self._sumsq = torch.zeros(1, dtype=torch.float32, device=flat.device)
-            L.tc_fill_f32(self._sumsq.data_ptr(), 1, 0.0, stream)
-            L.tc_grad_sumsq(g.data_ptr(), g.numel(), self._sumsq.data_ptr(), stream)
-            sumsq = self._sumsq.data_ptr()
-        # the 16-bit working copy of the weights is refreshed by the same kernel (the forward then skips its cast pass over the arena)
-        lp = M._flat_lp if (M.compute_dtype != torch.float32 and M._flat_lp is not None and M._flat_lp.dtype == M.compute_dtype) else None
+        sumsq = self._norm_launches(L, g, stream)
+        lp = self._working_copy()
         # `first` is baked into a captured kernel's arguments, and a skipped first step is harmless all the same: the momentum buffer
         # starts as zeros, so the later form mom * 0 + d equals the first-step form d
         args = (flat.data_ptr(), g.data_ptr(), self.buf.data_ptr(), self._segs_dev.data_ptr(), self._nseg, self._maxlen,
@@ -419,6 +471,95 @@ class FusedSGD:
             scaler.update(self._sumsq)
         M._lp_fresh = lp is not None
         self.steps += 1
+
+
+class FusedAdamW(_FusedOptimizer):
+    """torch.optim.AdamW (decoupled=True) or torch.optim.Adam (decoupled=False: the decay enters the gradient) as one kernel over the
+    model's flat arenas, under everything FusedSGD runs under: the captured step, gradient clipping, the 16-bit working copy, the
+    overflow guard and a DynamicLossScale.
+
+    The step number t of the bias corrections lives on the device (an Adam state, include/transception_hip.h: t, 1 - beta1^t,
+    sqrt(1 - beta2^t)): a captured kernel's scalar arguments are frozen at capture, so tc_adam_advance -- one single-thread launch
+    before the update -- counts the step and rewrites the two terms, and leaves all of it alone when the update is about to be skipped.
+    `steps` counts calls of step(); the device word counts applied updates (state_dict()["step"]).
+
+    no_decay: a predicate (name, shape) -> bool, or "norm_bias" for every tensor with ndim <= 1 (LayerNorm / BatchNorm affine parameters
+    and all biases): those tensors take no weight decay.  Segments are then not merged across a change of decay class and the kernel
+    reads one decay per segment from device memory."""
+
+    def __init__(self, model, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2, decoupled: bool = True,
+                 clip_norm: Optional[float] = None, no_decay=None):
+        super().__init__(model, lr, weight_decay, clip_norm)
+        b1, b2 = (float(b) for b in betas)
+        if not (0.0 <= b1 < 1.0 and 0.0 <= b2 < 1.0):
+            raise ValueError(f"betas must lie in [0, 1), got {betas!r}")
+        if not (isinstance(eps, (int, float)) and eps > 0.0):
+            raise ValueError(f"eps must be > 0, got {eps!r}")
+        if not (isinstance(weight_decay, (int, float)) and weight_decay >= 0.0):
+            raise ValueError(f"weight_decay must be >= 0, got {weight_decay!r}")
+        self.betas, self.eps, self.decoupled = (b1, b2), float(eps), bool(decoupled)
+        self._no_decay = check_no_decay(no_decay)
+        self.m: Optional[torch.Tensor] = None            # exp_avg
+        self.v: Optional[torch.Tensor] = None            # exp_avg_sq
+        self._adam_state: Optional[torch.Tensor] = None  # fp32[4]; words 0 and 3 are int32
+
+    def _decay_of(self, name: str, shape) -> float:
+        return 0.0 if self._no_decay is not None and self._no_decay(name, tuple(shape)) else float(self.wd)
+
+    def _ensure_state(self):
+        """Both moment arenas and the four-word Adam state.  Their addresses are baked into captured launches: never replaced."""
+        M = self.model
+        if M._flat is None:
+            M._ensure_flat(next(M.parameters()).device)
+        if self.m is None:
+            self.m, self.v = torch.zeros_like(M._flat), torch.zeros_like(M._flat)
+            self._adam_state = torch.zeros(4, dtype=torch.float32, device=M._flat.device)
+
+    def device_step(self) -> int:
+        """Updates applied so far, as counted on the device (skipped ones are not).  A host sync."""
+        return 0 if self._adam_state is None else int(self._adam_state.view(torch.int32)[0].item())
+
+    def step(self, grad_scale: Optional[float] = None):
+        grad_scale = self.grad_scale if grad_scale is None else grad_scale
+        M = self.model
+        flat, g = M._flat, M._gflat
+        self._ensure_state()
+        self._tables(flat)
+        if self._no_decay is not None and self._wd_dev is None:
+            self._wd_dev = torch.tensor([wd for _, _, wd in self._segs3()], dtype=torch.float32, device=flat.device)
+        L = lib()
+        stream = torch.cuda.current_stream(flat.device).cuda_stream
+        scaler = self.loss_scaler
+        sumsq = self._norm_launches(L, g, stream)
+        lp = self._working_copy()
+        st = self._adam_state.data_ptr()
+        L.tc_adam_advance(st, sumsq, self.betas[0], self.betas[1], stream)
+        L.tc_adam_step_multi(flat.data_ptr(), g.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), self._segs_dev.data_ptr(),
+                             self._wd_dev.data_ptr() if self._wd_dev is not None else None, self._nseg, self._maxlen, float(self.lr),
+                             self.lr_dev.data_ptr(), self.betas[0], self.betas[1], self.eps, float(self.wd), int(self.decoupled),
+                             float(grad_scale), sumsq, float((self.clip_norm or math.inf) / grad_scale),
+                             lp.data_ptr() if lp is not None else None, M._tc_dtype() if lp is not None else 0,
+                             scaler.state(flat.device).data_ptr() if scaler is not None else None, st, stream)
+        if scaler is not None:
+            scaler.update(self._sumsq)               # the scale takes its own step from the same squared norm
+        M._lp_fresh = lp is not None
+        self.steps += 1
+
+    def state_dict(self) -> dict:
+        """{"step", "exp_avg", "exp_avg_sq"}: the device's count of applied updates (a host sync) and clones of the two moment arenas."""
+        self._ensure_state()
+        return {"step": self.device_step(), "exp_avg": self.m.clone(), "exp_avg_sq": self.v.clone()}
+
+    def load_state_dict(self, sd: dict):
+        """Writes the step word and both arenas IN PLACE (same data_ptrs): a captured step keeps working and sees them on its next
+        replay.  The two bias words need no restoring: tc_adam_advance rewrites them from the step word before any use."""
+        step = int(sd["step"])
+        if step < 0:
+            raise ValueError(f"bad optimiser step {sd['step']!r}")
+        self._ensure_state()
+        self.m.copy_(sd["exp_avg"])
+        self.v.copy_(sd["exp_avg_sq"])
+        self._adam_state.view(torch.int32)[0:1].copy_(torch.tensor([step], dtype=torch.int32))
 
 
 def gradient_buckets(model, max_gap: int = 1 << 18):
@@ -616,7 +757,7 @@ def allreduce_gradients(model, group=None, part: Optional[str] = None, async_op:
     return works
 
 
-def train_step(model, loss_fn: SegLoss, opt: FusedSGD, images: torch.Tensor, labels: torch.Tensor, group=None):
+def train_step(model, loss_fn: SegLoss, opt: _FusedOptimizer, images: torch.Tensor, labels: torch.Tensor, group=None):
     """One step with trainer.py semantics; returns (loss, ce, dice) tensors (no host sync)."""
     opt.zero_grad()
     _wire_loss_scale(loss_fn, opt, images.device)

@@ -4,7 +4,8 @@ training step in place of the per-iteration Python loop body.
 
 What is kept from the reference loop:
   * global batch = batch_size * n_gpu (trainer.py:86) -- here batch_size per rank, one process per GPU;
-  * loss 0.4 CE + 0.6 Dice (trainer.py:141-143), SGD(momentum 0.9, weight_decay 1e-4) (:125);
+  * loss 0.4 CE + 0.6 Dice (trainer.py:141-143), SGD(momentum 0.9, weight_decay 1e-4) (:125) -- or, by TrainConfig.optimizer, AdamW / Adam
+    (train.FusedAdamW) under the same schedule, clipping, loss scale and skip logging; base_lr is used as given, and its default 0.05 is SGD's value;
   * CosineAnnealingLR(T_max = max_epochs * len(loader)) stepped every iteration (:126-127,151-153), or the polynomial decay
     base_lr (1 - iter/max_iter)^0.9 when use_scheduler is off (:154-157); optional clip_grad_norm_(5) (:147-148);
   * the learning-rate scaling quirk of the launcher (train_MSTransception.py:123-124) as `scaled_base_lr`;
@@ -25,7 +26,9 @@ import torch.distributed as dist
 
 from .data import DeviceLoader, SynapseSlices
 from .evaluate import inference
-from .train import DynamicLossScale, FusedSGD, GraphedStep, SegLoss, check_class_weights, check_ignore_index, cosine_lr, train_step
+from .train import DynamicLossScale, FusedAdamW, FusedSGD, GraphedStep, SegLoss, check_class_weights, check_ignore_index, cosine_lr, train_step
+
+OPTIMIZERS = ("sgd", "adamw", "adam")
 
 
 @dataclass
@@ -35,7 +38,8 @@ class TrainConfig:
     num_classes: int = 9
     max_epochs: int = 400
     batch_size: int = 24               # per GPU (train_MSTransception.py:35-36)
-    base_lr: float = 0.05
+    base_lr: float = 0.05              # SGD's value (train_MSTransception.py); it is used as given under every optimizer, never rescaled
+                                       # for one -- AdamW / Adam want something near 1e-3
     img_size: int = 224
     seed: int = 1234
     eval_interval: int = 20
@@ -51,8 +55,32 @@ class TrainConfig:
                                        # train.DynamicLossScale (device-resident, adjusts itself inside the captured step)
     class_weights: Optional[tuple] = None  # num_classes weights >= 0, not all zero, used as BOTH the CrossEntropyLoss weight and the Dice weight
     ignore_index: Optional[int] = None     # a label value outside [0, num_classes) (e.g. 255) whose pixels count in neither loss term
+    optimizer: str = "sgd"             # "sgd": the reference's SGD(momentum 0.9); "adamw" / "adam": train.FusedAdamW, decoupled / coupled decay
+    weight_decay: Optional[float] = None   # None: 1e-4 for sgd (trainer.py:125), 1e-2 for adamw / adam (torch's AdamW default)
+    betas: tuple = (0.9, 0.999)        # adamw / adam
+    adam_eps: float = 1e-8             # adamw / adam
+    no_decay: Optional[str] = None     # adamw / adam: "norm_bias" = no decay on tensors with ndim <= 1 (norm affine parameters and biases)
 
     def __post_init__(self):
+        if self.optimizer not in OPTIMIZERS:
+            raise ValueError(f"optimizer must be one of {OPTIMIZERS}, got {self.optimizer!r}")
+        wd = self.weight_decay
+        if wd is not None and (isinstance(wd, bool) or not isinstance(wd, (int, float)) or not math.isfinite(wd) or wd < 0):
+            raise ValueError(f"weight_decay must be None or a finite number >= 0, got {wd!r}")
+        try:
+            b1, b2 = self.betas
+            ok = all(isinstance(b, (int, float)) and not isinstance(b, bool) and 0.0 <= b < 1.0 for b in (b1, b2))
+        except (TypeError, ValueError):
+            ok = False
+        if not ok:
+            raise ValueError(f"betas must be two numbers in [0, 1), got {self.betas!r}")
+        e = self.adam_eps
+        if isinstance(e, bool) or not isinstance(e, (int, float)) or not math.isfinite(e) or e <= 0:
+            raise ValueError(f"adam_eps must be a finite number > 0, got {e!r}")
+        if self.no_decay not in (None, "norm_bias"):
+            raise ValueError(f'no_decay must be None or "norm_bias", got {self.no_decay!r}')
+        if self.no_decay is not None and self.optimizer == "sgd":
+            raise ValueError("no_decay needs optimizer=\"adamw\" or \"adam\": the SGD kernel takes one decay for all segments")
         make_loss_scale(self.loss_scale)
         check_class_weights("class_weights", self.class_weights, self.num_classes, need_positive=True)
         check_ignore_index(self.ignore_index, self.num_classes)
@@ -67,6 +95,15 @@ def make_loss_scale(spec) -> Union[float, DynamicLossScale]:
     if isinstance(spec, (int, float)) and not isinstance(spec, bool) and math.isfinite(spec) and spec > 0:
         return float(spec)
     raise ValueError(f'loss_scale must be None, a positive finite number or "dynamic", got {spec!r}')
+
+
+def make_optimizer(cfg: TrainConfig, model):
+    """The optimiser TrainConfig asks for.  "sgd" is the reference's, built with the arguments it always had."""
+    clip = 5.0 if cfg.grad_clipping else None
+    if cfg.optimizer == "sgd":
+        return FusedSGD(model, lr=cfg.base_lr, momentum=0.9, weight_decay=1e-4 if cfg.weight_decay is None else cfg.weight_decay, clip_norm=clip)
+    return FusedAdamW(model, lr=cfg.base_lr, betas=tuple(cfg.betas), eps=cfg.adam_eps, weight_decay=1e-2 if cfg.weight_decay is None else cfg.weight_decay,
+                      decoupled=cfg.optimizer == "adamw", clip_norm=clip, no_decay=cfg.no_decay)
 
 
 def scaled_base_lr(base_lr: float, batch_size: int) -> float:
@@ -88,7 +125,8 @@ def checkpoint_epochs(max_epoch: int, eval_interval: int) -> List[int]:
 def trainer_synapse(cfg: TrainConfig, model, snapshot_path: str, volumes: Optional[Callable[[], list]] = None, group=None,
                     log: Optional[Callable[[str], None]] = None) -> dict:
     """Trains `model` (a transception_amd.MSTransception on the GPU) and returns the history.  `volumes` is a callable that
-    yields the evaluation volumes as (image, label, case) triples (the `.npy.h5` reader needs h5py, see data.SynapseSlices)."""
+    yields the evaluation volumes as (image, label, case) triples (the `.npy.h5` reader needs h5py, see data.SynapseSlices).
+    Under optimizer="adamw" / "adam" the history also holds "optimizer_step", the updates the device counted as applied."""
     log = log or logging.info
     distributed = dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1
     rank = dist.get_rank(group) if distributed else 0
@@ -107,7 +145,7 @@ def trainer_synapse(cfg: TrainConfig, model, snapshot_path: str, volumes: Option
     scaler = loss_scale if isinstance(loss_scale, DynamicLossScale) else None
     loss_fn = SegLoss(cfg.num_classes, group=group, loss_scale=loss_scale, ce_weight=cfg.class_weights, dice_weight=cfg.class_weights,
                       ignore_index=cfg.ignore_index)
-    opt = FusedSGD(model, lr=cfg.base_lr, momentum=0.9, weight_decay=1e-4, clip_norm=5.0 if cfg.grad_clipping else None)
+    opt = make_optimizer(cfg, model)
 
     def lr_at(it: int) -> float:
         """Learning rate of step `it` (0-based).  Cosine: scheduler.step() follows every optimizer.step() (trainer.py:151-153).
@@ -188,4 +226,6 @@ def trainer_synapse(cfg: TrainConfig, model, snapshot_path: str, volumes: Option
                     hist["dice"].append(float(res[0] / res[2].clamp(min=1)))
                     hist["hd95"].append(float(res[1] / res[2].clamp(min=1)))
     hist["iterations"] = iter_num
+    if isinstance(opt, FusedAdamW):
+        hist["optimizer_step"] = opt.device_step()                # updates applied, as the device counted them: iterations minus skipped
     return hist
