@@ -18,7 +18,8 @@
  *  - `dtype` selects the storage type of activations/weights: TC_F32, TC_BF16 or TC_F16 (IEEE half); statistics,
  *    accumulators and every `float*` argument are always fp32; the 16-bit types share every kernel (one matrix-core rate),
  *    they differ in the conversion instructions and the MFMA operand type only;
- *  - return value: TC_OK (0) or a negative TC_ERR_* code; nothing throws across the ABI.
+ *  - return value: TC_OK (0) or a negative TC_ERR_* code; nothing throws across the ABI.  An entry marked TC_QUERY returns a value
+ *    instead (a version, a yes / no, a count or a size); an unmarked entry returns a status.
  */
 #ifndef TRANSCEPTION_HIP_H
 #define TRANSCEPTION_HIP_H
@@ -27,6 +28,8 @@
 extern "C" {
 #endif
 
+#define TC_ABI_VERSION 15
+#define TC_QUERY
 enum { TC_OK = 0, TC_ERR_ARG = -1, TC_ERR_LAUNCH = -2, TC_ERR_UNSUPPORTED = -3 };
 enum { TC_F32 = 0, TC_BF16 = 1, TC_F16 = 2 };
 enum { TC_ACT_NONE = 0, TC_ACT_HSWISH = 1, TC_ACT_COORD = 2, TC_ACT_SIGMOID = 3, TC_ACT_GELU = 4,
@@ -34,7 +37,7 @@ enum { TC_ACT_NONE = 0, TC_ACT_HSWISH = 1, TC_ACT_COORD = 2, TC_ACT_SIGMOID = 3,
        TC_ACT_RELU = 6  /* tc_bn_fwd / tc_bn_bwd only (SE_Block's act(bn(.)), MSTr.py:590) */ };
 
 /* library identity: returns the ABI version (bumped on any signature change) */
-int tc_abi_version(void);
+TC_QUERY int tc_abi_version(void);
 
 /* ------------------------------------------------------------------------------------------
  * GEMM:  C[b] = alpha * op(A[b]) * op(B[b]) (+ bias) (+ R[b]) ; optional sigmoid ; optional C += .
@@ -137,7 +140,7 @@ int tc_layernorm_bwd(const void* dy, int lddy, const void* x, int ldx, const voi
  * first 16 KiB are arrival counters: zero before the first use, left zero).  With it the per-workgroup parameter-gradient
  * partials are folded 16 at a time inside the kernel before anything touches dgamma / dbeta atomically -- one pass over
  * x / dy for dx, dgamma and dbeta together. */
-long long tc_layernorm_bwd_scratch_floats(int rows, int C, int groups);
+TC_QUERY long long tc_layernorm_bwd_scratch_floats(int rows, int C, int groups);
 /* Deferred parameter gradients (the backward of nn.LayerNorm's weight / bias at the same reference lines): tc_layernorm_bwd_defer is
  * tc_layernorm_bwd, but instead of folding its per-workgroup column sums at its tail it leaves them in `part`
  * ([groups][tc_layernorm_bwd_nblk(rows, C)][dgamma C | dbeta C] floats, a buffer of this launch's own, kept until the fold) and returns;
@@ -149,7 +152,7 @@ typedef struct {
     long long pstride;
     int nblk, C, groups;
 } TcLnFold;
-int tc_layernorm_bwd_nblk(int rows, int C);
+TC_QUERY int tc_layernorm_bwd_nblk(int rows, int C);
 int tc_layernorm_bwd_defer(const void* dy, int lddy, const void* x, int ldx, const void* gamma, const void* beta,
                            const float* mean, const float* rstd, void* dx, int lddx, const void* dres, int ldres,
                            float* dgamma, float* dbeta, int rows, int C, int act, int groups, long long pstride,
@@ -187,8 +190,8 @@ int tc_layernorm_ps_bwd(const void* dy, int lddy, const void* x, int ldx, const 
  *   scratch fp32, tc_ln_cls_scratch_floats(rows, ncls) floats (per-workgroup partial sums; folded by the call's second launch)
  * 16-bit storage, c = 64, ncls in {2, 9}: tc_ln_cls_supported; TC_ERR_ARG otherwise (callers keep the op-by-op form).
  * xn is kept in fp32 between the LayerNorm and the product (the op-by-op form rounds it to the storage type). */
-int tc_ln_cls_supported(int C, int ncls, int dtype);
-long long tc_ln_cls_scratch_floats(int rows, int ncls);
+TC_QUERY int tc_ln_cls_supported(int C, int ncls, int dtype);
+TC_QUERY long long tc_ln_cls_scratch_floats(int rows, int ncls);
 int tc_ln_cls_fwd(const void* x, int ldx, const void* gamma, const void* beta, const void* Wc, const void* bc, void* logits, int ldl,
                   float* mean, float* rstd, int B, int H, int W, int p, int C, int ncls, float eps, int dtype, void* stream);
 int tc_ln_cls_bwd(const void* dl, int lddl, const void* x, int ldx, const void* gamma, const void* beta, const void* Wc, const float* mean,
@@ -230,7 +233,7 @@ typedef struct {
     int ch, chunks, gx, nt;                    /* geometry of the sums ([group * chunks + chunk][gx walkers][nt taps][ch channels]): filled by the plans */
 } TcDwFold;
 /* floats the launch will leave (0: this shape cannot defer); fill *site's geometry */
-long long tc_dwconv_bwd_plan(int B, int H, int W, int C, int k, int groups, int dtype, TcDwFold* site);
+TC_QUERY long long tc_dwconv_bwd_plan(int B, int H, int W, int C, int k, int groups, int dtype, TcDwFold* site);
 int tc_dw_fold(const TcDwFold* sites, int n, void* stream);
 int tc_dwconv_bwd(const void* dy, int lddy, const void* x, int ldx, const void* w, void* dx, int lddx, float* dw, float* db, int B, int H,
                   int W, int C, int k, int add_input, int accumulate, int groups, long long wstride, void* ws, long long ws_bytes,
@@ -251,7 +254,7 @@ int tc_dwconv_multi(const TcDwSeg* segs, int nseg, int mode, int add_input, int 
                     void* ws, long long ws_bytes, int dtype, void* stream);
 /* Deferred weight gradients of a mode 2 / 3 launch (ws_bytes < 0, as tc_dwconv_bwd): total floats the launch will leave (0: cannot defer);
  * sites[i] gets segment i's geometry and offs[i] its offset (floats) into the one buffer -- the caller sets part / dw / db / wstride. */
-long long tc_dwconv_multi_plan(const TcDwSeg* segs, int nseg, int groups, int dtype, TcDwFold* sites, long long* offs);
+TC_QUERY long long tc_dwconv_multi_plan(const TcDwSeg* segs, int nseg, int groups, int dtype, TcDwFold* sites, long long* offs);
 
 /* ------------------------------------------------------------------------------------------
  * MixFFN_skip middle (MSTr.py:889-902 with DWConv :21-31): between fc1 and fc2 the reference runs dw3x3(+bias) + skip, LayerNorm(4C),
@@ -260,7 +263,7 @@ long long tc_dwconv_multi_plan(const TcDwSeg* segs, int nseg, int groups, int dt
  *        backward = fc2 input-gradient GEMM with TC_FFN_EP + fc2 weight-gradient GEMM with TC_FFN_LN_B -> tc_ffn_mid_bwd.
  */
 /* channels per statistics chunk of tc_ffn_dw_fwd for a C-channel map of this dtype (C must be a multiple of it) */
-int tc_ffn_chunk(int C, int dtype);
+TC_QUERY int tc_ffn_chunk(int C, int dtype);
 /* y = dw3x3(x) + bias + x on `groups` stacked sets of B images (parameters of set g at + g*wstride), and
  * stat[((g*B + b)*H*W + pixel) * (C / tc_ffn_chunk) + chunk] = float2(sum, squared deviations from the chunk mean) of y's channels. */
 int tc_ffn_dw_fwd(const void* x, int ldx, const void* w, const void* bias, void* y, int ldy, float* stat, int B, int H, int W,
@@ -278,7 +281,7 @@ int tc_ffn_mid_bwd(const TcFfnSeg* segs, int nseg, int groups, long long wstride
                    void* stream);
 /* Deferred parameter gradients of a tc_ffn_mid_bwd launch (ws_bytes < 0, as tc_dwconv_bwd): total floats it will leave (0: cannot defer);
  * sites[i] / offs[i] as tc_dwconv_multi_plan -- the caller sets part, dw, db, dgamma, dbeta and wstride, tc_dw_fold adds them. */
-long long tc_ffn_mid_plan(const TcFfnSeg* segs, int nseg, int groups, int dtype, TcDwFold* sites, long long* offs);
+TC_QUERY long long tc_ffn_mid_plan(const TcFfnSeg* segs, int nseg, int groups, int dtype, TcDwFold* sites, long long* offs);
 
 /* MixFFN_skip forward as ONE spatially tiled kernel (16-bit storage types, C = 64 or 128; see csrc/mixffn.hip):
  *   out = fc2(GELU(LayerNorm_4C(dw3x3(h) + bias + h))) + b2 + res,  h = x W1^T + b1        (MSTr.py:889-902, DWConv :21-31)
@@ -302,7 +305,7 @@ typedef struct TcFfnFused {
                                                                     :906-907), applied as the tile is loaded; null: x is used as it is.  Same
                                                                     per-group stride (wstride) as the other parameters */
 } TcFfnFused;
-int tc_ffn_fused_supported(int C, int dtype);
+TC_QUERY int tc_ffn_fused_supported(int C, int dtype);
 int tc_ffn_fused_fwd(const TcFfnFused* f, int dtype, void* stream);
 
 /* MixFFN_skip backward with the hidden maps kept on the chip (16-bit storage types; see csrc/mixffn_bwd.hip): the autograd backward of
@@ -331,8 +334,8 @@ typedef struct TcFfnBwd {
                                     becomes the gradient of the RAW x (LayerNorm backward applied where dx leaves launch 2) and the fp32
                                     dpre_* receive (+=) the LayerNorm's parameter gradients; null: no LayerNorm */
 } TcFfnBwd;
-int tc_ffn_fused_bwd_supported(int C, int dtype);
-long long tc_ffn_fused_bwd_scratch_floats(int C, int groups);
+TC_QUERY int tc_ffn_fused_bwd_supported(int C, int dtype);
+TC_QUERY long long tc_ffn_fused_bwd_scratch_floats(int C, int groups);
 int tc_ffn_fused_bwd(const TcFfnBwd* f, int dtype, void* stream);
 
 /* ---- EfficientAttention block: out = t + reproj(softmax_c(Q) . (softmax_n(K)^T V)) with K | Q | V = LayerNorm(t) W^T + b ----
@@ -354,8 +357,8 @@ typedef struct TcEffAtt {
     int ldt, ldo, lddo, lddt, acc_dt, C, B, N;
     float eps;
 } TcEffAtt;
-int tc_effatt_supported(int C, int dtype);
-long long tc_effatt_scratch_floats(int C, int B, int N);
+TC_QUERY int tc_effatt_supported(int C, int dtype);
+TC_QUERY long long tc_effatt_scratch_floats(int C, int B, int N);
 int tc_effatt_fwd(const TcEffAtt* f, int dtype, void* stream);
 int tc_effatt_bwd(const TcEffAtt* f, int dtype, void* stream);
 
@@ -370,7 +373,7 @@ int tc_effatt_bwd(const TcEffAtt* f, int dtype, void* stream);
  * stats_chunks > 0 (training only): `partial` ALREADY holds the shifted sums of x in stats_chunks row chunks, left there by the
  *   GEMM that produced x (TcGemm.bn_part; C * (1 + 2 * stats_chunks) floats) -- no statistics pass is launched.  0: computed here.
  */
-long long tc_bn_scratch_floats(int rows, int C);
+TC_QUERY long long tc_bn_scratch_floats(int rows, int C);
 int tc_bn_fwd(const void* x, int ldx, const void* gamma, const void* beta, float* running_mean,
               float* running_var, const void* res, int ldres, void* y, int ldy, float* save_mean,
               float* save_rstd, float* partial, int rows, int C, float eps, float momentum, int training,
@@ -389,7 +392,7 @@ int tc_bn_bwd(const void* dy, int lddy, const void* x, int ldx, const void* gamm
  * axis=0 is split over row ranges (two passes through caller-provided fp32 scratch of tc_softmax_scratch_floats floats);
  * scratch may be NULL for axis=1.
  */
-long long tc_softmax_scratch_floats(int nb, int R, int Ccols);
+TC_QUERY long long tc_softmax_scratch_floats(int nb, int R, int Ccols);
 int tc_softmax_fwd(const void* x, void* y, float* scratch, int nb, long long sbx, long long sby, int R, int Ccols,
                    int ldx, int ldy, int axis, int dtype, void* stream);
 int tc_softmax_bwd(const void* dy, const void* y, void* dx, float* scratch, int nb, long long sbdy, long long sby,
@@ -628,7 +631,7 @@ int tc_seg_loss_bwd_w(const float* prob, const void* logits, int ldl, const long
  * head h owning channels [h*Ch, (h+1)*Ch); convv = crpe(v) (row stride ldc).  stats: tc_factor_att_stats_floats() floats saved for
  * the backward (column max and 1/sum of the key softmax).  Backward: dq/dk/dv share the row stride ldd (slices of the qkv
  * gradient; acc_* = add to what is there), dconvv is overwritten.  Replaces 5 forward + 7 backward launches of the unfused form. */
-long long tc_factor_att_stats_floats(int Bt, int heads, int Ch);
+TC_QUERY long long tc_factor_att_stats_floats(int Bt, int heads, int Ch);
 /* The attention half of an MHCABlock after norm1 in one launch (16-bit storage; C = 64 / 128 / 320 with 8 heads; N = H * W tokens per
  * image small enough for one head's tiles to sit in LDS -- ask tc_mhca_att_supported): per (image, head)
  *   q | k | v = xn Wqkv_h^T + b_h (nn.Linear(C, 3C), MSTr.py:856-862), convv = crpe_h(v) (ConvRelPosEnc, :801-823: heads 0-1 3x3, 2-4 5x5,
@@ -640,15 +643,15 @@ long long tc_factor_att_stats_floats(int Bt, int heads, int Ch);
  * tc_factor_att_bwd followed by tc_dwconv_multi (mode 3) compute: dq | dk | dv into dqkv [.., 3C] (row stride ldd; acc_* = add to what is
  * there), the window's weight / bias gradients ADDED to dw3 / db3 / dw5 / db5 / dw7 / db7 (fp32, laid out like the weights, group g at
  * +g*gs).  go = d loss / d o.  dconvv is not materialised. */
-int tc_mhca_att_supported(int C, int N, int dtype);
+TC_QUERY int tc_mhca_att_supported(int C, int N, int dtype);
 /* tc_dw_ln_fwd: the head of an MHCABlock in one launch (16-bit storage, C = 64 / 128 / 320): t1 = x + dw3x3(x) + bias (ConvPosEnc,
  * MSTr.py:744-752), xn = LayerNorm_C(t1) (norm1, :932, 937), mean / rstd [groups*B*H*W] as tc_layernorm_fwd leaves them.  Parameters of
  * weight group g at +g*wstride (conv) / +g*gstride (norm).  Backward: tc_layernorm_bwd*, then tc_dwconv_bwd -- unchanged. */
-int tc_dw_ln_supported(int C, int dtype);
+TC_QUERY int tc_dw_ln_supported(int C, int dtype);
 int tc_dw_ln_fwd(const void* x, int ldx, const void* w, const void* b, long long wstride, const void* gamma, const void* beta,
                  long long gstride, void* t1, int ldt, void* xn, int ldn, float* mean, float* rstd, int groups, int B, int H, int W,
                  int C, float eps, int dtype, void* stream);
-int tc_mhca_att_bwd_supported(int C, int N, int dtype);
+TC_QUERY int tc_mhca_att_bwd_supported(int C, int N, int dtype);
 int tc_mhca_att_bwd(const void* qkv, int ldq, const void* convv, int ldc, const void* go, int ldgo, const float* stats, void* dqkv,
                     int ldd, int acc_q, int acc_k, int acc_v, const void* w3, const void* w5, const void* w7, float* dw3, float* db3,
                     float* dw5, float* db5, float* dw7, float* db7, long long gs, int groups, int B, int H, int W, int C, float scale,
@@ -694,7 +697,7 @@ int tc_argmax_counts(const void* logits, const long long* labels, unsigned char*
  *   distances at sorted positions floor(0.95 (n-1)) and min(that + 1, n-1); (0, 0, 0) for an empty histogram.  The host forms
  *   sqrt(d2_lo) + (sqrt(d2_hi) - sqrt(d2_lo)) * (0.95 (n-1) - floor(0.95 (n-1))) in fp64. */
 #define TC_METRIC_NO_SOURCE (1 << 28)
-long long tc_metric_hist_bins(int D, int H, int W);
+TC_QUERY long long tc_metric_hist_bins(int D, int H, int W);
 int tc_metric_surfaces(const unsigned char* pred, const unsigned char* gt, unsigned char* surf_pred, unsigned char* surf_gt,
                        long long* counts, int D, int H, int W, int ncls, int zfaces, void* stream);
 int tc_metric_edt(const unsigned char* surf, int k, int* d2, int D, int H, int W, int zfaces, void* stream);
@@ -856,8 +859,8 @@ int tc_cast(const void* src, void* dst, long long n, int src_dtype, int dst_dtyp
  *   part_out = shift[C] | S1[T][C] | S2[T][C], T = tc_ripm_tiles(B, Ho, Wo): sums of (z - shift) and (z - shift)^2 per 8 x 8-pixel tile
  *   (shift = shift_out[C] or 0) -- pass it to tc_bn_fwd(stats_chunks = T) / the next tc_ripm_fwd(part_in, chunks_in = T).
  * Backward: tc_bn_bwd, tc_gemm_pair, tc_dwconv_bwd* on the tensors left here -- unchanged. */
-int tc_ripm_supported(int C, int dtype);
-int tc_ripm_tiles(int B, int Ho, int Wo);
+TC_QUERY int tc_ripm_supported(int C, int dtype);
+TC_QUERY int tc_ripm_tiles(int B, int Ho, int Wo);
 int tc_ripm_fwd(const void* xin, int ldx, int bn_in, const float* part_in, int chunks_in, const void* gamma, const void* beta,
                 float* running_mean, float* running_var, float* save_mean, float* save_rstd, float eps, float momentum,
                 int training, void* xnorm, int ldn, const void* wd, const void* wp, void* y, int ldy, void* z, int ldz,
@@ -869,7 +872,7 @@ int tc_ripm_fwd(const void* xin, int ldx, int bn_in, const float* part_in, int c
  * 167-170).  `groups` row blocks of `rows` rows, group g's parameters at +g*wstride (W, b) / +g*gstride (gamma, beta).  Every pointer
  * 16-byte aligned, ld* and both strides multiples of 8 elements (TC_ERR_ARG otherwise).  Backward: tc_layernorm_bwd*, then tc_gemm_pair --
  * unchanged. */
-int tc_linear_ln_supported(int C, int dtype);
+TC_QUERY int tc_linear_ln_supported(int C, int dtype);
 int tc_linear_ln_fwd(const void* x, int ldx, const void* w, const void* b, long long wstride, const void* res, int ldr, const void* gamma,
                      const void* beta, long long gstride, void* t, int ldt, void* xn, int ldn, float* mean, float* rstd, int groups,
                      int rows, int C, float eps, int dtype, void* stream);

@@ -13,14 +13,13 @@ from layout_ref import col2im3s2_ref, im2col3s2_ref, stem_im2col_ref, tokens_to_
 
 pytestmark = pytest.mark.gpu
 
-from transception_amd._lib import EW_COPY, EW_DEINTERLEAVE, EW_PATCHIFY, TC_BF16, TC_F16, TC_F32, TcError, TcEwSeg, lib  # noqa: E402
+from transception_amd._lib import EW_COPY, EW_DEINTERLEAVE, EW_MULTI_MAX, EW_PATCHIFY, TC_BF16, TC_F16, TC_F32, TcError, TcEwSeg, lib  # noqa: E402
 from transception_amd.seeded_init import seeded_tensor  # noqa: E402
 
 DEV = "cuda:0"
 DTYPES = [torch.float32, torch.bfloat16, torch.float16]
 TC = {torch.float32: TC_F32, torch.bfloat16: TC_BF16, torch.float16: TC_F16}
 SENT = -96.0                       # exact in every storage type, outside the grid's sums (|sum of five| <= 20)
-EW_MULTI_MAX = 4                   # TC_EW_MULTI_MAX of include/transception_hip.h
 
 
 def _name(dtype):

@@ -19,7 +19,7 @@ from typing import Callable, Dict, List, Optional, Tuple
 import torch
 
 from ._lib import (ATTN_DKV_SPLITS, EW_COPY, EW_DEINTERLEAVE, EW_PATCHIFY, TcEffAtt, TcEwSeg, TcFfnBwd, TcFfnFused, ACT_COORD, ACT_GELU, ACT_HSWISH, ACT_NONE, ACT_SCALE, ACT_SIGMOID, FFN_EP, FFN_LN_A, FFN_LN_B, TC_BF16, TC_F16, TC_F32, TcDwFold, TcDwSeg, TcFfnSeg,
-                   TcGemm, lib)
+                   TcGemm, TcLnFold, lib)
 
 _DT = {torch.float32: TC_F32, torch.bfloat16: TC_BF16, torch.float16: TC_F16}
 
@@ -437,7 +437,6 @@ class Graph:
         self._flush_dw_folds()
         if not self._ln_pending:
             return
-        from ._lib import TcLnFold
         arr = (TcLnFold * len(self._ln_pending))()
         for i, (part, dg, db, gs, nblk, Cc, Gn) in enumerate(self._ln_pending):
             arr[i].part, arr[i].dgamma, arr[i].dbeta, arr[i].pstride = _ptr(part), _ptr(dg), _ptr(db), gs

@@ -19,7 +19,7 @@ from typing import Optional, Union
 import torch
 import torch.distributed as dist
 
-from ._lib import TC_BF16, TC_F16, TC_F32, lib
+from ._lib import TC_BF16, TC_F16, TC_F32, TC_IGNORE_NONE, lib
 
 
 def _dt(t: torch.Tensor) -> int:
@@ -79,7 +79,7 @@ def loss_from_sums(sums: torch.Tensor, n_pix: float, w_ce: float, w_dice: float,
     return w_ce * ce + w_dice * dice, ce, dice
 
 
-IGNORE_NONE = -2 ** 31           # include/transception_hip.h TC_IGNORE_NONE: "no ignore_index" for the tc_seg_loss_*_w entries
+IGNORE_NONE = TC_IGNORE_NONE     # "no ignore_index" for the tc_seg_loss_*_w entries
 
 
 def check_class_weights(name: str, w, ncls: int, need_positive: bool) -> Optional[tuple]:
