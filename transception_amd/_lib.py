@@ -1,7 +1,8 @@
 """ctypes binding of libtransception_hip.so -- the only way the Python host reaches the GPU arithmetic.
 
 The binding is derived from include/transception_hip.h at import (_header.py): signatures, structs and constants are written
-once, in the header.  What stands here is the list of names the host imports.
+once, in the header.  What stands here is the list of names the host imports.  The connected-component post-processing entries,
+which replace no reference call site, have a header and a version of their own (include/transception_post.h -> POST).
 
 There is deliberately NO fallback: if the shared library is missing or a call returns a non-zero
 status the host raises.  (The CPU oracle under oracle/ is test infrastructure and is never imported here.)
@@ -19,6 +20,7 @@ LIB_PATH = os.environ.get("TC_LIB_PATH") or os.path.join(HERE, "libtransception_
 ABI = _header.load()
 SIGNATURES = {name: f.argtypes for name, f in ABI.functions.items()}     # every pointer is a c_void_p: byref(), arrays, addresses, None
 K, S = ABI.constants, ABI.structs
+POST = _header.load(os.path.join(os.path.dirname(_header.HEADER), "transception_post.h"))    # connected-component post-processing: a header of its own
 
 ABI_VERSION = K["TC_ABI_VERSION"]
 TC_F32, TC_BF16, TC_F16 = K["TC_F32"], K["TC_BF16"], K["TC_F16"]
@@ -31,6 +33,8 @@ TC_AUG_SKIP, TC_AUG_FROM_RAW = K["TC_AUG_SKIP"], K["TC_AUG_FROM_RAW"]
 ATTN_DKV_SPLITS = K["TC_ATTN_DKV_SPLITS"]
 TC_METRIC_NO_SOURCE, TC_METRIC_SELECT_WORK_BYTES = K["TC_METRIC_NO_SOURCE"], K["TC_METRIC_SELECT_WORK_BYTES"]
 TC_IGNORE_NONE = K["TC_IGNORE_NONE"]
+POST_ABI_VERSION = POST.constants["TC_POST_ABI_VERSION"]
+TC_CC_LARGEST, TC_CC_MIN_VOXELS = POST.constants["TC_CC_LARGEST"], POST.constants["TC_CC_MIN_VOXELS"]
 
 TcGemm, TcLnFold, TcDwFold, TcDwSeg, TcFfnSeg = S["TcGemm"], S["TcLnFold"], S["TcDwFold"], S["TcDwSeg"], S["TcFfnSeg"]
 TcFfnFused, TcFfnBwd, TcEffAtt, TcEwSeg, TcSliceAug = S["TcFfnFused"], S["TcFfnBwd"], S["TcEffAtt"], S["TcEwSeg"], S["TcSliceAug"]
@@ -49,7 +53,7 @@ class _Lib:
                           "(there is no CPU/PyTorch fallback for the TransCeption hot path)")
         self.path = path
         self.cdll = C.CDLL(path)
-        for name, f in ABI.functions.items():
+        for name, f in (*ABI.functions.items(), *POST.functions.items()):
             fn = getattr(self.cdll, name)          # AttributeError if a declared symbol is not exported
             fn.argtypes = f.argtypes
             fn.restype = f.restype
@@ -57,6 +61,9 @@ class _Lib:
         v = self.cdll.tc_abi_version()
         if v != ABI_VERSION:
             raise TcError(f"ABI mismatch: library {v}, host {ABI_VERSION}")
+        v = self.cdll.tc_post_abi_version()
+        if v != POST_ABI_VERSION:
+            raise TcError(f"post-processing ABI mismatch: library {v}, host {POST_ABI_VERSION}")
 
     @staticmethod
     def _checked(name, fn):

@@ -20,9 +20,15 @@ that is exact integer work: int32 maps and a histogram indexed by the squared di
 one positive float per array axis, or a scalar for all) the maps are float64 and the order statistics come from a radix select
 over the doubles' bit patterns; the sums of squares differ from scipy's by rounding only.  Both metric paths take it, through
 `calculate_metric_percase`, `evaluate_volume`, `inference` and `TrainConfig.voxelspacing`.
+
+Connected-component post-processing (`PostProcess`; the reference has no such step) removes stray islands from the prediction before
+either metric: per class keep the largest component, or every component of at least N voxels.  `postprocess_device` runs it on the GPU
+(csrc/postprocess.hip: a lock-free union-find, integer atomics only), `postprocess_host` is the same definition on scipy.ndimage.label;
+include/transception_post.h states the definition.  `postprocess=None`, the default everywhere, changes nothing.
 """
 from __future__ import annotations
 
+from dataclasses import dataclass
 from typing import List, Optional, Tuple
 
 import math
@@ -30,7 +36,7 @@ import math
 import numpy as np
 import torch
 
-from ._lib import TC_F32, TC_METRIC_SELECT_WORK_BYTES, lib
+from ._lib import TC_CC_LARGEST, TC_CC_MIN_VOXELS, TC_F32, TC_METRIC_SELECT_WORK_BYTES, lib
 
 NO_CPU = "transception_amd.evaluate runs on MI355X only (no CPU fallback)"
 
@@ -254,6 +260,119 @@ def hd95_device(result: torch.Tensor, reference: torch.Tensor, voxelspacing=None
     return hd95_from_order_stats(*sel[1])
 
 
+POST_MODES = ("largest", "min_voxels")
+
+
+@dataclass(frozen=True)
+class PostProcess:
+    """Connected-component post-processing of a predicted label volume, per class 1..classes-1 (include/transception_post.h):
+    mode "largest" keeps the largest component of every class (a tie goes to the component that comes first in raster order),
+    mode "min_voxels" every component of at least `min_voxels` voxels; the rest becomes background.  connectivity 1: face neighbours
+    (scipy's generate_binary_structure(ndim, 1)), 3: the full neighbourhood (generate_binary_structure(ndim, ndim))."""
+    mode: str = "largest"
+    min_voxels: int = 0
+    connectivity: int = 1
+
+    def __post_init__(self):
+        if self.mode not in POST_MODES:
+            raise ValueError(f"mode must be one of {POST_MODES}, got {self.mode!r}")
+        n = self.min_voxels
+        if isinstance(n, bool) or not isinstance(n, (int, np.integer)):
+            raise ValueError(f"min_voxels must be an integer, got {n!r}")
+        if self.mode == "min_voxels" and not 1 <= n < 2 ** 63:
+            raise ValueError(f'mode "min_voxels" needs 1 <= min_voxels < 2^63, got {n!r}')
+        if self.mode == "largest" and n != 0:
+            raise ValueError(f'min_voxels belongs to mode "min_voxels" (leave it 0 with "largest"), got {n!r}')
+        if self.connectivity not in (1, 3) or isinstance(self.connectivity, bool):
+            raise ValueError(f"connectivity must be 1 (faces) or 3 (full neighbourhood), got {self.connectivity!r}")
+
+
+def postprocess_scratch_bytes(shape) -> int:
+    """What `postprocess_device` allocates beside its output: the int32 root and size maps, 8 bytes a voxel (the int64 [classes,2] record
+    of the largest components is not counted).  0 for a shape outside the library's limits."""
+    return int(lib().tc_cc_scratch_bytes(*_shape3(shape)))
+
+
+def _label_volume(lab: torch.Tensor) -> Tuple[int, int, int]:
+    if not lab.is_cuda:
+        raise RuntimeError(NO_CPU)
+    if lab.dtype != torch.uint8:
+        raise ValueError("connected components on the device take a uint8 label volume")
+    return _shape3(lab.shape)
+
+
+def component_roots(lab: torch.Tensor, classes: int, connectivity: int = 1) -> torch.Tensor:
+    """int32 map of lab's shape: for a foreground voxel (1 <= label < classes) the smallest linear index of its connected component, -1 for
+    background (tc_cc_label).  Nothing is synchronised; limits and errors are the library's (`TcError`)."""
+    shape = _label_volume(lab)
+    root = torch.empty(lab.shape, dtype=torch.int32, device=lab.device)
+    lib().tc_cc_label(lab.contiguous().data_ptr(), root.data_ptr(), *shape, classes, connectivity, torch.cuda.current_stream(lab.device).cuda_stream)
+    return root
+
+
+def component_sizes(lab: torch.Tensor, root: torch.Tensor, classes: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(size, best) from `component_roots`' map of the same volume: size is int32 of lab's shape, the voxel count of a component at its root
+    and 0 elsewhere; best is int64 [classes,2], (voxels, root) of the largest component of every class -- a tie goes to the smaller root --
+    and (0, -1) for a class without a voxel (tc_cc_sizes).  Nothing is synchronised."""
+    shape = _label_volume(lab)
+    if not root.is_cuda:
+        raise RuntimeError(NO_CPU)
+    if root.dtype != torch.int32 or root.shape != lab.shape or not root.is_contiguous():
+        raise ValueError("root is the contiguous int32 map `component_roots` returned for this volume")
+    size = torch.empty(lab.shape, dtype=torch.int32, device=lab.device)
+    best = torch.empty((classes, 2), dtype=torch.int64, device=lab.device)
+    lib().tc_cc_sizes(lab.contiguous().data_ptr(), root.data_ptr(), size.data_ptr(), best.data_ptr(), *shape, classes,
+                      torch.cuda.current_stream(lab.device).cuda_stream)
+    return size, best
+
+
+def postprocess_device(pred: torch.Tensor, classes: int = 9, post: PostProcess = PostProcess(), out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """`post` applied to the uint8 CUDA label volume `pred` ([D,H,W], or [H,W]: true 2-D), on the device: a new tensor, or `out` (uint8, pred's
+    shape; `out is pred` works in place).  Labels 0 and >= classes pass through unchanged.  Scratch: `postprocess_scratch_bytes`, 8 bytes
+    a voxel.  Nothing is synchronised."""
+    shape = _label_volume(pred)
+    if out is not None and (not out.is_cuda or out.dtype != torch.uint8 or out.shape != pred.shape):
+        raise ValueError("`out` is a uint8 CUDA tensor of pred's shape")
+    lab = pred.contiguous()
+    root = component_roots(lab, classes, post.connectivity)
+    size, best = component_sizes(lab, root, classes)
+    dst = out if out is not None and out.is_contiguous() else (lab if out is pred else torch.empty_like(lab))
+    lib().tc_cc_keep(lab.data_ptr(), root.data_ptr(), size.data_ptr(), best.data_ptr(), dst.data_ptr(),
+                     TC_CC_LARGEST if post.mode == "largest" else TC_CC_MIN_VOXELS, int(post.min_voxels), *shape, classes,
+                     torch.cuda.current_stream(pred.device).cuda_stream)
+    if out is None:
+        return dst
+    if dst is not out:
+        out.copy_(dst)
+    return out
+
+
+def postprocess_host(pred: np.ndarray, classes: int = 9, post: PostProcess = PostProcess()) -> np.ndarray:
+    """The same step on the host, with scipy.ndimage.label per class: a new array.  scipy numbers components in raster order of their first
+    voxel, so numpy.argmax over their sizes picks, among equally large ones, the one with the smaller root: the device's tie rule."""
+    from scipy.ndimage import generate_binary_structure, label
+    pred = np.asarray(pred)
+    if pred.dtype != np.uint8 or pred.ndim not in (2, 3):
+        raise ValueError("post-processing takes a uint8 label volume [D,H,W] or [H,W]")
+    if not 2 <= classes <= 16:
+        raise ValueError("classes must be in 2..16")
+    structure = generate_binary_structure(pred.ndim, 1 if post.connectivity == 1 else pred.ndim)
+    out = pred.copy()
+    for k in range(1, classes):
+        comp, ncomp = label(pred == k, structure=structure)
+        if ncomp == 0:
+            continue
+        sizes = np.bincount(comp.ravel(), minlength=ncomp + 1)
+        if post.mode == "largest":
+            keep = np.zeros(ncomp + 1, bool)
+            keep[1 + int(np.argmax(sizes[1:]))] = True
+        else:
+            keep = sizes >= post.min_voxels
+        keep[0] = True                                                   # not of class k: untouched
+        out[~keep[comp]] = 0
+    return out
+
+
 @torch.no_grad()
 def predict_slices(model, slices: torch.Tensor, batch: int = 16) -> torch.Tensor:
     """slices: float [N,H,W] in [0,1] at the network size (a multiple of 32); returns uint8 [N,H,W] labels.
@@ -303,13 +422,18 @@ def zoom_labels(pred: torch.Tensor, size: Tuple[int, int]) -> torch.Tensor:
 
 @torch.no_grad()
 def evaluate_volume(model, image: np.ndarray, label: np.ndarray, classes: int = 9, patch_size=(224, 224),
-                    batch: int = 16, with_hd95: bool = False, host_zoom: bool = False, device_metrics: bool = False, voxelspacing=None):
+                    batch: int = 16, with_hd95: bool = False, host_zoom: bool = False, device_metrics: bool = False, voxelspacing=None,
+                    postprocess: Optional[PostProcess] = None):
     """`test_single_volume` for one [D,H,W] volume (utils.py:63-98): per-class Dice for classes 1..classes-1, or with
     `with_hd95` the reference's metric_list of (dice, hd95) pairs.  The volume goes to the GPU once; the order-3 zoom to the network
     size, inference, argmax and the order-0 zoom back all run there (host_zoom=True: scipy per slice, as the reference does).
     `device_metrics=True`: the prediction stays on the GPU, the label volume is uploaded once and `metrics_device` (with_hd95) or the
     counts of its first kernel (Dice only) replace the host metric; same returned structure.  `voxelspacing`: the (z, y, x) size of a voxel
-    of `label`, for the HD95 of either metric path (Dice does not depend on it)."""
+    of `label`, for the HD95 of either metric path (Dice does not depend on it).  `postprocess`: a `PostProcess` applied in 3-D to the
+    prediction at `label`'s resolution (after the order-0 zoom back) before either metric path: on the device wherever the prediction is
+    there (host_zoom=False, whatever `device_metrics` is), else on the host; None: no such step."""
+    if postprocess is not None and not isinstance(postprocess, PostProcess):
+        raise ValueError(f"postprocess must be None or a PostProcess, got {postprocess!r}")
     dev = next(model.parameters()).device
     if device_metrics and dev.type != "cuda":
         raise RuntimeError(NO_CPU)
@@ -321,11 +445,15 @@ def evaluate_volume(model, image: np.ndarray, label: np.ndarray, classes: int = 
         pred = predict_slices(model, torch.from_numpy(sl.astype(np.float32)).to(dev), batch).cpu().numpy()
         if resize:
             pred = np.stack([zoom(pred[d], (X / patch_size[0], Y / patch_size[1]), order=0) for d in range(D)])
+        if postprocess is not None:
+            pred = postprocess_host(pred, classes, postprocess)
     else:
         vol = torch.from_numpy(np.ascontiguousarray(image, np.float32)).to(dev)
         sl = zoom_volume_to_network(vol, tuple(patch_size)) if resize else vol
         pred_d = predict_slices(model, sl, batch)
         pred = zoom_labels(pred_d, (X, Y)) if resize else pred_d
+        if postprocess is not None:
+            pred = postprocess_device(pred, classes, postprocess, out=pred)
         if not device_metrics:
             pred = pred.cpu().numpy()
     if device_metrics:
@@ -344,13 +472,13 @@ def evaluate_volume(model, image: np.ndarray, label: np.ndarray, classes: int = 
 
 
 def inference(model, volumes, classes: int = 9, img_size: int = 224, batch: int = 16, log=None,
-              device_metrics: bool = False, voxelspacing=None) -> Tuple[float, float]:
+              device_metrics: bool = False, voxelspacing=None, postprocess: Optional[PostProcess] = None) -> Tuple[float, float]:
     """trainer.py:25-47: mean Dice and mean HD95 over `volumes` = iterable of (image [D,H,W] in [0,1], label [D,H,W], case name).
-    `device_metrics`, `voxelspacing` (one spacing for every volume): as in `evaluate_volume`."""
+    `device_metrics`, `voxelspacing` (one spacing for every volume), `postprocess`: as in `evaluate_volume`."""
     total, n = 0.0, 0
     for i, (image, label, name) in enumerate(volumes):
         m = np.array(evaluate_volume(model, np.asarray(image), np.asarray(label), classes, (img_size, img_size), batch, with_hd95=True,
-                                     device_metrics=device_metrics, voxelspacing=voxelspacing))
+                                     device_metrics=device_metrics, voxelspacing=voxelspacing, postprocess=postprocess))
         total = total + m
         n += 1
         if log:

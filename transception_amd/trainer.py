@@ -25,7 +25,7 @@ import torch
 import torch.distributed as dist
 
 from .data import DeviceLoader, SynapseSlices
-from .evaluate import inference
+from .evaluate import PostProcess, inference
 from .train import DynamicLossScale, FusedAdamW, FusedSGD, GraphedStep, SegLoss, check_class_weights, check_ignore_index, cosine_lr, train_step
 
 OPTIMIZERS = ("sgd", "adamw", "adam")
@@ -50,6 +50,7 @@ class TrainConfig:
     graphed: bool = True               # replay the captured step (hipGraph); False launches every kernel from Python
     device_metrics: bool = False       # Dice / HD95 of the evaluation on the GPU (evaluate.metrics_device) instead of scipy on the host
     voxelspacing: Optional[tuple] = None   # (z, y, x) voxel size for the HD95 of the evaluation, on either metric path; None: in voxels
+    postprocess: Optional[PostProcess] = None   # connected-component post-processing of the evaluation's predictions (evaluate.PostProcess); None: none
     log_every: int = 1                 # iterations between log lines (each one reads three scalars back from the GPU)
     loss_scale: Union[None, float, str] = None   # float16 storage: None = no scale (1), a number = static scale, "dynamic" = a default
                                        # train.DynamicLossScale (device-resident, adjusts itself inside the captured step)
@@ -81,6 +82,8 @@ class TrainConfig:
             raise ValueError(f'no_decay must be None or "norm_bias", got {self.no_decay!r}')
         if self.no_decay is not None and self.optimizer == "sgd":
             raise ValueError("no_decay needs optimizer=\"adamw\" or \"adam\": the SGD kernel takes one decay for all segments")
+        if self.postprocess is not None and not isinstance(self.postprocess, PostProcess):
+            raise ValueError(f"postprocess must be None or an evaluate.PostProcess, got {self.postprocess!r}")
         make_loss_scale(self.loss_scale)
         check_class_weights("class_weights", self.class_weights, self.num_classes, need_positive=True)
         check_ignore_index(self.ignore_index, self.num_classes)
@@ -218,7 +221,7 @@ def trainer_synapse(cfg: TrainConfig, model, snapshot_path: str, volumes: Option
                         if rank == 0:
                             log(f"Running Inference after epoch {epoch_num}")
                         mean_dice, mean_hd95 = inference(model, vols, cfg.num_classes, cfg.img_size, log=log, device_metrics=cfg.device_metrics,
-                                                        voxelspacing=cfg.voxelspacing)
+                                                        voxelspacing=cfg.voxelspacing, postprocess=cfg.postprocess)
                         res[0], res[1], res[2] = mean_dice * len(vols), mean_hd95 * len(vols), len(vols)
                         model.train()
                     if distributed:
