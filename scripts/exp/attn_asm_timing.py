@@ -1,5 +1,5 @@
 """Per-wave s_memtime stamps of the hand-scheduled attention forward (libattn_timing.so = csrc/attention_seg.hip built with
-TC_ATTN_TIMING=1 python csrc/gen_attn_asm.py): entry, asm start, prologue end, first body end, loop end, drain end, epilogue end, exit."""
+python csrc/gen_attn_asm.py --timing --out PATH): entry, asm start, prologue end, first body end, loop end, drain end, epilogue end, exit."""
 import ctypes as C, os, sys, numpy as np, torch
 here = os.path.dirname(os.path.abspath(__file__))
 import glob

@@ -214,23 +214,24 @@ __global__ __launch_bounds__(FW_NT, 1) void attn_fwd_seg_kernel(const bf16_t* __
 
 // Forward, hand-scheduled (the default for 16-bit storage; the kernel above stays as the generic fallback and the A/B baseline).
 // Same decomposition -- one 12-wave workgroup per CU, a 32-query tile per wave -- but the whole key loop of a wave is one
-// instruction stream emitted by gen_attn_asm.py (attn_fwd_asm.inc; the reasons and the measurements are in that file's header):
+// instruction stream emitted by gen_attn_asm.py (attn_fwd_asm.inc; the reasons and the measurements are in that file's header; the
+// macro assembler it is spelled in, asm_stream.py, is shared with the dQ and dK/dV streams below):
 // software-pipelined so that every group of four MFMAs carries softmax arithmetic or fragment reads of another sub-tile, which
 // keeps the twelve waves from running their matrix and VALU phases in lock step.  Scores are produced directly as
 // s * scale * log2(e) - m: Q is scaled when it is staged and -m is the C operand of the first QK^T MFMA, so the softmax is
 // max3 tree + exp2 + add + pack per score.  K / V sub-tiles of 32 keys go through a 12-slot LDS ring (buffer loads six
 // sub-tiles ahead: waves 0-3 stage K, waves 4-7 V, one 16-byte chunk per thread; one barrier per FOUR sub-tiles).  This function stages
 // Q and the first five sub-tiles, hands the addresses to the stream and stores the O tile / lse the stream leaves in the wave's LDS tile.
+// The .inc also carries the ring layout the stream was generated for (TC_AS_*: row pitch, slot size, slots, sub-tiles ahead, barrier
+// period) and, as a comment, the order of the asm operands: the constants below come from it or are checked against it.
 #include "attn_fwd_asm.inc"
 typedef int tc_i32x4 __attribute__((ext_vector_type(4)));
-// LDS: 12 ring slots of one 32-key K | V sub-tile; the twelve 32-query wave tiles (Q in, O out) alias slots 6-11, which the stream
-// does not store to before every wave has read its Q fragments and does not read after the barrier in front of the O tiles.
-#ifndef TC_AS_AHEAD
-#define TC_AS_AHEAD 6                                            // keep in sync with AHEAD of gen_attn_asm.py (TC_ATTN_AHEAD)
-#endif
-constexpr int AS_NW = 12, AS_VOFF = 32 * LDR * 2, AS_SLOT = 2 * AS_VOFF, AS_NSLOT = 12, AS_AHEAD = TC_AS_AHEAD, AS_WT = 32 * LDR * 2, AS_WT0 = 6 * AS_SLOT,
-              AS_LSE0 = AS_NSLOT * AS_SLOT;
-static_assert(AS_WT0 + AS_NW * AS_WT <= AS_LSE0, "wave tiles must fit in the ring");
+// LDS: 12 ring slots of one 32-key K | V sub-tile; the twelve 32-query wave tiles (Q in, O out) alias the last slots (6-11), which the
+// stream does not store to before every wave has read its Q fragments and does not read after the barrier in front of the O tiles.
+constexpr int AS_NW = 12, AS_VOFF = 32 * LDR * 2, AS_SLOT = 2 * AS_VOFF, AS_NSLOT = TC_AS_NSLOT, AS_AHEAD = TC_AS_AHEAD, AS_WT = 32 * LDR * 2,
+              AS_LSE0 = AS_NSLOT * AS_SLOT, AS_WT0 = AS_LSE0 - AS_NW * AS_WT;
+static_assert(LDR * 2 == TC_AS_LDR_B && AS_SLOT == TC_AS_SLOT_B, "the ring layout of the forward stream (gen_attn_asm.py)");
+static_assert(AS_WT0 % AS_SLOT == 0 && AS_WT0 >= (AS_AHEAD - 1) * AS_SLOT, "wave tiles alias whole ring slots behind the ones staged before the stream");
 #ifdef TC_ATTN_ASM_TIMING
 constexpr size_t AS_SMEM = AS_LSE0 + AS_NW * 32 * sizeof(float) + 8192;
 __device__ unsigned long long g_attn_dbg[256 * 12 * 8];
@@ -748,6 +749,8 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_bwd_dkv_seg_kernel(const bf16
 // and ring (attn_fwd_asm_kernel), K rows in tc_krow order and V rows in natural order.  This function computes the row deltas (and the
 // per-tile statistics of the dK/dV stream), stages sub-tiles 0..4, runs the stream and stores the dQ tile it leaves in the wave's LDS tile.
 #include "attn_dq_asm.inc"
+static_assert(TC_DQ_LDR_B == TC_AS_LDR_B && TC_DQ_SLOT_B == TC_AS_SLOT_B && TC_DQ_NSLOT == TC_AS_NSLOT && TC_DQ_AHEAD == TC_AS_AHEAD &&
+              TC_DQ_PERIOD == TC_AS_PERIOD, "the dQ stream was generated for the forward stream's ring (same --ahead for both generators)");
 template <typename H>
 __global__ __launch_bounds__(AS_NW * 64, 1) void attn_bwd_dq_asm_kernel(const bf16_t* __restrict__ Q, int ldq, const bf16_t* __restrict__ K, int ldk,
                                                                         const bf16_t* __restrict__ V, int ldv, long long skv,
@@ -858,9 +861,14 @@ __global__ __launch_bounds__(AS_NW * 64, 1) void attn_bwd_dq_asm_kernel(const bf
 // (4 x 32 keys of one image, one chunk of that image's 32-query tiles), every wave owns 32 keys -- with the 32-query sub-tiles of
 // Q | dO | statistics streaming through an 8-slot LDS ring (buffer loads six sub-tiles ahead, one barrier per two sub-tiles).  This
 // function stages sub-tiles 0..4 and the parameter block, runs the stream and stores the [d][key] fp32 tiles it leaves in LDS.
+// The ring layout (TC_DA_*) comes with the .inc, as do the orders of the asm operands and of the parameter block (comments there).
 #include "attn_dkv_asm.inc"
-constexpr int DA_TILE = 32 * LDR * 2, DA_SLOT = 2 * DA_TILE + 256, DA_NSLOT = 8, DA_AHEAD = 6, DA_PRM0 = DA_NSLOT * DA_SLOT, DA_SMEM = DA_PRM0 + 64;
+constexpr int DA_TILE = 32 * LDR * 2, DA_SLOT = 2 * DA_TILE + 256, DA_NSLOT = TC_DA_NSLOT, DA_AHEAD = TC_DA_AHEAD, DA_PRM0 = DA_NSLOT * DA_SLOT,
+              DA_SMEM = DA_PRM0 + 64;
 constexpr int DA_RED = D * 33 * 4;
+static_assert(LDR * 2 == TC_DA_LDR_B && DA_TILE == TC_DA_TILE_B && DA_SLOT == TC_DA_SLOT_B && DA_RED == TC_DA_RED_B,
+              "the ring and accumulator tile layout of the dK/dV stream (gen_dkv_asm.py)");
+static_assert(TC_DA_NPRM * 4 <= DA_SMEM - DA_PRM0, "the parameter block fits behind the ring");
 static_assert(4 * 2 * DA_RED <= DA_NSLOT * DA_SLOT, "the accumulator tiles of the four waves fit the ring");
 // PAIR = 2: an 8-wave workgroup whose two halves take two query chunks of the same 128 keys -- each half with its own ring and parameter
 // block, the barriers of the stream shared (the chunks are equally long by construction: see the host) -- and add their accumulator tiles
@@ -917,6 +925,8 @@ __global__ __launch_bounds__(256 * PAIR, 3 - PAIR) void attn_bwd_dkv_asm_kernel(
         }
     }
     if (tid < 16) {
+        constexpr int nprm = 13;                                // the cases below, in the order of the generator's PARAMS (the .inc lists it)
+        static_assert(nprm == TC_DA_NPRM, "the switch fills exactly the parameter dwords the dK/dV stream reads");
         int v = 0;
         switch (tid) {
             case 0: v = nsub; break;
@@ -944,11 +954,7 @@ __global__ __launch_bounds__(256 * PAIR, 3 - PAIR) void attn_bwd_dkv_asm_kernel(
         const unsigned wq = lds0 + tc_krow(sr) * (LDR * 2) + 16 * sc, ws = lds0 + 2 * DA_TILE + 16 * (tid & 15);
         const unsigned rb = lds0 + tc_krow(pi_row(j)) * (LDR * 2) + 16 * h;
         const unsigned tb = lds0 + (16 * h + 4 * (gi >> 2)) * (LDR * 2) + 32 * gq + 8 * (gi & 3);
-#ifdef TC_DKV_B128STATS
-        const unsigned sb = lds0 + 2 * DA_TILE + 64 * h;
-#else
         const unsigned sb = lds0 + 2 * DA_TILE + 4 * (16 * h + (lane & 15));
-#endif
         const unsigned ko = (unsigned)((key * ldk + 8 * h) * 2), vo = (unsigned)((key * ldv + 8 * h) * 2);
         const unsigned red = lds0 + wave * (2 * DA_RED) + (4 * h * 33 + j) * 4;
         const unsigned prm = lds0 + DA_PRM0;

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Emits the hand-scheduled gfx950 instruction stream of the bridge SR-attention dK / dV kernel (attn_bwd_dkv_asm_kernel in
-attention_seg.hip), with the macro assembler of gen_attn_asm.py (counted waits, wait-state padding, back-edge queue check).
+attention_seg.hip), with the macro assembler of asm_stream.py (counted waits, wait-state padding, back-edge queue check, loop skeleton);
+this file holds the dK / dV stream's register map, operand list, parameter block, ring layout and schedule.
 
 The compiler-scheduled kernel (attn_bwd_dkv_seg_kernel) holds 210 registers, so two waves share a SIMD and neither covers the other's
 dependent chain S/dP MFMAs -> exp2 / multiply / pack -> dV^T/dK^T MFMAs: 78 us per launch at 224^2 B=16, a third of what its
@@ -21,23 +22,22 @@ refills the same registers with the fragment MFMA i of the NEXT group needs.
 Arithmetic = attn_bwd_dkv_seg_kernel<H, 4, true> (Q stored as q * scale * log2 e): dV = P^T dO, dK = ln 2 * dS^T Q, dS = P (dP - delta).
 
     python gen_dkv_asm.py            # writes attn_dkv_asm.inc next to this file
+    python gen_dkv_asm.py --ablate nolds,nobar --out PATH            # an experiment build (scripts/exp): never the committed file
 """
 from __future__ import annotations
 
 import os
-import sys
 
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from gen_attn_asm import Gen, Ins, areg, check_hazards, cvt_name, regs, vreg  # noqa: E402
+import asm_stream
+from asm_stream import AHEAD, LDR_B, Gen, areg, cvt_name, interleave, regs, vreg
 
-# layout shared with attn_bwd_dkv_asm_kernel (keep in sync with the DA_* constants there) --------------------------------------------
-LDR_B = 144                      # bytes per LDS row: 64 halfs + 8 pad
+# ring layout: written into the .inc as TC_DA_*, where attn_bwd_dkv_asm_kernel takes it from --------------------------------------------
 TILE_B = 32 * LDR_B               # one 32-row operand tile
 SLOT_B = 2 * TILE_B + 256         # ring slot: Q tile | dO tile | 32 x (-lse log2 e) | 32 x (-delta)
-OFF_G, OFF_L, OFF_D = TILE_B, 2 * TILE_B, 2 * TILE_B + 128
-ABL = os.environ.get("TC_DKV_ABLATE", "")    # timing experiments only (wrong results): novalu, nopack, nolds, nostage, nobar, noprio, nosalu
-NSLOT, AHEAD, PERIOD = 8, 6, 2    # stores run AHEAD - 1 sub-tiles ahead: AHEAD - 1 >= PERIOD + 2, NSLOT >= AHEAD - 1 + PERIOD - 1 (gen_attn_asm.py)
+OFF_G = TILE_B
+NSLOT, PERIOD = 8, 2              # stores run AHEAD - 1 sub-tiles ahead: AHEAD - 1 >= PERIOD + 2, NSLOT >= AHEAD - 1 + PERIOD - 1 (gen_attn_asm.py)
 RED_B = 64 * 33 * 4               # one [d][key] fp32 accumulator tile in the epilogue's LDS layout
+ABLATIONS = ("nomfma", "noexp", "novalu", "nopack", "nolds", "nostage", "nobar", "noprio")    # --ablate: timing experiments only (wrong results)
 
 # VGPRs
 S, DP, NEGL, NEGD = 0, 16, 32, 48
@@ -55,14 +55,16 @@ def KF(ks): return 64 + 4 * ks
 def VF(ks): return 80 + 4 * ks
 def F(i): return 96 + 4 * i
 NA = 128
-# operands
+# operands, by the kernel's names
+OPERANDS = ("vq", "vg", "vs", "wq", "ws", "rb", "tb", "sb", "ko", "vo", "red", "prm", "rq", "rg", "rs", "rk", "rv", "smask")
 (OP_VQ, OP_VG, OP_VS, OP_WQ, OP_WS, OP_RB, OP_TB, OP_SB, OP_KO, OP_VO, OP_RED, OP_PRM,
- OP_RQ, OP_RG, OP_RS, OP_RK, OP_RV, OP_SMASK) = (f"%{i}" for i in range(18))
-# SGPRs (parameters first, in the order of the parameter block)
-(S_NSUB, S_T, S_OS, S_T1, S_T2, S_T3, S_A0, S_A1, S_A2, S_A3, S_LDQ, S_LDG, S_KSC) = range(36, 49)
-S_CNT, S_PH, S_SR, S_ST, S_SW, S_A, S_X, S_OQ, S_OG = range(49, 58)
-SGPRS = list(range(36, 58))
-NPRM = 13
+ OP_RQ, OP_RG, OP_RS, OP_RK, OP_RV, OP_SMASK) = asm_stream.operands(OPERANDS)
+# parameter block: the dwords the kernel leaves in LDS at `prm`, in this order; the prologue moves them to the first NPRM SGPRs
+PARAMS = ("nsub", "first tile to request", "its statistics offset", "Ts[1]", "Ts[2]", "Ts[3]", "As[0]", "As[1]", "As[2]", "As[3]", "ldq * 2", "lddo * 2", "kscale")
+NPRM = len(PARAMS)
+(S_NSUB, S_T, S_OS, S_T1, S_T2, S_T3, S_A0, S_A1, S_A2, S_A3, S_LDQ, S_LDG, S_KSC) = range(36, 36 + NPRM)
+S_CNT, S_PH, S_SR, S_ST, S_SW, S_A, S_X, S_OQ, S_OG = range(36 + NPRM, 45 + NPRM)
+SGPRS = list(range(36, 45 + NPRM))
 
 
 def mf_sdp(g, i):
@@ -98,12 +100,6 @@ def stat_loads(g, base):
     tuple -- 0.5 KB of LDS traffic per wave and sub-tile instead of the 8 KB of eight 16-byte reads (the stream is LDS-bandwidth-bound:
     removing every MFMA and VALU instruction left 44 of its 59 us)."""
     b = base if isinstance(base, str) else vreg(base)
-    if "b128stats" in ABL:        # the first version: eight 16-byte reads (needs the statistics base at + 64 h instead of + 4 (16 h + lane & 15))
-        ld = []
-        for q in range(4):
-            ld.append(lambda q=q: g.emit(f"ds_read_b128 {vreg(NEGL + 4 * q, 4)}, {b} offset:{16 * q}", "ds_read", [b], regs("v", NEGL + 4 * q, 4)))
-            ld.append(lambda q=q: g.emit(f"ds_read_b128 {vreg(NEGD + 4 * q, 4)}, {b} offset:{128 + 16 * q}", "ds_read", [b], regs("v", NEGD + 4 * q, 4)))
-        return ld, []
     ld = [lambda: g.emit(f"ds_read_b32 {vreg(XL)}, {b}", "ds_read", [b], [vreg(XL)]),
           lambda: g.emit(f"ds_read_b32 {vreg(XD)}, {b} offset:128", "ds_read", [b], [vreg(XD)])]
     mv = []
@@ -125,21 +121,6 @@ def pack_items(g):
     it = [lambda q=q: g.valu(f"{cvt_name(g.half)} {vreg(PP + q)}, {vreg(S + 2 * q)}, {vreg(S + 2 * q + 1)}", regs("v", S + 2 * q, 2), [vreg(PP + q)]) for q in range(8)]
     it += [lambda q=q: g.valu(f"{cvt_name(g.half)} {vreg(PD + q)}, {vreg(DP + 2 * q)}, {vreg(DP + 2 * q + 1)}", regs("v", DP + 2 * q, 2), [vreg(PD + q)]) for q in range(8)]
     return it
-
-
-def interleave(g, n, mf, after, free, head=()):
-    """head; then for i < n: mf(i), after(i), and an even share of the `free` closures."""
-    for f in head:
-        f()
-    per = [len(free) // n + (1 if k < len(free) % n else 0) for k in range(n)]
-    pos = 0
-    for i in range(n):
-        if mf is not None:
-            mf(i)
-        after(i)
-        for f in free[pos: pos + per[i]]:
-            f()
-        pos += per[i]
 
 
 def stage_request(g):
@@ -177,57 +158,40 @@ def stash(g):
     g.salu("s_mov_b64 exec, -1")
 
 
-def slots(g, which):
-    for s in which:
-        g.salu(f"s_add_u32 s{s}, s{s}, {SLOT_B}")
-        g.salu(f"s_cmp_eq_u32 s{s}, {SLOT_B * NSLOT}")
-        g.salu(f"s_cselect_b32 s{s}, 0, s{s}")
-
-
 def iteration(g, mode):
     """mode 'first' (j = -1): no dV / dK MFMAs; 'loop'; 'last' (j = nsub - 2): no sub-tile j + 2; 'drain' (j = nsub - 1): dV / dK only."""
     first, last, drain = mode == "first", mode == "last", mode == "drain"
     stage = not (last or drain)
     head = []
     if mode == "loop":
-        def bar():
-            g.wait_lgkm(0)
-            if "nobar" not in ABL:
-                g.salu(f"s_cmp_lg_u32 s{S_PH}, 0")
-                g.emit(f"s_cbranch_scc1 .Lnobar{g.uid}_%=", "branch")
-                g.emit("s_barrier", "barrier")
-                g.label(f".Lnobar{g.uid}_%=")
-                g.uid += 1
-            g.salu(f"s_add_u32 s{S_PH}, s{S_PH}, 1")
-            g.salu(f"s_and_b32 s{S_PH}, s{S_PH}, {PERIOD - 1}")
-        head.append(bar)
-    if stage and not ("nostage" in ABL and mode == "loop"):
+        head.append(lambda: asm_stream.ring_barrier(g, S_PH, PERIOD))
+    if stage and not ("nostage" in g.ablate and mode == "loop"):
         if not first:
             head.append(lambda: stash(g))                  # the sub-tile requested one iteration ago: a whole iteration of latency cover
         head.append(lambda: stage_request(g))
     if stage:
         head.append(lambda: g.valu(f"v_add_u32_e32 {vreg(AR)}, s{S_SR}, {OP_RB}", [], [vreg(AR)]))
         head.append(lambda: g.valu(f"v_add_u32_e32 {vreg(AS)}, s{S_SR}, {OP_SB}", [], [vreg(AS)]))
-    free = [] if (drain or "novalu" in ABL) else valu_items(g)
-    nolds = "nolds" in ABL and mode == "loop"
+    free = [] if (drain or "novalu" in g.ablate) else valu_items(g)
+    nolds = "nolds" in g.ablate and mode == "loop"
     if stage and not nolds:
         ld, mv = stat_loads(g, AS)
         free = ld + free + mv
-    if not first and "noprio" not in ABL:
+    if not first and "noprio" not in g.ablate:
         head.append(lambda: g.salu("s_setprio 1"))
-    interleave(g, 8, None if first else (lambda i: mf_dvdk(g, i)), (lambda i: row_load(g, i, AR)) if (stage and not nolds) else (lambda i: None), free, head)
-    if not first and "noprio" not in ABL:
+    interleave(8, None if first else (lambda i: mf_dvdk(g, i)), (lambda i: row_load(g, i, AR)) if (stage and not nolds) else None, free, head)
+    if not first and "noprio" not in g.ablate:
         g.salu("s_setprio 0")
     if drain:
         return
-    if "nopack" not in ABL:
+    if "nopack" not in g.ablate:
         for f in pack_items(g):
             f()
     # ---- S / dP (j+2) group: transpose reads of sub-tile j+1 behind the MFMAs
     head = [lambda: g.valu(f"v_add_u32_e32 {vreg(AT)}, s{S_ST}, {OP_TB}", [], [vreg(AT)])]
     noop = lambda: None
-    free = [noop] * 7 + [(lambda: slots(g, (S_SR, S_ST, S_SW))) if not last else noop]
-    interleave(g, 8, None if last else (lambda i: mf_sdp(g, i)), (lambda i: None) if nolds else (lambda i: tr_load(g, i, AT)), free, head)
+    free = [noop] * 7 + [(lambda: asm_stream.ring_advance(g, (S_SR, S_ST, S_SW), SLOT_B, NSLOT)) if not last else noop]
+    interleave(8, None if last else (lambda i: mf_sdp(g, i)), None if nolds else (lambda i: tr_load(g, i, AT)), free, head)
 
 
 def prologue(g):
@@ -279,59 +243,19 @@ def epilogue(g):
     g.wait_lgkm(0)
 
 
-def generate(half):
-    g = Gen(half)
-    prologue(g)
-    g.wait_lgkm(0)
-    iteration(g, "first")
-    first_end = len(g.out)
-    st_in = g.state()
-    g.salu(f"s_cmp_lt_i32 s{S_CNT}, 1")
-    g.emit("s_cbranch_scc1 .Llast_%=", "branch")
-    g.label(".Lloop_%=")
-    loop_begin = len(g.out)
-    iteration(g, "loop")
-    g.salu(f"s_sub_u32 s{S_CNT}, s{S_CNT}, 1")
-    g.salu(f"s_cmp_lg_u32 s{S_CNT}, 0")
-    g.emit("s_cbranch_scc1 .Lloop_%=", "branch")
-    loop_end = len(g.out)
-    if g.state() != st_in and not ABL:
-        raise RuntimeError(f"loop back-edge changes the outstanding-load queues:\n in  {st_in}\n out {g.state()}")
-    g.label(".Llast_%=")
-    last_begin = len(g.out)
-    g.nop(11)
-    iteration(g, "last")
-    iteration(g, "drain")
-    g.wait_lgkm(0)
-    g.emit("s_barrier", "barrier")                           # the accumulator tiles below overwrite ring slots other waves may still read
-    epilogue(g)
-    main = g.out
-    check_hazards(main[:loop_end] + main[loop_begin:loop_end] + main[last_begin:])
-    check_hazards(main[:first_end] + main[last_begin:])
-    return g, dict(first=first_end, loop=loop_end - loop_begin, last=len(g.out) - last_begin)
+def generate(half, k):
+    g = Gen(half, k.ablate)
+    return g, asm_stream.pipelined_loop(g, S_CNT, lambda: prologue(g), lambda mode: iteration(g, mode), lambda: epilogue(g),
+                                        back_edge_check=not k.ablate)     # only an ablated loop body may leave other queues than it found
 
 
-def clobbers():
-    c = [f"v{i}" for i in range(NV)] + [f"a{i}" for i in range(NA)] + [f"s{i}" for i in SGPRS] + ["vcc", "scc", "memory"]
-    return ", ".join(f'"{x}"' for x in c)
-
-
-def main():
-    here = os.path.dirname(os.path.abspath(__file__))
-    out = os.path.join(here, "attn_dkv_asm.inc")
-    parts = ["// GENERATED by gen_dkv_asm.py -- do not edit; edit the generator and re-run it (transception_amd.build does).\n"]
-    for half in ("bf16", "f16"):
-        g, stats = generate(half)
-        nm = sum(1 for i in g.out if i.kind == "mfma")
-        parts.append(f"// {half}: {len(g.out)} lines, {nm} MFMAs; sections {stats}\n")
-        parts.append(f"#define TC_ATTN_DKV_ASM_{half.upper()} R\"ASM(\n" + "\n".join(i.text for i in g.out) + "\n)ASM\"\n")
-    parts.append(f"#define TC_ATTN_DKV_ASM_CLOBBERS {clobbers()}\n")
-    text = "".join(parts)
-    if not os.path.exists(out) or open(out).read() != text:
-        with open(out, "w") as f:
-            f.write(text)
-    if "-v" in sys.argv:
-        print(text)
+def main(argv=None):
+    committed = os.path.join(os.path.dirname(os.path.abspath(__file__)), "attn_dkv_asm.inc")
+    k = asm_stream.parse_args(argv, committed, ABLATIONS)
+    defines = {"TC_DA_LDR_B": LDR_B, "TC_DA_TILE_B": TILE_B, "TC_DA_SLOT_B": SLOT_B, "TC_DA_NSLOT": NSLOT, "TC_DA_AHEAD": AHEAD, "TC_DA_RED_B": RED_B,
+               "TC_DA_NPRM": NPRM}
+    asm_stream.write_inc(k, "gen_dkv_asm.py", "TC_ATTN_DKV_ASM", {h: generate(h, k) for h in ("bf16", "f16")},
+                         asm_stream.clobbers(NV, NA, SGPRS), OPERANDS, defines, ["parameter block, dword by dword: " + " | ".join(PARAMS)])
 
 
 if __name__ == "__main__":

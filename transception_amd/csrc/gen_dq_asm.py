@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Emits the hand-scheduled gfx950 instruction stream of the bridge SR-attention dQ kernel (attn_bwd_dq_asm_kernel in attention_seg.hip)
-with the macro assembler of gen_attn_asm.py.
+with the macro assembler of asm_stream.py; this file holds the dQ stream's register map, operand list and schedule.
 
 The forward's decomposition and ring: one 12-wave workgroup per CU, a 32-query tile per wave (Q / dO fragments and the dQ^T accumulators
 stay in AGPRs), 32-key K | V sub-tiles through the 12-slot LDS ring (waves 0-3 stage K, 4-7 V, buffer loads six sub-tiles ahead, a
@@ -15,16 +15,18 @@ kinds in turn -- MFMA i of a group reads fragment i and the load behind it refil
 Arithmetic = attn_bwd_dq_seg_kernel<H, 1> (Q stored as q * scale * log2 e): dQ = scale * (P (dP - delta)) K.
 
     python gen_dq_asm.py            # writes attn_dq_asm.inc next to this file
+    python gen_dq_asm.py --ahead 7 --out PATH        # an experiment build (scripts/exp): never the committed file
 """
 from __future__ import annotations
 
 import os
-import sys
 
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from gen_attn_asm import AHEAD, LDR_B, NSLOT, PERIOD, SLOT_B, Gen, Ins, areg, check_hazards, cvt_name, regs, vreg  # noqa: E402
+import asm_stream
+from asm_stream import LDR_B, Gen, areg, cvt_name, interleave, regs, vreg
+from gen_attn_asm import AHEAD, NSLOT, PERIOD, SLOT_B, layout_defines      # the forward's ring, nothing else: written into the .inc as TC_DQ_*
 
-VOFF = 32 * LDR_B                 # V sub-tile behind the K sub-tile of a slot
+ABLATIONS = ("nomfma", "noexp")   # timing experiments only (wrong results)
+KNOBS = (("--ahead", dict(type=int, default=AHEAD)),)     # to go with the forward's --ahead
 
 # VGPRs
 S, DP, NEGL = 0, 16, 32
@@ -39,9 +41,10 @@ def QF(ks): return 32 + 4 * ks
 def GF(ks): return 48 + 4 * ks
 def F(i): return 64 + 4 * i
 NA = 80
-# operands: %0 "+v" global offset of this thread's staging chunk
+# operands, by the kernel's names: %0 "+v" global offset of this thread's staging chunk
+OPERANDS = ("goff", "kbase", "vbase", "tbase", "wbase", "qoff", "gooff", "oaddr", "nl2", "dl0", "mask", "rsrc", "rq", "rg", "nsub", "step", "wexec", "scl")
 (OP_GOFF, OP_KBASE, OP_VBASE, OP_TBASE, OP_WBASE, OP_QOFF, OP_GOOFF, OP_OADDR, OP_NL2, OP_DLT, OP_MASK,
- OP_RSRC, OP_RQ, OP_RG, OP_NSUB, OP_STEP, OP_WEXEC, OP_SCALE) = (f"%{i}" for i in range(18))
+ OP_RSRC, OP_RQ, OP_RG, OP_NSUB, OP_STEP, OP_WEXEC, OP_SCALE) = asm_stream.operands(OPERANDS)
 S_CNT, S_SV, S_SK, S_SW, S_PH, S_STEP, S_SCL = 60, 62, 63, 64, 65, 69, 68
 SGPRS = list(range(60, 70))
 
@@ -93,46 +96,19 @@ def pack_items(g):
             for q in range(8)]
 
 
-def interleave(g, n, mf, after, free, head=()):
-    for f in head:
-        f()
-    per = [len(free) // n + (1 if k < len(free) % n else 0) for k in range(n)]
-    pos = 0
-    for i in range(n):
-        if mf is not None:
-            mf(i)
-        after(i)
-        for f in free[pos: pos + per[i]]:
-            f()
-        pos += per[i]
-
-
 def iteration(g, mode):
     first, last, drain = mode == "first", mode == "last", mode == "drain"
     stage = not (last or drain)
-    nothing = lambda i: None
     # ---- dQ^T(j) | VALU(j+1) | K rows (j+2)
     head = []
     if mode == "loop":
-        def bar():
-            g.wait_lgkm(0)
-            g.salu(f"s_cmp_lg_u32 s{S_PH}, 0")
-            g.emit(f"s_cbranch_scc1 .Lnobar{g.uid}_%=", "branch")
-            g.emit("s_barrier", "barrier")
-            g.label(f".Lnobar{g.uid}_%=")
-            g.uid += 1
-            g.salu(f"s_add_u32 s{S_PH}, s{S_PH}, 1")
-            g.salu(f"s_and_b32 s{S_PH}, s{S_PH}, {PERIOD - 1}")
-        head.append(bar)
+        head.append(lambda: asm_stream.ring_barrier(g, S_PH, PERIOD))
     if stage:
-        head.append(lambda: g.salu(f"s_mov_b64 exec, {OP_WEXEC}"))
-        head.append(lambda: g.emit(f"buffer_load_dwordx4 {vreg(ST, 4)}, {OP_GOFF}, {OP_RSRC}, 0 offen", "vmem_load", [], regs("v", ST, 4)))
-        head.append(lambda: g.salu("s_mov_b64 exec, -1"))
-        head.append(lambda: g.valu(f"v_add_u32_e32 {OP_GOFF}, s{S_STEP}, {OP_GOFF}", [], []))
+        head += asm_stream.ring_request(g, ST, OP_GOFF, OP_RSRC, OP_WEXEC, S_STEP)
         head.append(lambda: g.valu(f"v_add_u32_e32 {vreg(AK)}, s{S_SK}, {OP_KBASE}", [], [vreg(AK)]))
     if not first:
         head.append(lambda: g.salu("s_setprio 1"))
-    interleave(g, 4, None if first else (lambda i: mf_dq(g, i)), (lambda i: krow_load(g, i, AK)) if stage else nothing,
+    interleave(4, None if first else (lambda i: mf_dq(g, i)), (lambda i: krow_load(g, i, AK)) if stage else None,
                [] if drain else valu_items(g, last), head)
     if not first:
         g.salu("s_setprio 0")
@@ -144,36 +120,25 @@ def iteration(g, mode):
     if not last:
         head.append(lambda: g.valu(f"v_add_u32_e32 {vreg(AV)}, s{S_SK}, {OP_VBASE}", [], [vreg(AV)]))
     head.append(lambda: g.valu(f"v_add_u32_e32 {vreg(AT)}, s{S_SV}, {OP_TBASE}", [], [vreg(AT)]))
-    interleave(g, 4, None if last else (lambda i: mf_s(g, i)), (lambda i: krow_load(g, i, AV)) if not last else nothing, pack_items(g), head)
+    interleave(4, None if last else (lambda i: mf_s(g, i)), None if last else (lambda i: krow_load(g, i, AV)), pack_items(g), head)
     # ---- dP^T(j+2) | K^T fragments (j+1) | ring store, slot bookkeeping
     free = []
     if stage:
-        def stash():
-            g.wait_vm(0)
-            g.valu(f"v_add_u32_e32 {vreg(AW)}, s{S_SW}, {OP_WBASE}", [], [vreg(AW)])
-            g.salu(f"s_mov_b64 exec, {OP_WEXEC}")
-            g.emit(f"ds_write_b128 {vreg(AW)}, {vreg(ST, 4)}", "ds_write", [vreg(AW)] + regs("v", ST, 4))
-            g.salu("s_mov_b64 exec, -1")
-        free.append(stash)
+        free.append(lambda: asm_stream.ring_stash(g, ST, AW, S_SW, OP_WBASE, OP_WEXEC))
     if not last:
-        def slots():
-            for s in (S_SV, S_SK, S_SW):
-                g.salu(f"s_add_u32 s{s}, s{s}, {SLOT_B}")
-                g.salu(f"s_cmp_eq_u32 s{s}, {SLOT_B * NSLOT}")
-                g.salu(f"s_cselect_b32 s{s}, 0, s{s}")
-        free.append(slots)
+        free.append(lambda: asm_stream.ring_advance(g, (S_SV, S_SK, S_SW), SLOT_B, NSLOT))
     noop = lambda: None
     free = [noop] * (4 - len(free)) + free
-    interleave(g, 4, None if last else (lambda i: mf_dp(g, i)), lambda i: tr_load(g, i, AT), free)
+    interleave(4, None if last else (lambda i: mf_dp(g, i)), lambda i: tr_load(g, i, AT), free)
 
 
-def prologue(g):
+def prologue(g, ahead):
     g.salu(f"s_mov_b32 s{S_CNT}, {OP_NSUB}")
     g.salu(f"s_mov_b32 s{S_STEP}, {OP_STEP}")
     g.salu(f"s_mov_b32 s{S_SCL}, {OP_SCALE}")
     g.salu(f"s_mov_b32 s{S_SV}, 0")                                                       # K^T fragments of sub-tile 0
     g.salu(f"s_mov_b32 s{S_SK}, {SLOT_B}")                                                # K / V rows of sub-tile 1
-    g.salu(f"s_mov_b32 s{S_SW}, {(AHEAD - 1) * SLOT_B}")
+    g.salu(f"s_mov_b32 s{S_SW}, {(ahead - 1) * SLOT_B}")
     g.salu(f"s_mov_b32 s{S_PH}, {2 % PERIOD}")
     g.salu(f"s_sub_u32 s{S_CNT}, s{S_CNT}, 2")
     for ks in range(4):                                                                   # Q / dO fragments of the wave's 32 queries: global -> AGPRs
@@ -195,72 +160,20 @@ def prologue(g):
 
 def epilogue(g):
     g.nop(32)
-    for blk in range(2):
-        for q in range(4):
-            for e in range(4):
-                a = DQ(blk) + 4 * q + e
-                g.valu(f"v_accvgpr_read_b32 {vreg(S + e)}, {areg(a)}", [areg(a)], [vreg(S + e)])
-            for e in range(4):
-                g.valu(f"v_mul_f32_e32 {vreg(S + e)}, s{S_SCL}, {vreg(S + e)}", [vreg(S + e)], [vreg(S + e)])
-            g.valu(f"{cvt_name(g.half)} {vreg(S + 4)}, {vreg(S)}, {vreg(S + 1)}", regs("v", S, 2), [vreg(S + 4)])
-            g.valu(f"{cvt_name(g.half)} {vreg(S + 5)}, {vreg(S + 2)}, {vreg(S + 3)}", regs("v", S + 2, 2), [vreg(S + 5)])
-            g.emit(f"ds_write_b64 {OP_OADDR}, {vreg(S + 4, 2)} offset:{64 * blk + 16 * q}", "ds_write", [vreg(S + 4), vreg(S + 5)])
+    asm_stream.write_acc_tile(g, DQ, S, f"s{S_SCL}", OP_OADDR)
     g.wait_lgkm(0)
 
 
-def generate(half):
-    g = Gen(half)
-    prologue(g)
-    g.wait_lgkm(0)
-    iteration(g, "first")
-    first_end = len(g.out)
-    st_in = g.state()
-    g.salu(f"s_cmp_lt_i32 s{S_CNT}, 1")
-    g.emit("s_cbranch_scc1 .Llast_%=", "branch")
-    g.label(".Lloop_%=")
-    loop_begin = len(g.out)
-    iteration(g, "loop")
-    g.salu(f"s_sub_u32 s{S_CNT}, s{S_CNT}, 1")
-    g.salu(f"s_cmp_lg_u32 s{S_CNT}, 0")
-    g.emit("s_cbranch_scc1 .Lloop_%=", "branch")
-    loop_end = len(g.out)
-    if g.state() != st_in:
-        raise RuntimeError(f"loop back-edge changes the outstanding-load queues:\n in  {st_in}\n out {g.state()}")
-    g.label(".Llast_%=")
-    last_begin = len(g.out)
-    g.nop(11)
-    iteration(g, "last")
-    iteration(g, "drain")
-    g.wait_lgkm(0)
-    g.emit("s_barrier", "barrier")                           # the dQ tiles written below lie in ring slots other waves may still be reading
-    epilogue(g)
-    main = g.out
-    check_hazards(main[:loop_end] + main[loop_begin:loop_end] + main[last_begin:])
-    check_hazards(main[:first_end] + main[last_begin:])
-    return g, dict(first=first_end, loop=loop_end - loop_begin, last=len(g.out) - last_begin)
+def generate(half, k):
+    g = Gen(half, k.ablate)
+    return g, asm_stream.pipelined_loop(g, S_CNT, lambda: prologue(g, k.ahead), lambda mode: iteration(g, mode), lambda: epilogue(g))
 
 
-def clobbers():
-    c = [f"v{i}" for i in range(NV)] + [f"a{i}" for i in range(NA)] + [f"s{i}" for i in SGPRS] + ["vcc", "scc", "memory"]
-    return ", ".join(f'"{x}"' for x in c)
-
-
-def main():
-    here = os.path.dirname(os.path.abspath(__file__))
-    out = os.path.join(here, "attn_dq_asm.inc")
-    parts = ["// GENERATED by gen_dq_asm.py -- do not edit; edit the generator and re-run it (transception_amd.build does).\n"]
-    for half in ("bf16", "f16"):
-        g, stats = generate(half)
-        nm = sum(1 for i in g.out if i.kind == "mfma")
-        parts.append(f"// {half}: {len(g.out)} lines, {nm} MFMAs; sections {stats}\n")
-        parts.append(f"#define TC_ATTN_DQ_ASM_{half.upper()} R\"ASM(\n" + "\n".join(i.text for i in g.out) + "\n)ASM\"\n")
-    parts.append(f"#define TC_ATTN_DQ_ASM_CLOBBERS {clobbers()}\n")
-    text = "".join(parts)
-    if not os.path.exists(out) or open(out).read() != text:
-        with open(out, "w") as f:
-            f.write(text)
-    if "-v" in sys.argv:
-        print(text)
+def main(argv=None):
+    committed = os.path.join(os.path.dirname(os.path.abspath(__file__)), "attn_dq_asm.inc")
+    k = asm_stream.parse_args(argv, committed, ABLATIONS, KNOBS)
+    asm_stream.write_inc(k, "gen_dq_asm.py", "TC_ATTN_DQ_ASM", {h: generate(h, k) for h in ("bf16", "f16")},
+                         asm_stream.clobbers(NV, NA, SGPRS), OPERANDS, layout_defines("TC_DQ", k.ahead))
 
 
 if __name__ == "__main__":
