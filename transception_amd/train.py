@@ -12,6 +12,7 @@ torch.distributed only.
 """
 from __future__ import annotations
 
+import contextlib
 import math
 import os
 from typing import Optional, Union
@@ -349,10 +350,140 @@ def check_no_decay(no_decay):
     raise ValueError(f'no_decay must be None, "norm_bias" or a predicate (name, shape) -> bool, got {no_decay!r}')
 
 
+def check_ema_decay(decay) -> float:
+    """An EMA decay as a float: a finite number in [0, 1), not a bool.  Anything else is a ValueError."""
+    if isinstance(decay, bool) or not isinstance(decay, (int, float)) or not math.isfinite(decay) or not 0.0 <= decay < 1.0:
+        raise ValueError(f"the EMA decay must be a finite number in [0, 1), got {decay!r}")
+    return float(decay)
+
+
+class WeightEMA:
+    """An exponential moving average of the weights, kept in a shadow of the model's flat fp32 arena and updated from inside the
+    (captured) step: attach it to a fused optimiser (`opt.ema = WeightEMA(model)`) and every opt.step() launches tc_ema_advance and
+    tc_ema_update_multi right after its own update kernel, on the same stream, under the same squared gradient norm -- a step the
+    device skips (float16 overflow) is not averaged in and not counted.
+
+    The rule is torch.optim.swa_utils.AveragedModel's with get_ema_multi_avg_fn(decay): the first update copies the weights, every later
+    one is e.lerp_(w, 1 - d).  warmup: d = min(decay, (1 + n) / (10 + n)) at the n-th update, so that early averages are not dominated by
+    the initial weights.  The count n and the decay derived from it live in four 32-bit words on the device (include/transception_ema.h),
+    because a captured kernel's scalar arguments are frozen at capture.
+
+    The shadow is a clone of the whole arena, created on first use: parameters that never receive a gradient hold their true value in it
+    for good, and memory grows by 4 bytes per weight.  Neither the shadow nor the state word is ever replaced (captured launches hold
+    their addresses).  The segment table is the optimiser's set of views under ONE decay class: adjacent views always merge, whatever
+    no_decay splits the optimiser's own table into.  BatchNorm running statistics are buffers, not weights: they are not averaged and
+    are taken live (AveragedModel(use_buffers=False)).  Several GPUs: every rank averages identical weights, so no collective is needed."""
+
+    def __init__(self, model, decay: float = 0.999, warmup: bool = True):
+        self.model, self.decay, self.warmup = model, check_ema_decay(decay), bool(warmup)
+        self.shadow: Optional[torch.Tensor] = None       # fp32, the arena's size
+        self._state: Optional[torch.Tensor] = None       # fp32[4]; words 0 and 3 are int32
+        self._segs_dev: Optional[torch.Tensor] = None
+        self._launched = False                           # an update was launched (perhaps captured) with this decay and warmup
+        self._swapped = False
+
+    def _ensure_state(self):
+        """The shadow arena and the four-word state.  Their addresses are baked into captured launches: never replaced."""
+        M = self.model
+        if M._flat is None:
+            M._ensure_flat(next(M.parameters()).device)
+        if self.shadow is None:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("the EMA's shadow arena must exist before a step is captured: run one eager step first")
+            self.shadow = M._flat.clone()
+            self._state = torch.zeros(4, dtype=torch.float32, device=M._flat.device)
+        elif self.shadow.shape != M._flat.shape or self.shadow.device != M._flat.device:
+            raise RuntimeError("the model's parameter arena was rebuilt after this WeightEMA was created: make a new one")
+
+    def segments(self):
+        """[(offset, length)] over the views of the parameters that receive a gradient, as ONE decay class (build_segments)."""
+        flat = self.model._flat
+        views = sorted((off, math.prod(shape), 0.0) for off, shape in self.model._used_views.values())
+        return [(off, min(n, flat.numel() - off)) for off, n, _ in build_segments(views)]
+
+    def update(self, sumsq: Optional[int], stream: int):
+        """The two launches of one step (the fused optimisers call it right after their update kernel).  sumsq: the device address of
+        the squared gradient norm that update used, or None."""
+        self.check_not_swapped()
+        self._ensure_state()
+        if self._segs_dev is None:
+            segs = self.segments()
+            self._segs_dev = torch.tensor([v for s in segs for v in s], dtype=torch.int64, device=self.shadow.device)
+            self._nseg, self._maxlen = len(segs), max(n for _, n in segs)
+        L = lib()
+        L.tc_ema_advance(self._state.data_ptr(), sumsq, self.decay, int(self.warmup), stream)
+        L.tc_ema_update_multi(self.shadow.data_ptr(), self.model._flat.data_ptr(), self._segs_dev.data_ptr(), self._nseg, self._maxlen,
+                              self._state.data_ptr(), sumsq, stream)
+        self._launched = True
+
+    def updates(self) -> int:
+        """Updates averaged so far, as counted on the device (skipped ones are not).  A host sync."""
+        return 0 if self._state is None else int(self._state.view(torch.int32)[0].item())
+
+    def check_not_swapped(self):
+        if self._swapped:
+            raise RuntimeError("the averaged weights are swapped into the model (WeightEMA.swapped()): no optimiser step in there")
+
+    def _swap(self):
+        M = self.model
+        lib().tc_swap_f32(M._flat.data_ptr(), self.shadow.data_ptr(), M._flat.numel(), torch.cuda.current_stream(M._flat.device).cuda_stream)
+        M.invalidate_working_copy()                      # the 16-bit copy follows, in place
+
+    @contextlib.contextmanager
+    def swapped(self):
+        """Inside the context the model holds the averaged weights and the shadow holds the trained ones: the contents of the two
+        arenas are exchanged IN PLACE (tc_swap_f32) and the 16-bit working copy is recast, on entry and again on exit.  Addresses never
+        change, so a captured step keeps working afterwards.  Entering twice raises, and so does an opt.step() inside."""
+        if self._swapped:
+            raise RuntimeError("WeightEMA.swapped() is already active")
+        self._ensure_state()
+        self._swap()
+        self._swapped = True
+        try:
+            yield self.model
+        finally:
+            self._swap()
+            self._swapped = False
+
+    def model_state_dict(self) -> dict:
+        """model.state_dict() with every parameter entry replaced by a clone of its averaged value; buffers (the BatchNorm statistics
+        among them) are the live ones.  Loads with strict=True wherever model.state_dict() does."""
+        self._ensure_state()
+        M = self.model
+        src = M._flat if self._swapped else self.shadow
+        sd = M.state_dict()
+        for name, (off, shape) in M._index.items():
+            if name in sd:
+                sd[name] = src[off:off + math.prod(shape)].view(shape).clone()
+        return sd
+
+    def state_dict(self) -> dict:
+        """{"n", "decay", "warmup", "shadow"}: the device's count (a host sync), the two settings and a clone of the shadow arena."""
+        self.check_not_swapped()
+        self._ensure_state()
+        return {"n": self.updates(), "decay": self.decay, "warmup": self.warmup, "shadow": self.shadow.clone()}
+
+    def load_state_dict(self, sd: dict):
+        """Writes the count and the shadow IN PLACE (same data_ptrs): a captured step keeps working and sees them on its next replay.
+        Words 1 and 2 need no restoring: tc_ema_advance rewrites them from the count before any use.  decay and warmup are arguments
+        of the launches, frozen in a captured step: once an update has been launched, other values than the current ones are refused."""
+        n, decay, warmup = int(sd["n"]), check_ema_decay(sd["decay"]), bool(sd["warmup"])
+        if n < 0:
+            raise ValueError(f"bad EMA update count {sd['n']!r}")
+        if self._launched and (decay, warmup) != (self.decay, self.warmup):
+            raise ValueError(f"updates were launched with decay {self.decay!r}, warmup {self.warmup!r}: cannot load {decay!r}, {warmup!r}")
+        self.check_not_swapped()
+        self._ensure_state()
+        self.decay, self.warmup = decay, warmup
+        self.shadow.copy_(sd["shadow"])
+        self._state.view(torch.int32)[0:1].copy_(torch.tensor([n], dtype=torch.int32))
+
+
 class _FusedOptimizer:
     """What the fused optimisers share: the segment table over the parameters that receive a gradient (the 332 grad-less tensors of
     the reference are left untouched, as torch.optim skips `p.grad is None`), the device learning rate, the squared-norm launches of
-    clipping and of the overflow guard, the choice of the 16-bit working copy the update refreshes, and the skip read-back."""
+    clipping and of the overflow guard, the choice of the 16-bit working copy the update refreshes, the skip read-back, and the weight
+    average that follows the update (`ema`)."""
 
     def __init__(self, model, lr: float, weight_decay: float, clip_norm: Optional[float]):
         self.model, self.lr, self.wd = model, lr, weight_decay
@@ -366,7 +497,7 @@ class _FusedOptimizer:
         self.grad_scale = 1.0                            # gradients in the arena are this many times too small (1 / loss scale)
         self.guard_overflow: Optional[bool] = None       # skip the update when the gradient norm is not finite; None: on for float16 storage
         self.loss_scaler: Optional[DynamicLossScale] = None   # gradients carry its device scale instead (the guard is then always on)
-
+        self.ema: Optional[WeightEMA] = None             # averages the weights after every update, under the update's own skip; None: no launch
         self.skipped_steps = 0                           # updates found skipped by last_step_skipped() (read back at the caller's log cadence)
 
     def last_step_skipped(self) -> bool:
@@ -427,6 +558,13 @@ class _FusedOptimizer:
         L.tc_grad_sumsq(g.data_ptr(), g.numel(), self._sumsq.data_ptr(), stream)
         return self._sumsq.data_ptr()
 
+    def _ema_check(self):
+        """Before anything is launched: an attached WeightEMA is this model's and does not have its weights swapped in."""
+        if self.ema is not None:
+            if self.ema.model is not self.model:
+                raise ValueError("the attached WeightEMA averages another model")
+            self.ema.check_not_swapped()
+
     def _working_copy(self):
         """The 16-bit working copy of the weights that the update kernel refreshes (the forward then skips its cast pass over the arena)."""
         M = self.model
@@ -446,6 +584,7 @@ class FusedSGD(_FusedOptimizer):
 
     def step(self, grad_scale: Optional[float] = None):
         grad_scale = self.grad_scale if grad_scale is None else grad_scale
+        self._ema_check()
         M = self.model
         flat, g = M._flat, M._gflat
         if self.buf is None:
@@ -469,6 +608,8 @@ class FusedSGD(_FusedOptimizer):
             # then the scale takes its own step from the same squared norm
             L.tc_sgd_step_multi_scaled(*args, scaler.state(flat.device).data_ptr(), stream)
             scaler.update(self._sumsq)
+        if self.ema is not None:
+            self.ema.update(sumsq, stream)               # the same squared norm: a skipped update is not averaged in
         M._lp_fresh = lp is not None
         self.steps += 1
 
@@ -521,6 +662,7 @@ class FusedAdamW(_FusedOptimizer):
 
     def step(self, grad_scale: Optional[float] = None):
         grad_scale = self.grad_scale if grad_scale is None else grad_scale
+        self._ema_check()
         M = self.model
         flat, g = M._flat, M._gflat
         self._ensure_state()
@@ -542,6 +684,8 @@ class FusedAdamW(_FusedOptimizer):
                              scaler.state(flat.device).data_ptr() if scaler is not None else None, st, stream)
         if scaler is not None:
             scaler.update(self._sumsq)               # the scale takes its own step from the same squared norm
+        if self.ema is not None:
+            self.ema.update(sumsq, stream)               # the same squared norm: a skipped update is not averaged in
         M._lp_fresh = lp is not None
         self.steps += 1
 

@@ -15,6 +15,7 @@ Not kept: TensorBoard writers and the matplotlib/CSV result plots (:216-237).
 """
 from __future__ import annotations
 
+import contextlib
 import logging
 import math
 import os
@@ -26,7 +27,8 @@ import torch.distributed as dist
 
 from .data import DeviceLoader, SynapseSlices
 from .evaluate import PostProcess, inference
-from .train import DynamicLossScale, FusedAdamW, FusedSGD, GraphedStep, SegLoss, check_class_weights, check_ignore_index, cosine_lr, train_step
+from .train import (DynamicLossScale, FusedAdamW, FusedSGD, GraphedStep, SegLoss, WeightEMA, check_class_weights, check_ema_decay,
+                    check_ignore_index, cosine_lr, train_step)
 
 OPTIMIZERS = ("sgd", "adamw", "adam")
 
@@ -61,6 +63,9 @@ class TrainConfig:
     betas: tuple = (0.9, 0.999)        # adamw / adam
     adam_eps: float = 1e-8             # adamw / adam
     no_decay: Optional[str] = None     # adamw / adam: "norm_bias" = no decay on tensors with ndim <= 1 (norm affine parameters and biases)
+    ema_decay: Optional[float] = None  # a number in [0, 1): keep an exponential moving average of the weights (train.WeightEMA) inside the step
+    ema_warmup: bool = True            # the n-th update uses min(ema_decay, (1 + n) / (10 + n))
+    ema_eval: bool = True              # evaluate the averaged weights (BatchNorm statistics stay the live ones) instead of the last iterate
 
     def __post_init__(self):
         if self.optimizer not in OPTIMIZERS:
@@ -87,6 +92,8 @@ class TrainConfig:
         make_loss_scale(self.loss_scale)
         check_class_weights("class_weights", self.class_weights, self.num_classes, need_positive=True)
         check_ignore_index(self.ignore_index, self.num_classes)
+        if self.ema_decay is not None:
+            check_ema_decay(self.ema_decay)
 
 
 def make_loss_scale(spec) -> Union[float, DynamicLossScale]:
@@ -129,7 +136,9 @@ def trainer_synapse(cfg: TrainConfig, model, snapshot_path: str, volumes: Option
                     log: Optional[Callable[[str], None]] = None) -> dict:
     """Trains `model` (a transception_amd.MSTransception on the GPU) and returns the history.  `volumes` is a callable that
     yields the evaluation volumes as (image, label, case) triples (the `.npy.h5` reader needs h5py, see data.SynapseSlices).
-    Under optimizer="adamw" / "adam" the history also holds "optimizer_step", the updates the device counted as applied."""
+    Under optimizer="adamw" / "adam" the history also holds "optimizer_step", the updates the device counted as applied.
+    With ema_decay set it holds "ema_checkpoints" (`<model_name>_ema_epoch_<n>.pth`, the averaged weights, written beside every plain
+    checkpoint) and "ema_updates", the updates the device averaged in; the evaluation then runs on the averaged weights (ema_eval)."""
     log = log or logging.info
     distributed = dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1
     rank = dist.get_rank(group) if distributed else 0
@@ -149,6 +158,9 @@ def trainer_synapse(cfg: TrainConfig, model, snapshot_path: str, volumes: Option
     loss_fn = SegLoss(cfg.num_classes, group=group, loss_scale=loss_scale, ce_weight=cfg.class_weights, dice_weight=cfg.class_weights,
                       ignore_index=cfg.ignore_index)
     opt = make_optimizer(cfg, model)
+    ema = None
+    if cfg.ema_decay is not None:
+        ema = opt.ema = WeightEMA(model, decay=cfg.ema_decay, warmup=cfg.ema_warmup)
 
     def lr_at(it: int) -> float:
         """Learning rate of step `it` (0-based).  Cosine: scheduler.step() follows every optimizer.step() (trainer.py:151-153).
@@ -169,6 +181,8 @@ def trainer_synapse(cfg: TrainConfig, model, snapshot_path: str, volumes: Option
 
     saves = set(checkpoint_epochs(cfg.max_epochs, cfg.eval_interval))
     hist = {"loss": [], "lr": [], "dice": [], "hd95": [], "checkpoints": []}
+    if ema is not None:
+        hist["ema_checkpoints"] = []
     if scaler is not None:
         hist["loss_scale"] = []                                   # the scale after the step of each log line
     step = None
@@ -207,6 +221,11 @@ def trainer_synapse(cfg: TrainConfig, model, snapshot_path: str, volumes: Option
                     torch.save(model.state_dict(), path)
                     hist["checkpoints"].append(path)
                     log("save model to {}".format(path))
+                    if ema is not None:
+                        path = os.path.join(snapshot_path, f'{cfg.model_name}_ema_epoch_{epoch_num}.pth')
+                        torch.save(ema.model_state_dict(), path)
+                        hist["ema_checkpoints"].append(path)
+                        log("save averaged model to {}".format(path))
                 if volumes is not None:
                     # Every rank evaluates its share of the volumes with the replica the checkpoint holds (rank 0's BatchNorm statistics
                     # are broadcast first; the weights are identical already) and the per-case sums are all-reduced: no rank sits in a
@@ -220,8 +239,10 @@ def trainer_synapse(cfg: TrainConfig, model, snapshot_path: str, volumes: Option
                     if vols:
                         if rank == 0:
                             log(f"Running Inference after epoch {epoch_num}")
-                        mean_dice, mean_hd95 = inference(model, vols, cfg.num_classes, cfg.img_size, log=log, device_metrics=cfg.device_metrics,
-                                                        voxelspacing=cfg.voxelspacing, postprocess=cfg.postprocess)
+                        # the averaged weights are swapped into the arenas for the evaluation and out again (every rank holds the same average)
+                        with ema.swapped() if ema is not None and cfg.ema_eval else contextlib.nullcontext():
+                            mean_dice, mean_hd95 = inference(model, vols, cfg.num_classes, cfg.img_size, log=log, device_metrics=cfg.device_metrics,
+                                                            voxelspacing=cfg.voxelspacing, postprocess=cfg.postprocess)
                         res[0], res[1], res[2] = mean_dice * len(vols), mean_hd95 * len(vols), len(vols)
                         model.train()
                     if distributed:
@@ -231,4 +252,6 @@ def trainer_synapse(cfg: TrainConfig, model, snapshot_path: str, volumes: Option
     hist["iterations"] = iter_num
     if isinstance(opt, FusedAdamW):
         hist["optimizer_step"] = opt.device_step()                # updates applied, as the device counted them: iterations minus skipped
+    if ema is not None:
+        hist["ema_updates"] = ema.updates()                       # likewise: a skipped update is not averaged in
     return hist
