@@ -25,6 +25,12 @@ Connected-component post-processing (`PostProcess`; the reference has no such st
 either metric: per class keep the largest component, or every component of at least N voxels.  `postprocess_device` runs it on the GPU
 (csrc/postprocess.hip: a lock-free union-find, integer atomics only), `postprocess_host` is the same definition on scipy.ndimage.label;
 include/transception_post.h states the definition.  `postprocess=None`, the default everywhere, changes nothing.
+
+Test-time augmentation (`TTA`; the reference scores one forward pass per slice, but trains on every flipped and 90-degree-rotated
+orientation, dataset_synapse.py:39-46) averages the class probabilities over flip / transpose views of the input before the argmax.  Per
+view `tc_tta_view` makes the normalised view, the network runs, and `tc_tta_accumulate` reads the logits once and folds their softmax
+into one fp32 accumulator at the un-transformed position -- or, for the last view, writes the label (csrc/tta.hip;
+include/transception_tta.h states the definition).  `tta=None`, the default everywhere, changes nothing.
 """
 from __future__ import annotations
 
@@ -36,7 +42,7 @@ import math
 import numpy as np
 import torch
 
-from ._lib import TC_CC_LARGEST, TC_CC_MIN_VOXELS, TC_F32, TC_METRIC_SELECT_WORK_BYTES, lib
+from ._lib import TC_BF16, TC_CC_LARGEST, TC_CC_MIN_VOXELS, TC_F16, TC_F32, TC_METRIC_SELECT_WORK_BYTES, TC_TTA_TRANSPOSE, lib
 
 NO_CPU = "transception_amd.evaluate runs on MI355X only (no CPU fallback)"
 
@@ -373,20 +379,119 @@ def postprocess_host(pred: np.ndarray, classes: int = 9, post: PostProcess = Pos
     return out
 
 
+@dataclass(frozen=True)
+class TTA:
+    """Test-time augmentation: the views of the input whose class probabilities are averaged (include/transception_tta.h).  A view is three
+    bits -- 1: rows reversed, 2: columns reversed, 4: transpose, applied after the flips (square slices only) -- so 0..3 are the identity and
+    the flips and 0..7 the eight symmetries of the square.  Views are evaluated, and their probabilities added, in the order given: another
+    order may differ in the last bits of the sums."""
+    views: Tuple[int, ...] = (0, 1, 2, 3)
+
+    def __post_init__(self):
+        v = self.views
+        if not isinstance(v, tuple) or not v:
+            raise ValueError(f"views must be a non-empty tuple of views 0..7, got {v!r}")
+        if any(isinstance(i, bool) or not isinstance(i, (int, np.integer)) or not 0 <= i <= 7 for i in v):
+            raise ValueError(f"views must be integers in 0..7, got {v!r}")
+        if len(set(int(i) for i in v)) != len(v):
+            raise ValueError(f"views must be distinct, got {v!r}")
+
+    @classmethod
+    def flips(cls) -> "TTA":
+        """Identity and the three flips: any slice shape."""
+        return cls((0, 1, 2, 3))
+
+    @classmethod
+    def dihedral(cls) -> "TTA":
+        """All eight symmetries of the square: square slices only."""
+        return cls((0, 1, 2, 3, 4, 5, 6, 7))
+
+
+def _check_tta(tta, shape=None) -> None:
+    """None or a TTA; with `shape` = (H, W) of the slices, a transposed view needs H == W."""
+    if tta is not None and not isinstance(tta, TTA):
+        raise ValueError(f"tta must be None or a TTA, got {tta!r}")
+    if tta is not None and shape is not None and shape[0] != shape[1] and any(int(v) & TC_TTA_TRANSPOSE for v in tta.views):
+        raise ValueError(f"a transposed view (>= 4) needs square slices, got {shape[0]} x {shape[1]}")
+
+
+_TC_DTYPES = {torch.float32: TC_F32, torch.bfloat16: TC_BF16, torch.float16: TC_F16}
+
+
+def _tta_batches(model, slices: torch.Tensor, batch: int, tta: TTA, labels: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
+    """The views of every batch of `slices` through `model` and tc_tta_accumulate, in the order given.  With `labels` (uint8 [N,H,W]) the last
+    view writes the labels and one fp32 [batch,C,H,W] accumulator, allocated at the first logits (none for a single view), holds the views
+    before it.  Without, every view is added into the batch's part of an fp32 [N,C,H,W] tensor of sums, which is returned."""
+    if not slices.is_cuda:
+        raise RuntimeError(NO_CPU)
+    N, H, W = slices.shape
+    _check_tta(tta, (H, W))
+    views = tta.views
+    L, stream = lib(), torch.cuda.current_stream(slices.device).cuda_stream
+    acc, out = None, None
+    for i in range(0, N, batch):
+        src = slices[i:i + batch].float().contiguous()
+        n = src.shape[0]
+        for j, v in enumerate(views):
+            x = torch.empty((n, 1, W, H) if int(v) & TC_TTA_TRANSPOSE else (n, 1, H, W), dtype=torch.float32, device=src.device)
+            L.tc_tta_view(src.data_ptr(), x.data_ptr(), n, H, W, int(v), 0.5, 0.5, stream)
+            lg = model(x)
+            if lg.dtype not in _TC_DTYPES:
+                lg = lg.float()
+            lg = lg.contiguous()
+            C = lg.shape[1]
+            if lg.shape != x.shape[:1] + (C,) + x.shape[2:]:
+                raise ValueError(f"the model returned logits of shape {tuple(lg.shape)} for a view of shape {tuple(x.shape)}")
+            first, last = int(j == 0), j == len(views) - 1
+            if labels is None:
+                if out is None:
+                    out = torch.empty((N, C, H, W), dtype=torch.float32, device=src.device)
+                L.tc_tta_accumulate(lg.data_ptr(), _TC_DTYPES[lg.dtype], out[i:i + n].data_ptr(), None, n, C, H, W, int(v), first, stream)
+                continue
+            if acc is None and len(views) > 1:
+                acc = torch.empty((batch, C, H, W), dtype=torch.float32, device=src.device)
+            L.tc_tta_accumulate(lg.data_ptr(), _TC_DTYPES[lg.dtype], acc.data_ptr() if acc is not None else None,
+                                labels[i:i + n].data_ptr() if last else None, n, C, H, W, int(v), first, stream)
+    return out
+
+
 @torch.no_grad()
-def predict_slices(model, slices: torch.Tensor, batch: int = 16) -> torch.Tensor:
+def predict_slices(model, slices: torch.Tensor, batch: int = 16, tta: Optional[TTA] = None) -> torch.Tensor:
     """slices: float [N,H,W] in [0,1] at the network size (a multiple of 32); returns uint8 [N,H,W] labels.
-    Normalisation (x-0.5)/0.5 as `transforms.Normalize([0.5],[0.5])` (utils.py:71-75); eval-mode BatchNorm (utils.py:78)."""
+    Normalisation (x-0.5)/0.5 as `transforms.Normalize([0.5],[0.5])` (utils.py:71-75); eval-mode BatchNorm (utils.py:78).
+    `tta`: a `TTA`; the label is then the argmax of the class probabilities summed over its views (`views=(0,)` is softmax-then-argmax of
+    the one plain pass: not bit-pinned to the path without `tta`, which takes the argmax of the logits)."""
+    _check_tta(tta)
     was_training = model.training
     model.eval()
     out = torch.empty(slices.shape, dtype=torch.uint8, device=slices.device)
     try:
-        for i in range(0, slices.shape[0], batch):
-            x = ((slices[i:i + batch].float() - 0.5) / 0.5).unsqueeze(1)
-            out[i:i + batch] = argmax_counts(model(x))[0]
+        if tta is not None:
+            _tta_batches(model, slices, batch, tta, out)
+        else:
+            for i in range(0, slices.shape[0], batch):
+                x = ((slices[i:i + batch].float() - 0.5) / 0.5).unsqueeze(1)
+                out[i:i + batch] = argmax_counts(model(x))[0]
     finally:
         model.train(was_training)
     return out
+
+
+@torch.no_grad()
+def predict_probs(model, slices: torch.Tensor, batch: int = 16, tta: Optional[TTA] = None) -> torch.Tensor:
+    """The class probabilities of `predict_slices`' input averaged over the views of `tta` (None: the single view 0): fp32 [N,C,H,W], the
+    accumulator of tc_tta_accumulate divided by the number of views."""
+    _check_tta(tta)
+    tta = tta if tta is not None else TTA((0,))
+    if slices.shape[0] == 0:
+        raise ValueError("predict_probs needs at least one slice")
+    was_training = model.training
+    model.eval()
+    try:
+        out = _tta_batches(model, slices, batch, tta, None)
+    finally:
+        model.train(was_training)
+    return out.div_(len(tta.views)) if len(tta.views) > 1 else out
 
 
 @torch.no_grad()
@@ -423,7 +528,7 @@ def zoom_labels(pred: torch.Tensor, size: Tuple[int, int]) -> torch.Tensor:
 @torch.no_grad()
 def evaluate_volume(model, image: np.ndarray, label: np.ndarray, classes: int = 9, patch_size=(224, 224),
                     batch: int = 16, with_hd95: bool = False, host_zoom: bool = False, device_metrics: bool = False, voxelspacing=None,
-                    postprocess: Optional[PostProcess] = None):
+                    postprocess: Optional[PostProcess] = None, tta: Optional[TTA] = None):
     """`test_single_volume` for one [D,H,W] volume (utils.py:63-98): per-class Dice for classes 1..classes-1, or with
     `with_hd95` the reference's metric_list of (dice, hd95) pairs.  The volume goes to the GPU once; the order-3 zoom to the network
     size, inference, argmax and the order-0 zoom back all run there (host_zoom=True: scipy per slice, as the reference does).
@@ -431,9 +536,11 @@ def evaluate_volume(model, image: np.ndarray, label: np.ndarray, classes: int = 
     counts of its first kernel (Dice only) replace the host metric; same returned structure.  `voxelspacing`: the (z, y, x) size of a voxel
     of `label`, for the HD95 of either metric path (Dice does not depend on it).  `postprocess`: a `PostProcess` applied in 3-D to the
     prediction at `label`'s resolution (after the order-0 zoom back) before either metric path: on the device wherever the prediction is
-    there (host_zoom=False, whatever `device_metrics` is), else on the host; None: no such step."""
+    there (host_zoom=False, whatever `device_metrics` is), else on the host; None: no such step.  `tta`: a `TTA` handed to `predict_slices`
+    (both zoom paths; the views are taken at the network size, before the zoom back and `postprocess`); None: one plain pass."""
     if postprocess is not None and not isinstance(postprocess, PostProcess):
         raise ValueError(f"postprocess must be None or a PostProcess, got {postprocess!r}")
+    _check_tta(tta, tuple(patch_size))
     dev = next(model.parameters()).device
     if device_metrics and dev.type != "cuda":
         raise RuntimeError(NO_CPU)
@@ -442,7 +549,7 @@ def evaluate_volume(model, image: np.ndarray, label: np.ndarray, classes: int = 
     if host_zoom:
         from scipy.ndimage import zoom
         sl = np.stack([zoom(image[d], (patch_size[0] / X, patch_size[1] / Y), order=3) if resize else image[d] for d in range(D)])
-        pred = predict_slices(model, torch.from_numpy(sl.astype(np.float32)).to(dev), batch).cpu().numpy()
+        pred = predict_slices(model, torch.from_numpy(sl.astype(np.float32)).to(dev), batch, tta).cpu().numpy()
         if resize:
             pred = np.stack([zoom(pred[d], (X / patch_size[0], Y / patch_size[1]), order=0) for d in range(D)])
         if postprocess is not None:
@@ -450,7 +557,7 @@ def evaluate_volume(model, image: np.ndarray, label: np.ndarray, classes: int = 
     else:
         vol = torch.from_numpy(np.ascontiguousarray(image, np.float32)).to(dev)
         sl = zoom_volume_to_network(vol, tuple(patch_size)) if resize else vol
-        pred_d = predict_slices(model, sl, batch)
+        pred_d = predict_slices(model, sl, batch, tta)
         pred = zoom_labels(pred_d, (X, Y)) if resize else pred_d
         if postprocess is not None:
             pred = postprocess_device(pred, classes, postprocess, out=pred)
@@ -472,13 +579,15 @@ def evaluate_volume(model, image: np.ndarray, label: np.ndarray, classes: int = 
 
 
 def inference(model, volumes, classes: int = 9, img_size: int = 224, batch: int = 16, log=None,
-              device_metrics: bool = False, voxelspacing=None, postprocess: Optional[PostProcess] = None) -> Tuple[float, float]:
+              device_metrics: bool = False, voxelspacing=None, postprocess: Optional[PostProcess] = None,
+              tta: Optional[TTA] = None) -> Tuple[float, float]:
     """trainer.py:25-47: mean Dice and mean HD95 over `volumes` = iterable of (image [D,H,W] in [0,1], label [D,H,W], case name).
-    `device_metrics`, `voxelspacing` (one spacing for every volume), `postprocess`: as in `evaluate_volume`."""
+    `device_metrics`, `voxelspacing` (one spacing for every volume), `postprocess`, `tta`: as in `evaluate_volume`."""
+    _check_tta(tta)
     total, n = 0.0, 0
     for i, (image, label, name) in enumerate(volumes):
         m = np.array(evaluate_volume(model, np.asarray(image), np.asarray(label), classes, (img_size, img_size), batch, with_hd95=True,
-                                     device_metrics=device_metrics, voxelspacing=voxelspacing, postprocess=postprocess))
+                                     device_metrics=device_metrics, voxelspacing=voxelspacing, postprocess=postprocess, tta=tta))
         total = total + m
         n += 1
         if log:

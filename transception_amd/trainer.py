@@ -19,14 +19,14 @@ import contextlib
 import logging
 import math
 import os
-from dataclasses import dataclass
+from dataclasses import dataclass, field
 from typing import Callable, List, Optional, Union
 
 import torch
 import torch.distributed as dist
 
 from .data import DeviceLoader, SynapseSlices
-from .evaluate import PostProcess, inference
+from .evaluate import TTA, PostProcess, inference
 from .train import (DynamicLossScale, FusedAdamW, FusedSGD, GraphedStep, SegLoss, WeightEMA, check_class_weights, check_ema_decay,
                     check_ignore_index, cosine_lr, train_step)
 
@@ -53,6 +53,9 @@ class TrainConfig:
     device_metrics: bool = False       # Dice / HD95 of the evaluation on the GPU (evaluate.metrics_device) instead of scipy on the host
     voxelspacing: Optional[tuple] = None   # (z, y, x) voxel size for the HD95 of the evaluation, on either metric path; None: in voxels
     postprocess: Optional[PostProcess] = None   # connected-component post-processing of the evaluation's predictions (evaluate.PostProcess); None: none
+    # test-time augmentation of the evaluation (evaluate.TTA: flip / transpose views whose class probabilities are averaged); None: one pass.
+    # Keyword-only, so the positional order of the fields around it is what it was
+    tta: Optional[TTA] = field(default=None, kw_only=True)
     log_every: int = 1                 # iterations between log lines (each one reads three scalars back from the GPU)
     loss_scale: Union[None, float, str] = None   # float16 storage: None = no scale (1), a number = static scale, "dynamic" = a default
                                        # train.DynamicLossScale (device-resident, adjusts itself inside the captured step)
@@ -89,6 +92,8 @@ class TrainConfig:
             raise ValueError("no_decay needs optimizer=\"adamw\" or \"adam\": the SGD kernel takes one decay for all segments")
         if self.postprocess is not None and not isinstance(self.postprocess, PostProcess):
             raise ValueError(f"postprocess must be None or an evaluate.PostProcess, got {self.postprocess!r}")
+        if self.tta is not None and not isinstance(self.tta, TTA):
+            raise ValueError(f"tta must be None or an evaluate.TTA, got {self.tta!r}")
         make_loss_scale(self.loss_scale)
         check_class_weights("class_weights", self.class_weights, self.num_classes, need_positive=True)
         check_ignore_index(self.ignore_index, self.num_classes)
@@ -242,7 +247,7 @@ def trainer_synapse(cfg: TrainConfig, model, snapshot_path: str, volumes: Option
                         # the averaged weights are swapped into the arenas for the evaluation and out again (every rank holds the same average)
                         with ema.swapped() if ema is not None and cfg.ema_eval else contextlib.nullcontext():
                             mean_dice, mean_hd95 = inference(model, vols, cfg.num_classes, cfg.img_size, log=log, device_metrics=cfg.device_metrics,
-                                                            voxelspacing=cfg.voxelspacing, postprocess=cfg.postprocess)
+                                                            voxelspacing=cfg.voxelspacing, postprocess=cfg.postprocess, tta=cfg.tta)
                         res[0], res[1], res[2] = mean_dice * len(vols), mean_hd95 * len(vols), len(vols)
                         model.train()
                     if distributed:
