@@ -404,6 +404,9 @@ int tc_softmax_bwd(const void* dy, const void* y, void* dx, float* scratch, int 
  *   O[b] = softmax(Q[b] K[b]^T * scale) V[b],  head dim 64, no score matrix in HBM.
  *   lse[b, q] = log-sum-exp of the scaled scores (fp32), saved for backward.
  * Replaces MSTr.py:2281-2287 (M_EfficientSelfAtten: q@k^T*scale -> softmax -> @v) and its backward.
+ * tc_attn_fwd / tc_attn_bwd are the fp32 parity form: one query group per launch, exact fp32 products, dtype = TC_F32 only
+ * (any other dtype is TC_ERR_ARG, before any launch).  tc_attn_fwd_seg / tc_attn_bwd_seg below run them once per segment for
+ * fp32 storage; 16-bit storage goes through the _seg entries, which have their own kernels.
  */
 int tc_attn_fwd(const void* Q, int ldq, long long sq, const void* K, int ldk, const void* V, int ldv,
                 long long skv, void* O, int ldo, long long so, float* lse, int B, int Nq, int Nk,

@@ -256,6 +256,7 @@ class Graph:
     # branches, which hipStreamEndCapture crashed on for some shapes.
     ngroups = 1          # ops with parameters run `ngroups` stacked row blocks, block g with the weights at +g*P.gs
     pgs = 0
+    use_fused_attention = False   # attention(): the fused kernels (attention_seg) instead of bmm + softmax + bmm
 
     def grouped(self, n: int, pgs: int) -> _Grouped:
         return _Grouped(self, n, pgs)
@@ -2028,10 +2029,12 @@ class Graph:
         return out
 
     def attention(self, q: Var, k: Var, v: Var, B: int, Nq: int, Nk: int, scale: float, out: Optional[Var] = None) -> Var:
-        """softmax(q k^T * scale) v per batch (single head, d = q.cols)."""
-        d = q.cols
+        """softmax(q k^T * scale) v per batch (single head, d = q.cols).  With use_fused_attention this is attention_seg with one
+        segment (stage-major and image-major rows coincide), under its conditions: d = 64, contiguous q / out, and q / k / v used
+        once -- a k / v gradient that other consumers add to is not supported.  Otherwise op by op: bmm, softmax, bmm."""
         if self.use_fused_attention:
-            return self._attention_fused(q, k, v, B, Nq, Nk, scale, out)
+            return self.attention_seg(q, k, v, B, [Nq], Nk, scale, out=out)
+        d = q.cols
         S = self.new(B * Nq, Nk)
         self.bmm(q, k, S, Nq, Nk, d, 0, 1, nb1=B, sA=(Nq * q.ld, 0), sB=(Nk * k.ld, 0), sC=(Nq * Nk, 0), alpha=scale)
         Pm = self.softmax(S, B, 1)
@@ -2039,8 +2042,6 @@ class Graph:
             out = self.new(B * Nq, d)
         self.bmm(Pm, v, out, Nq, d, Nk, 0, 0, nb1=B, sA=(Nq * Nk, 0), sB=(Nk * v.ld, 0), sC=(Nq * out.ld, 0))
         return out
-
-    use_fused_attention = False
 
     def attention_seg(self, q: Var, k: Var, v: Var, B: int, nq: List[int], Nk: int, scale: float, out: Optional[Var] = None,
                       q_prescaled: bool = False) -> Var:
@@ -2075,32 +2076,5 @@ class Graph:
                 _ptr(q.data), q.ld, _ptr(k.data), k.ld, _ptr(v.data), v.ld, Nk * k.ld, _ptr(out.data), out.ld, _ptr(dO),
                 dO.stride(0), _ptr(lse), _ptr(delta), _ptr(dkv32), _ptr(gq), gq.stride(0), _ptr(gk), gk.stride(0), _ptr(gv),
                 gv.stride(0), Nk * gk.stride(0), B, len(nq), nq_c, Nk, scale, int(q_prescaled), self.dt, self.stream))
-        self._rec(bwd)
-        return out
-
-    def _attention_fused(self, q: Var, k: Var, v: Var, B: int, Nq: int, Nk: int, scale: float, out: Optional[Var] = None) -> Var:
-        d = q.cols
-        assert d == 64
-        if out is None:
-            out = self.new(B * Nq, d)
-        lse = self.f32(B * Nq)
-        _timed("attn_fwd", 4.0 * B * Nq * Nk * d, lambda: self.L.tc_attn_fwd(
-            _ptr(q.data), q.ld, Nq * q.ld, _ptr(k.data), k.ld, _ptr(v.data), v.ld, Nk * k.ld, _ptr(out.data), out.ld, Nq * out.ld,
-            _ptr(lse), B, Nq, Nk, scale, self.dt, self.stream))
-
-        def bwd():
-            dO = self.grad_of(out)
-            if dO is None:
-                return
-            gq, aq = self.wgrad(q)
-            gk, ak = self.wgrad(k)
-            gv, av = self.wgrad(v)
-            assert not aq and ak == av, "fused attention: q single-use, k/v written together"
-            delta = self.f32(B * Nq)
-            _timed("attn_bwd", 10.0 * B * Nq * Nk * d, lambda: self.L.tc_attn_bwd(
-                _ptr(q.data), q.ld, Nq * q.ld, _ptr(k.data), k.ld, _ptr(v.data), v.ld, Nk * k.ld, _ptr(out.data), out.ld,
-                Nq * out.ld, _ptr(dO), dO.stride(0), Nq * dO.stride(0), _ptr(lse), _ptr(delta), _ptr(gq), gq.stride(0),
-                Nq * gq.stride(0), _ptr(gk), gk.stride(0), _ptr(gv), gv.stride(0), Nk * gk.stride(0), ak, B, Nq, Nk, scale,
-                self.dt, self.stream))
         self._rec(bwd)
         return out
