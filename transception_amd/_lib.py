@@ -3,7 +3,8 @@
 The binding is derived from include/transception_hip.h at import (_header.py): signatures, structs and constants are written
 once, in the header.  What stands here is the list of names the host imports.  The connected-component post-processing entries,
 which replace no reference call site, have a header and a version of their own (include/transception_post.h -> POST), and so has the
-weight averaging (include/transception_ema.h -> EMA) and the test-time augmentation (include/transception_tta.h -> TTA).
+weight averaging (include/transception_ema.h -> EMA), the test-time augmentation (include/transception_tta.h -> TTA) and the resampling of
+class scores (include/transception_resample.h -> RESAMPLE).
 
 There is deliberately NO fallback: if the shared library is missing or a call returns a non-zero
 status the host raises.  (The CPU oracle under oracle/ is test infrastructure and is never imported here.)
@@ -24,6 +25,7 @@ K, S = ABI.constants, ABI.structs
 POST = _header.load(os.path.join(os.path.dirname(_header.HEADER), "transception_post.h"))    # connected-component post-processing: a header of its own
 EMA = _header.load(os.path.join(os.path.dirname(_header.HEADER), "transception_ema.h"))      # weight averaging on the flat arenas: likewise
 TTA = _header.load(os.path.join(os.path.dirname(_header.HEADER), "transception_tta.h"))      # test-time augmentation views: likewise
+RESAMPLE = _header.load(os.path.join(os.path.dirname(_header.HEADER), "transception_resample.h"))   # bilinear class scores + argmax: likewise
 
 ABI_VERSION = K["TC_ABI_VERSION"]
 TC_F32, TC_BF16, TC_F16 = K["TC_F32"], K["TC_BF16"], K["TC_F16"]
@@ -40,6 +42,7 @@ POST_ABI_VERSION = POST.constants["TC_POST_ABI_VERSION"]
 TC_CC_LARGEST, TC_CC_MIN_VOXELS = POST.constants["TC_CC_LARGEST"], POST.constants["TC_CC_MIN_VOXELS"]
 EMA_ABI_VERSION = EMA.constants["TC_EMA_ABI_VERSION"]
 TTA_ABI_VERSION = TTA.constants["TC_TTA_ABI_VERSION"]
+RESAMPLE_ABI_VERSION, TC_RESAMPLE_MAX_EXTENT = RESAMPLE.constants["TC_RESAMPLE_ABI_VERSION"], RESAMPLE.constants["TC_RESAMPLE_MAX_EXTENT"]
 TC_TTA_FLIP_H, TC_TTA_FLIP_W, TC_TTA_TRANSPOSE = TTA.constants["TC_TTA_FLIP_H"], TTA.constants["TC_TTA_FLIP_W"], TTA.constants["TC_TTA_TRANSPOSE"]
 
 TcGemm, TcLnFold, TcDwFold, TcDwSeg, TcFfnSeg = S["TcGemm"], S["TcLnFold"], S["TcDwFold"], S["TcDwSeg"], S["TcFfnSeg"]
@@ -59,7 +62,8 @@ class _Lib:
                           "(there is no CPU/PyTorch fallback for the TransCeption hot path)")
         self.path = path
         self.cdll = C.CDLL(path)
-        for name, f in (*ABI.functions.items(), *POST.functions.items(), *EMA.functions.items(), *TTA.functions.items()):
+        for name, f in (*ABI.functions.items(), *POST.functions.items(), *EMA.functions.items(), *TTA.functions.items(),
+                        *RESAMPLE.functions.items()):
             fn = getattr(self.cdll, name)          # AttributeError if a declared symbol is not exported
             fn.argtypes = f.argtypes
             fn.restype = f.restype
@@ -76,6 +80,9 @@ class _Lib:
         v = self.cdll.tc_tta_abi_version()
         if v != TTA_ABI_VERSION:
             raise TcError(f"test-time augmentation ABI mismatch: library {v}, host {TTA_ABI_VERSION}")
+        v = self.cdll.tc_resample_abi_version()
+        if v != RESAMPLE_ABI_VERSION:
+            raise TcError(f"score resampling ABI mismatch: library {v}, host {RESAMPLE_ABI_VERSION}")
 
     @staticmethod
     def _checked(name, fn):

@@ -12,7 +12,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libtransception_hip.so")
-SOURCES = ["gemm.hip", "norm.hip", "dwconv.hip", "softmax.hip", "attention.hip", "attention_seg.hip", "elementwise.hip", "train.hip", "factoratt.hip", "data.hip", "mixffn.hip", "mixffn_bwd.hip", "effatt.hip", "cbam.hip", "ripm.hip", "linln.hip", "lncls.hip", "legacy.hip", "metrics.hip", "postprocess.hip", "ema.hip", "tta.hip"]
+SOURCES = ["gemm.hip", "norm.hip", "dwconv.hip", "softmax.hip", "attention.hip", "attention_seg.hip", "elementwise.hip", "train.hip", "factoratt.hip", "data.hip", "mixffn.hip", "mixffn_bwd.hip", "effatt.hip", "cbam.hip", "ripm.hip", "linln.hip", "lncls.hip", "legacy.hip", "metrics.hip", "postprocess.hip", "ema.hip", "tta.hip", "resample.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=fast", "-munsafe-fp-atomics"]
 
 
@@ -39,7 +39,7 @@ def build(force: bool = False, verbose: bool = True) -> str:
             raise RuntimeError(f"{gen} failed:\n{r.stderr}")
     headers = [os.path.join(CSRC, "tc_common.h"), os.path.join(HERE, "..", "include", "transception_hip.h"),
                os.path.join(HERE, "..", "include", "transception_post.h"), os.path.join(HERE, "..", "include", "transception_ema.h"),
-               os.path.join(HERE, "..", "include", "transception_tta.h")]
+               os.path.join(HERE, "..", "include", "transception_tta.h"), os.path.join(HERE, "..", "include", "transception_resample.h")]
     extra = {"attention_seg.hip": [os.path.join(CSRC, "attn_fwd_asm.inc"), os.path.join(CSRC, "attn_dkv_asm.inc"), os.path.join(CSRC, "attn_dq_asm.inc")]}
     objdir = os.path.join(HERE, "build")
     os.makedirs(objdir, exist_ok=True)

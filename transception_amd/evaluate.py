@@ -31,6 +31,11 @@ orientation, dataset_synapse.py:39-46) averages the class probabilities over fli
 view `tc_tta_view` makes the normalised view, the network runs, and `tc_tta_accumulate` reads the logits once and folds their softmax
 into one fp32 accumulator at the un-transformed position -- or, for the last view, writes the label (csrc/tta.hip;
 include/transception_tta.h states the definition).  `tta=None`, the default everywhere, changes nothing.
+
+Evaluation at label resolution (`resample="scores"`; the reference carries it as a commented-out line, utils.py:81): instead of zooming the
+argmax with order 0, the class scores -- the logits, or with `TTA` the summed probabilities -- are resampled bilinearly to the label's size and
+the argmax is taken there.  `tc_resample_scores` reads the small score maps once, interpolates in registers and writes only the uint8 label
+(csrc/resample.hip; include/transception_resample.h states the definition).  `resample="labels"`, the default everywhere, changes nothing.
 """
 from __future__ import annotations
 
@@ -42,7 +47,8 @@ import math
 import numpy as np
 import torch
 
-from ._lib import TC_BF16, TC_CC_LARGEST, TC_CC_MIN_VOXELS, TC_F16, TC_F32, TC_METRIC_SELECT_WORK_BYTES, TC_TTA_TRANSPOSE, lib
+from ._lib import (TC_BF16, TC_CC_LARGEST, TC_CC_MIN_VOXELS, TC_F16, TC_F32, TC_METRIC_SELECT_WORK_BYTES, TC_RESAMPLE_MAX_EXTENT, TC_TTA_TRANSPOSE,
+                   lib)
 
 NO_CPU = "transception_amd.evaluate runs on MI355X only (no CPU fallback)"
 
@@ -418,10 +424,82 @@ def _check_tta(tta, shape=None) -> None:
 _TC_DTYPES = {torch.float32: TC_F32, torch.bfloat16: TC_BF16, torch.float16: TC_F16}
 
 
-def _tta_batches(model, slices: torch.Tensor, batch: int, tta: TTA, labels: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
+def _tta_view_logits(L, model, src: torch.Tensor, H: int, W: int, v: int, stream):
+    """(logits, C): view `v` of the fp32 [n,H,W] batch `src`, normalised (tc_tta_view), through `model`; the logits contiguous and in a dtype
+    of the library."""
+    n = src.shape[0]
+    x = torch.empty((n, 1, W, H) if v & TC_TTA_TRANSPOSE else (n, 1, H, W), dtype=torch.float32, device=src.device)
+    L.tc_tta_view(src.data_ptr(), x.data_ptr(), n, H, W, v, 0.5, 0.5, stream)
+    lg = model(x)
+    if lg.dtype not in _TC_DTYPES:
+        lg = lg.float()
+    lg = lg.contiguous()
+    C = lg.shape[1]
+    if lg.shape != x.shape[:1] + (C,) + x.shape[2:]:
+        raise ValueError(f"the model returned logits of shape {tuple(lg.shape)} for a view of shape {tuple(x.shape)}")
+    return lg, C
+
+
+RESAMPLE_MODES = ("labels", "scores")
+
+
+def _check_resample(resample, host_zoom: bool = False) -> None:
+    if not isinstance(resample, str) or resample not in RESAMPLE_MODES:
+        raise ValueError(f"resample must be one of {RESAMPLE_MODES}, got {resample!r}")
+    if resample == "scores" and host_zoom:
+        raise ValueError('resample="scores" runs on the device; host_zoom=True is the reference\'s path (order-0 zoom of the labels on the host)')
+
+
+def _check_out_size(out_size) -> Optional[Tuple[int, int]]:
+    """None, or (X, Y): two integers in 1..TC_RESAMPLE_MAX_EXTENT."""
+    if out_size is None:
+        return None
+    try:
+        X, Y = out_size
+        ok = all(not isinstance(v, bool) and isinstance(v, (int, np.integer)) and 1 <= v <= TC_RESAMPLE_MAX_EXTENT for v in (X, Y))
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError(f"out_size must be None or two integers in 1..{TC_RESAMPLE_MAX_EXTENT}, got {out_size!r}")
+    return int(X), int(Y)
+
+
+def resample_scores(src: torch.Tensor, size: Tuple[int, int], *, scores: bool = False, pred: bool = True,
+                    pred_out: Optional[torch.Tensor] = None, scores_out: Optional[torch.Tensor] = None):
+    """(scores, pred) of `src` [N,C,h,w] (fp32, bf16 or fp16 CUDA class scores) at `size` = (H, W): the bilinear, align_corners=False
+    resampling of every class map as fp32 [N,C,H,W] (`scores`) and its first-maximum argmax as uint8 [N,H,W] (`pred`), one kernel
+    (tc_resample_scores; include/transception_resample.h states the definition).  What is not asked for is None and is never written: with
+    `pred` alone nothing of the size of the resampled scores exists.  `pred_out` / `scores_out`: contiguous tensors to write into.
+    Nothing is synchronised."""
+    if not src.is_cuda:
+        raise RuntimeError(NO_CPU)
+    if src.dim() != 4 or src.dtype not in _TC_DTYPES:
+        raise ValueError("class scores are a [N,C,h,w] tensor of float32, bfloat16 or float16")
+    H, W = _check_out_size(size)
+    scores, pred = scores or scores_out is not None, pred or pred_out is not None
+    if not (scores or pred):
+        raise ValueError("ask for the scores, the labels or both")
+    src = src.contiguous()
+    N, C, h, w = src.shape
+    if scores and scores_out is None:
+        scores_out = torch.empty((N, C, H, W), dtype=torch.float32, device=src.device)
+    if pred and pred_out is None:
+        pred_out = torch.empty((N, H, W), dtype=torch.uint8, device=src.device)
+    for t, dt, shape in ((scores_out, torch.float32, (N, C, H, W)), (pred_out, torch.uint8, (N, H, W))):
+        if t is not None and (not t.is_cuda or t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous()):
+            raise ValueError(f"an output of resample_scores is a contiguous CUDA {dt} tensor of shape {shape}")
+    lib().tc_resample_scores(src.data_ptr(), _TC_DTYPES[src.dtype], scores_out.data_ptr() if scores else None,
+                             pred_out.data_ptr() if pred else None, N, C, h, w, H, W, torch.cuda.current_stream(src.device).cuda_stream)
+    return (scores_out if scores else None), (pred_out if pred else None)
+
+
+def _tta_batches(model, slices: torch.Tensor, batch: int, tta: TTA, labels: Optional[torch.Tensor],
+                 out_size: Optional[Tuple[int, int]] = None) -> Optional[torch.Tensor]:
     """The views of every batch of `slices` through `model` and tc_tta_accumulate, in the order given.  With `labels` (uint8 [N,H,W]) the last
     view writes the labels and one fp32 [batch,C,H,W] accumulator, allocated at the first logits (none for a single view), holds the views
-    before it.  Without, every view is added into the batch's part of an fp32 [N,C,H,W] tensor of sums, which is returned."""
+    before it.  Without, every view is added into the batch's part of an fp32 [N,C,H,W] tensor of sums, which is returned.
+    `out_size` = (X, Y): every view, the last included, is added into the [batch,C,H,W] accumulator, which tc_resample_scores then takes to
+    (X, Y): to `labels` (uint8 [N,X,Y]) or, without, to the batch's part of the returned fp32 [N,C,X,Y] sums."""
     if not slices.is_cuda:
         raise RuntimeError(NO_CPU)
     N, H, W = slices.shape
@@ -429,19 +507,27 @@ def _tta_batches(model, slices: torch.Tensor, batch: int, tta: TTA, labels: Opti
     views = tta.views
     L, stream = lib(), torch.cuda.current_stream(slices.device).cuda_stream
     acc, out = None, None
+    if out_size is not None:
+        for i in range(0, N, batch):
+            src = slices[i:i + batch].float().contiguous()
+            n = src.shape[0]
+            for j, v in enumerate(views):
+                lg, C = _tta_view_logits(L, model, src, H, W, int(v), stream)
+                if acc is None:
+                    acc = torch.empty((batch, C, H, W), dtype=torch.float32, device=src.device)
+                    if labels is None:
+                        out = torch.empty((N, C) + tuple(out_size), dtype=torch.float32, device=src.device)
+                L.tc_tta_accumulate(lg.data_ptr(), _TC_DTYPES[lg.dtype], acc.data_ptr(), None, n, C, H, W, int(v), int(j == 0), stream)
+            if labels is None:
+                resample_scores(acc[:n], out_size, pred=False, scores_out=out[i:i + n])
+            else:
+                resample_scores(acc[:n], out_size, pred_out=labels[i:i + n])
+        return out
     for i in range(0, N, batch):
         src = slices[i:i + batch].float().contiguous()
         n = src.shape[0]
         for j, v in enumerate(views):
-            x = torch.empty((n, 1, W, H) if int(v) & TC_TTA_TRANSPOSE else (n, 1, H, W), dtype=torch.float32, device=src.device)
-            L.tc_tta_view(src.data_ptr(), x.data_ptr(), n, H, W, int(v), 0.5, 0.5, stream)
-            lg = model(x)
-            if lg.dtype not in _TC_DTYPES:
-                lg = lg.float()
-            lg = lg.contiguous()
-            C = lg.shape[1]
-            if lg.shape != x.shape[:1] + (C,) + x.shape[2:]:
-                raise ValueError(f"the model returned logits of shape {tuple(lg.shape)} for a view of shape {tuple(x.shape)}")
+            lg, C = _tta_view_logits(L, model, src, H, W, int(v), stream)
             first, last = int(j == 0), j == len(views) - 1
             if labels is None:
                 if out is None:
@@ -456,18 +542,29 @@ def _tta_batches(model, slices: torch.Tensor, batch: int, tta: TTA, labels: Opti
 
 
 @torch.no_grad()
-def predict_slices(model, slices: torch.Tensor, batch: int = 16, tta: Optional[TTA] = None) -> torch.Tensor:
+def predict_slices(model, slices: torch.Tensor, batch: int = 16, tta: Optional[TTA] = None, *, out_size: Optional[Tuple[int, int]] = None) -> torch.Tensor:
     """slices: float [N,H,W] in [0,1] at the network size (a multiple of 32); returns uint8 [N,H,W] labels.
     Normalisation (x-0.5)/0.5 as `transforms.Normalize([0.5],[0.5])` (utils.py:71-75); eval-mode BatchNorm (utils.py:78).
     `tta`: a `TTA`; the label is then the argmax of the class probabilities summed over its views (`views=(0,)` is softmax-then-argmax of
-    the one plain pass: not bit-pinned to the path without `tta`, which takes the argmax of the logits)."""
+    the one plain pass: not bit-pinned to the path without `tta`, which takes the argmax of the logits).
+    `out_size` = (X, Y) other than (H, W): uint8 [N,X,Y] labels, the argmax of the class scores resampled bilinearly to that size
+    (tc_resample_scores) -- each batch's logits in their own dtype, or with `tta` the summed probabilities of all its views.  None or
+    (H, W): the calls above, unchanged."""
     _check_tta(tta)
+    out_size = _check_out_size(out_size)
+    if out_size == tuple(slices.shape[1:]):
+        out_size = None
     was_training = model.training
     model.eval()
-    out = torch.empty(slices.shape, dtype=torch.uint8, device=slices.device)
+    out = torch.empty(slices.shape if out_size is None else slices.shape[:1] + out_size, dtype=torch.uint8, device=slices.device)
     try:
         if tta is not None:
-            _tta_batches(model, slices, batch, tta, out)
+            _tta_batches(model, slices, batch, tta, out, out_size)
+        elif out_size is not None:
+            for i in range(0, slices.shape[0], batch):
+                x = ((slices[i:i + batch].float() - 0.5) / 0.5).unsqueeze(1)
+                lg = model(x)
+                resample_scores(lg if lg.dtype in _TC_DTYPES else lg.float(), out_size, pred_out=out[i:i + batch])
         else:
             for i in range(0, slices.shape[0], batch):
                 x = ((slices[i:i + batch].float() - 0.5) / 0.5).unsqueeze(1)
@@ -478,17 +575,21 @@ def predict_slices(model, slices: torch.Tensor, batch: int = 16, tta: Optional[T
 
 
 @torch.no_grad()
-def predict_probs(model, slices: torch.Tensor, batch: int = 16, tta: Optional[TTA] = None) -> torch.Tensor:
+def predict_probs(model, slices: torch.Tensor, batch: int = 16, tta: Optional[TTA] = None, *, out_size: Optional[Tuple[int, int]] = None) -> torch.Tensor:
     """The class probabilities of `predict_slices`' input averaged over the views of `tta` (None: the single view 0): fp32 [N,C,H,W], the
-    accumulator of tc_tta_accumulate divided by the number of views."""
+    accumulator of tc_tta_accumulate divided by the number of views.  `out_size` = (X, Y) other than (H, W): fp32 [N,C,X,Y], the accumulator
+    resampled bilinearly (the `scores` output of tc_resample_scores) and then divided."""
     _check_tta(tta)
+    out_size = _check_out_size(out_size)
+    if out_size == tuple(slices.shape[1:]):
+        out_size = None
     tta = tta if tta is not None else TTA((0,))
     if slices.shape[0] == 0:
         raise ValueError("predict_probs needs at least one slice")
     was_training = model.training
     model.eval()
     try:
-        out = _tta_batches(model, slices, batch, tta, None)
+        out = _tta_batches(model, slices, batch, tta, None, out_size)
     finally:
         model.train(was_training)
     return out.div_(len(tta.views)) if len(tta.views) > 1 else out
@@ -528,7 +629,7 @@ def zoom_labels(pred: torch.Tensor, size: Tuple[int, int]) -> torch.Tensor:
 @torch.no_grad()
 def evaluate_volume(model, image: np.ndarray, label: np.ndarray, classes: int = 9, patch_size=(224, 224),
                     batch: int = 16, with_hd95: bool = False, host_zoom: bool = False, device_metrics: bool = False, voxelspacing=None,
-                    postprocess: Optional[PostProcess] = None, tta: Optional[TTA] = None):
+                    postprocess: Optional[PostProcess] = None, tta: Optional[TTA] = None, *, resample: str = "labels"):
     """`test_single_volume` for one [D,H,W] volume (utils.py:63-98): per-class Dice for classes 1..classes-1, or with
     `with_hd95` the reference's metric_list of (dice, hd95) pairs.  The volume goes to the GPU once; the order-3 zoom to the network
     size, inference, argmax and the order-0 zoom back all run there (host_zoom=True: scipy per slice, as the reference does).
@@ -537,7 +638,13 @@ def evaluate_volume(model, image: np.ndarray, label: np.ndarray, classes: int = 
     of `label`, for the HD95 of either metric path (Dice does not depend on it).  `postprocess`: a `PostProcess` applied in 3-D to the
     prediction at `label`'s resolution (after the order-0 zoom back) before either metric path: on the device wherever the prediction is
     there (host_zoom=False, whatever `device_metrics` is), else on the host; None: no such step.  `tta`: a `TTA` handed to `predict_slices`
-    (both zoom paths; the views are taken at the network size, before the zoom back and `postprocess`); None: one plain pass."""
+    (both zoom paths; the views are taken at the network size, before the zoom back and `postprocess`); None: one plain pass.
+    `resample`: what goes from the network size to `label`'s.  "labels": the argmax, by the reference's order-0 zoom (utils.py:83-84).
+    "scores": the class scores (with `tta` the summed probabilities), bilinearly, and then the argmax -- the reference's commented-out
+    `F.interpolate(outputs, ..., mode='bilinear')` (utils.py:81) -- fused in tc_resample_scores, so that only the uint8 labels exist at
+    `label`'s size; `postprocess` and both metric paths follow as before.  Without a resize both values run the same calls; "scores" with
+    `host_zoom=True` is a ValueError."""
+    _check_resample(resample, host_zoom)
     if postprocess is not None and not isinstance(postprocess, PostProcess):
         raise ValueError(f"postprocess must be None or a PostProcess, got {postprocess!r}")
     _check_tta(tta, tuple(patch_size))
@@ -557,8 +664,11 @@ def evaluate_volume(model, image: np.ndarray, label: np.ndarray, classes: int = 
     else:
         vol = torch.from_numpy(np.ascontiguousarray(image, np.float32)).to(dev)
         sl = zoom_volume_to_network(vol, tuple(patch_size)) if resize else vol
-        pred_d = predict_slices(model, sl, batch, tta)
-        pred = zoom_labels(pred_d, (X, Y)) if resize else pred_d
+        if resize and resample == "scores":
+            pred = predict_slices(model, sl, batch, tta, out_size=(X, Y))
+        else:
+            pred_d = predict_slices(model, sl, batch, tta)
+            pred = zoom_labels(pred_d, (X, Y)) if resize else pred_d
         if postprocess is not None:
             pred = postprocess_device(pred, classes, postprocess, out=pred)
         if not device_metrics:
@@ -580,14 +690,15 @@ def evaluate_volume(model, image: np.ndarray, label: np.ndarray, classes: int = 
 
 def inference(model, volumes, classes: int = 9, img_size: int = 224, batch: int = 16, log=None,
               device_metrics: bool = False, voxelspacing=None, postprocess: Optional[PostProcess] = None,
-              tta: Optional[TTA] = None) -> Tuple[float, float]:
+              tta: Optional[TTA] = None, *, resample: str = "labels") -> Tuple[float, float]:
     """trainer.py:25-47: mean Dice and mean HD95 over `volumes` = iterable of (image [D,H,W] in [0,1], label [D,H,W], case name).
-    `device_metrics`, `voxelspacing` (one spacing for every volume), `postprocess`, `tta`: as in `evaluate_volume`."""
+    `device_metrics`, `voxelspacing` (one spacing for every volume), `postprocess`, `tta`, `resample`: as in `evaluate_volume`."""
     _check_tta(tta)
+    _check_resample(resample)
     total, n = 0.0, 0
     for i, (image, label, name) in enumerate(volumes):
         m = np.array(evaluate_volume(model, np.asarray(image), np.asarray(label), classes, (img_size, img_size), batch, with_hd95=True,
-                                     device_metrics=device_metrics, voxelspacing=voxelspacing, postprocess=postprocess, tta=tta))
+                                     device_metrics=device_metrics, voxelspacing=voxelspacing, postprocess=postprocess, tta=tta, resample=resample))
         total = total + m
         n += 1
         if log:

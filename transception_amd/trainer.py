@@ -17,6 +17,7 @@ from __future__ import annotations
 
 import contextlib
 import logging
+import inspect
 import math
 import os
 from dataclasses import dataclass, field
@@ -26,7 +27,7 @@ import torch
 import torch.distributed as dist
 
 from .data import DeviceLoader, SynapseSlices
-from .evaluate import TTA, PostProcess, inference
+from .evaluate import RESAMPLE_MODES, TTA, PostProcess, inference
 from .train import (DynamicLossScale, FusedAdamW, FusedSGD, GraphedStep, SegLoss, WeightEMA, check_class_weights, check_ema_decay,
                     check_ignore_index, cosine_lr, train_step)
 
@@ -94,11 +95,36 @@ class TrainConfig:
             raise ValueError(f"postprocess must be None or an evaluate.PostProcess, got {self.postprocess!r}")
         if self.tta is not None and not isinstance(self.tta, TTA):
             raise ValueError(f"tta must be None or an evaluate.TTA, got {self.tta!r}")
+        if not isinstance(self.resample, str) or self.resample not in RESAMPLE_MODES:
+            raise ValueError(f"resample must be one of {RESAMPLE_MODES}, got {self.resample!r}")
         make_loss_scale(self.loss_scale)
         check_class_weights("class_weights", self.class_weights, self.num_classes, need_positive=True)
         check_ignore_index(self.ignore_index, self.num_classes)
         if self.ema_decay is not None:
             check_ema_decay(self.ema_decay)
+
+
+def _keyword_only_resample(cls):
+    """`TrainConfig(..., resample="labels")`: what the evaluation resamples to the label's size (evaluate.evaluate_volume: "labels", the
+    reference's order-0 zoom of the argmax, or "scores", bilinear class scores and then the argmax).  Keyword-only, validated in
+    `__post_init__` and kept as a plain attribute beside the dataclass fields: the field list -- the positional order, repr and eq of the
+    configuration, which ends with the ema_* fields -- is what it was."""
+    init = cls.__init__
+
+    def __init__(self, *args, resample: str = "labels", **kwargs):
+        self.resample = resample
+        init(self, *args, **kwargs)
+
+    sig = inspect.signature(init)
+    extra = inspect.Parameter("resample", inspect.Parameter.KEYWORD_ONLY, default="labels", annotation=str)
+    __init__.__signature__ = sig.replace(parameters=[*sig.parameters.values(), extra])
+    __init__.__qualname__ = init.__qualname__
+    cls.__init__ = __init__
+    cls.resample = "labels"                       # the default, readable on the class as a field's would be
+    return cls
+
+
+TrainConfig = _keyword_only_resample(TrainConfig)
 
 
 def make_loss_scale(spec) -> Union[float, DynamicLossScale]:
@@ -247,7 +273,7 @@ def trainer_synapse(cfg: TrainConfig, model, snapshot_path: str, volumes: Option
                         # the averaged weights are swapped into the arenas for the evaluation and out again (every rank holds the same average)
                         with ema.swapped() if ema is not None and cfg.ema_eval else contextlib.nullcontext():
                             mean_dice, mean_hd95 = inference(model, vols, cfg.num_classes, cfg.img_size, log=log, device_metrics=cfg.device_metrics,
-                                                            voxelspacing=cfg.voxelspacing, postprocess=cfg.postprocess, tta=cfg.tta)
+                                                            voxelspacing=cfg.voxelspacing, postprocess=cfg.postprocess, tta=cfg.tta, resample=cfg.resample)
                         res[0], res[1], res[2] = mean_dice * len(vols), mean_hd95 * len(vols), len(vols)
                         model.train()
                     if distributed:
