@@ -14,6 +14,26 @@ from typing import NamedTuple
 
 HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "transception_hip.h")
 
+
+class SideHeader(NamedTuple):
+    """A part of the C ABI that replaces no reference call site and so has a header and a version of its own."""
+    attr: str                 # the name _lib.py gives the parsed header
+    file: str                 # beside HEADER
+    version: str              # the constant that holds the host's version
+    entry: str                # the TC_QUERY entry that returns the library's
+    what: str                 # how a mismatch names it
+
+    @property
+    def path(self) -> str:
+        return os.path.join(os.path.dirname(HEADER), self.file)
+
+
+# read by _lib.py (load, bind, version check) and by build.py (staleness): a new side header is one line here
+SIDE_HEADERS = (SideHeader("POST", "transception_post.h", "TC_POST_ABI_VERSION", "tc_post_abi_version", "post-processing"),
+                SideHeader("EMA", "transception_ema.h", "TC_EMA_ABI_VERSION", "tc_ema_abi_version", "weight-averaging"),
+                SideHeader("TTA", "transception_tta.h", "TC_TTA_ABI_VERSION", "tc_tta_abi_version", "test-time augmentation"),
+                SideHeader("RESAMPLE", "transception_resample.h", "TC_RESAMPLE_ABI_VERSION", "tc_resample_abi_version", "score resampling"))
+
 SCALARS = {"int": C.c_int, "long long": C.c_longlong, "float": C.c_float, "double": C.c_double,
            "unsigned": C.c_uint, "unsigned int": C.c_uint}
 POINTEES = set(SCALARS) | {"void", "unsigned char"}       # what a pointer may point to, besides the structs; every pointer is a c_void_p

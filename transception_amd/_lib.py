@@ -22,10 +22,8 @@ LIB_PATH = os.environ.get("TC_LIB_PATH") or os.path.join(HERE, "libtransception_
 ABI = _header.load()
 SIGNATURES = {name: f.argtypes for name, f in ABI.functions.items()}     # every pointer is a c_void_p: byref(), arrays, addresses, None
 K, S = ABI.constants, ABI.structs
-POST = _header.load(os.path.join(os.path.dirname(_header.HEADER), "transception_post.h"))    # connected-component post-processing: a header of its own
-EMA = _header.load(os.path.join(os.path.dirname(_header.HEADER), "transception_ema.h"))      # weight averaging on the flat arenas: likewise
-TTA = _header.load(os.path.join(os.path.dirname(_header.HEADER), "transception_tta.h"))      # test-time augmentation views: likewise
-RESAMPLE = _header.load(os.path.join(os.path.dirname(_header.HEADER), "transception_resample.h"))   # bilinear class scores + argmax: likewise
+SIDE = {s.attr: _header.load(s.path) for s in _header.SIDE_HEADERS}       # the headers of their own: one line each in _header.SIDE_HEADERS
+POST, EMA, TTA, RESAMPLE = SIDE["POST"], SIDE["EMA"], SIDE["TTA"], SIDE["RESAMPLE"]
 
 ABI_VERSION = K["TC_ABI_VERSION"]
 TC_F32, TC_BF16, TC_F16 = K["TC_F32"], K["TC_BF16"], K["TC_F16"]
@@ -38,11 +36,9 @@ TC_AUG_SKIP, TC_AUG_FROM_RAW = K["TC_AUG_SKIP"], K["TC_AUG_FROM_RAW"]
 ATTN_DKV_SPLITS = K["TC_ATTN_DKV_SPLITS"]
 TC_METRIC_NO_SOURCE, TC_METRIC_SELECT_WORK_BYTES = K["TC_METRIC_NO_SOURCE"], K["TC_METRIC_SELECT_WORK_BYTES"]
 TC_IGNORE_NONE = K["TC_IGNORE_NONE"]
-POST_ABI_VERSION = POST.constants["TC_POST_ABI_VERSION"]
+POST_ABI_VERSION, EMA_ABI_VERSION, TTA_ABI_VERSION, RESAMPLE_ABI_VERSION = (SIDE[s.attr].constants[s.version] for s in _header.SIDE_HEADERS)
 TC_CC_LARGEST, TC_CC_MIN_VOXELS = POST.constants["TC_CC_LARGEST"], POST.constants["TC_CC_MIN_VOXELS"]
-EMA_ABI_VERSION = EMA.constants["TC_EMA_ABI_VERSION"]
-TTA_ABI_VERSION = TTA.constants["TC_TTA_ABI_VERSION"]
-RESAMPLE_ABI_VERSION, TC_RESAMPLE_MAX_EXTENT = RESAMPLE.constants["TC_RESAMPLE_ABI_VERSION"], RESAMPLE.constants["TC_RESAMPLE_MAX_EXTENT"]
+TC_RESAMPLE_MAX_EXTENT = RESAMPLE.constants["TC_RESAMPLE_MAX_EXTENT"]
 TC_TTA_FLIP_H, TC_TTA_FLIP_W, TC_TTA_TRANSPOSE = TTA.constants["TC_TTA_FLIP_H"], TTA.constants["TC_TTA_FLIP_W"], TTA.constants["TC_TTA_TRANSPOSE"]
 
 TcGemm, TcLnFold, TcDwFold, TcDwSeg, TcFfnSeg = S["TcGemm"], S["TcLnFold"], S["TcDwFold"], S["TcDwSeg"], S["TcFfnSeg"]
@@ -62,27 +58,18 @@ class _Lib:
                           "(there is no CPU/PyTorch fallback for the TransCeption hot path)")
         self.path = path
         self.cdll = C.CDLL(path)
-        for name, f in (*ABI.functions.items(), *POST.functions.items(), *EMA.functions.items(), *TTA.functions.items(),
-                        *RESAMPLE.functions.items()):
-            fn = getattr(self.cdll, name)          # AttributeError if a declared symbol is not exported
-            fn.argtypes = f.argtypes
-            fn.restype = f.restype
-            setattr(self, name, fn if f.query else self._checked(name, fn))
-        v = self.cdll.tc_abi_version()
-        if v != ABI_VERSION:
-            raise TcError(f"ABI mismatch: library {v}, host {ABI_VERSION}")
-        v = self.cdll.tc_post_abi_version()
-        if v != POST_ABI_VERSION:
-            raise TcError(f"post-processing ABI mismatch: library {v}, host {POST_ABI_VERSION}")
-        v = self.cdll.tc_ema_abi_version()
-        if v != EMA_ABI_VERSION:
-            raise TcError(f"weight-averaging ABI mismatch: library {v}, host {EMA_ABI_VERSION}")
-        v = self.cdll.tc_tta_abi_version()
-        if v != TTA_ABI_VERSION:
-            raise TcError(f"test-time augmentation ABI mismatch: library {v}, host {TTA_ABI_VERSION}")
-        v = self.cdll.tc_resample_abi_version()
-        if v != RESAMPLE_ABI_VERSION:
-            raise TcError(f"score resampling ABI mismatch: library {v}, host {RESAMPLE_ABI_VERSION}")
+        headers = [(ABI, "TC_ABI_VERSION", "tc_abi_version", "ABI"),
+                   *((SIDE[s.attr], s.version, s.entry, s.what + " ABI") for s in _header.SIDE_HEADERS)]
+        for header, *_ in headers:
+            for name, f in header.functions.items():
+                fn = getattr(self.cdll, name)      # AttributeError if a declared symbol is not exported
+                fn.argtypes = f.argtypes
+                fn.restype = f.restype
+                setattr(self, name, fn if f.query else self._checked(name, fn))
+        for header, version, entry, what in headers:
+            v, host = getattr(self.cdll, entry)(), header.constants[version]
+            if v != host:
+                raise TcError(f"{what} mismatch: library {v}, host {host}")
 
     @staticmethod
     def _checked(name, fn):

@@ -9,6 +9,8 @@ import os
 import subprocess
 import sys
 
+from ._header import HEADER, SIDE_HEADERS
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libtransception_hip.so")
@@ -37,9 +39,7 @@ def build(force: bool = False, verbose: bool = True) -> str:
         r = subprocess.run([sys.executable, os.path.join(CSRC, gen)], capture_output=True, text=True)
         if r.returncode != 0:
             raise RuntimeError(f"{gen} failed:\n{r.stderr}")
-    headers = [os.path.join(CSRC, "tc_common.h"), os.path.join(HERE, "..", "include", "transception_hip.h"),
-               os.path.join(HERE, "..", "include", "transception_post.h"), os.path.join(HERE, "..", "include", "transception_ema.h"),
-               os.path.join(HERE, "..", "include", "transception_tta.h"), os.path.join(HERE, "..", "include", "transception_resample.h")]
+    headers = [os.path.join(CSRC, "tc_common.h"), HEADER, *(s.path for s in SIDE_HEADERS)]
     extra = {"attention_seg.hip": [os.path.join(CSRC, "attn_fwd_asm.inc"), os.path.join(CSRC, "attn_dkv_asm.inc"), os.path.join(CSRC, "attn_dq_asm.inc")]}
     objdir = os.path.join(HERE, "build")
     os.makedirs(objdir, exist_ok=True)

@@ -21,7 +21,7 @@ import torch
 from ._lib import (ATTN_DKV_SPLITS, EW_COPY, EW_DEINTERLEAVE, EW_PATCHIFY, TcEffAtt, TcEwSeg, TcFfnBwd, TcFfnFused, ACT_COORD, ACT_GELU, ACT_HSWISH, ACT_NONE, ACT_SCALE, ACT_SIGMOID, FFN_EP, FFN_LN_A, FFN_LN_B, TC_BF16, TC_F16, TC_F32, TcDwFold, TcDwSeg, TcFfnSeg,
                    TcGemm, TcLnFold, lib)
 
-_DT = {torch.float32: TC_F32, torch.bfloat16: TC_BF16, torch.float16: TC_F16}
+TC_DTYPE = {torch.float32: TC_F32, torch.bfloat16: TC_BF16, torch.float16: TC_F16}     # the storage dtypes, as the library's codes
 
 # bench.py sets this to a dict {kernel name: [(start_event, stop_event, algorithmic_flops), ...]} to time individual
 # launches with HIP events on the launching stream (the events are recorded on torch's current stream, which is the
@@ -264,7 +264,7 @@ class Graph:
     def __init__(self, dtype: torch.dtype, device, training: bool, record: bool):
         self.L = lib()
         self.dtype = dtype
-        self.dt = _DT[dtype]
+        self.dt = TC_DTYPE[dtype]
         self.dev = device
         self.training = training
         self.record = record

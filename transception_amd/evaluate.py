@@ -39,16 +39,17 @@ the argmax is taken there.  `tc_resample_scores` reads the small score maps once
 """
 from __future__ import annotations
 
+import contextlib
 from dataclasses import dataclass
-from typing import List, Optional, Tuple
+from typing import Callable, List, Optional, Tuple
 
 import math
 
 import numpy as np
 import torch
 
-from ._lib import (TC_BF16, TC_CC_LARGEST, TC_CC_MIN_VOXELS, TC_F16, TC_F32, TC_METRIC_SELECT_WORK_BYTES, TC_RESAMPLE_MAX_EXTENT, TC_TTA_TRANSPOSE,
-                   lib)
+from ._lib import TC_CC_LARGEST, TC_CC_MIN_VOXELS, TC_F32, TC_METRIC_SELECT_WORK_BYTES, TC_RESAMPLE_MAX_EXTENT, TC_TTA_TRANSPOSE, lib
+from .engine import TC_DTYPE
 
 NO_CPU = "transception_amd.evaluate runs on MI355X only (no CPU fallback)"
 
@@ -73,18 +74,20 @@ def argmax_counts(logits: torch.Tensor, labels: Optional[torch.Tensor] = None,
     return pred, counts
 
 
+def _percase(inter, p, g, hd95_fn: Callable[[], float]) -> Tuple[float, float]:
+    """The reference's rule for one class of one volume (utils.py:50-60) from |P&G|, |P| and |G|: (Dice, hd95_fn()) when both are non-empty
+    -- the distance is computed only then --, (1, 0) when only the prediction is non-empty, else (0, 0)."""
+    if p > 0 and g > 0:
+        return float(2.0 * inter / (p + g)), hd95_fn()
+    if p > 0:
+        return 1.0, 0.0
+    return 0.0, 0.0
+
+
 def dice_from_counts(counts: np.ndarray) -> List[float]:
     """Per-class Dice with calculate_metric_percase's conventions (utils.py:50-60) for classes 1..C-1:
     2|P&G|/(|P|+|G|) when both are non-empty, 1 when only the prediction is non-empty, else 0."""
-    out = []
-    for inter, p, g in np.asarray(counts, dtype=np.float64)[1:]:
-        if p > 0 and g > 0:
-            out.append(float(2.0 * inter / (p + g)))
-        elif p > 0:
-            out.append(1.0)
-        else:
-            out.append(0.0)
-    return out
+    return [_percase(inter, p, g, lambda: 0.0)[0] for inter, p, g in np.asarray(counts, dtype=np.float64)[1:]]
 
 
 def surface_distances(result: np.ndarray, reference: np.ndarray, voxelspacing=None, connectivity: int = 1) -> np.ndarray:
@@ -110,12 +113,7 @@ def hd95(result: np.ndarray, reference: np.ndarray, voxelspacing=None, connectiv
 def calculate_metric_percase(pred: np.ndarray, gt: np.ndarray, voxelspacing=None) -> Tuple[float, float]:
     """(dice, hd95) of one class of one volume with the reference's conventions (utils.py:50-60); `voxelspacing` as `hd95` takes it."""
     pred, gt = pred > 0, gt > 0
-    ps, gs = int(pred.sum()), int(gt.sum())
-    if ps > 0 and gs > 0:
-        return float(2.0 * np.logical_and(pred, gt).sum() / (ps + gs)), hd95(pred, gt, voxelspacing)
-    if ps > 0:
-        return 1.0, 0.0
-    return 0.0, 0.0
+    return _percase(np.logical_and(pred, gt).sum(), int(pred.sum()), int(gt.sum()), lambda: hd95(pred, gt, voxelspacing))
 
 
 def _shape3(shape) -> Tuple[int, int, int]:
@@ -250,15 +248,7 @@ def metrics_device(pred: torch.Tensor, label: torch.Tensor, classes: int = 9, vo
     array axis order, or a scalar): the fp64 kernels, 18 bytes a voxel.  The library takes D, H, W up to 2048 and fewer than 2^31 voxels;
     a larger volume raises `TcError`."""
     counts, sel = _order_stats_to_host(metrics_order_stats(pred, label, classes, voxelspacing), voxelspacing is not None)
-    out = []
-    for (inter, p, g), (n, lo, hi) in zip(counts[1:], sel[1:]):
-        if p > 0 and g > 0:
-            out.append((float(2.0 * inter / (p + g)), hd95_from_order_stats(n, lo, hi)))
-        elif p > 0:
-            out.append((1.0, 0.0))
-        else:
-            out.append((0.0, 0.0))
-    return out
+    return [_percase(inter, p, g, lambda: hd95_from_order_stats(n, lo, hi)) for (inter, p, g), (n, lo, hi) in zip(counts[1:], sel[1:])]
 
 
 def hd95_device(result: torch.Tensor, reference: torch.Tensor, voxelspacing=None) -> float:
@@ -413,41 +403,32 @@ class TTA:
         return cls((0, 1, 2, 3, 4, 5, 6, 7))
 
 
+RESAMPLE_MODES = ("labels", "scores")
+
+
+# what an option of the evaluation may be: `_check_options` and `TrainConfig` apply these, each with its own message
+VALID_OPTION = {"postprocess": lambda v: v is None or isinstance(v, PostProcess),
+                "tta": lambda v: v is None or isinstance(v, TTA),
+                "resample": lambda v: isinstance(v, str) and v in RESAMPLE_MODES}
+
+
 def _check_tta(tta, shape=None) -> None:
     """None or a TTA; with `shape` = (H, W) of the slices, a transposed view needs H == W."""
-    if tta is not None and not isinstance(tta, TTA):
+    if not VALID_OPTION["tta"](tta):
         raise ValueError(f"tta must be None or a TTA, got {tta!r}")
     if tta is not None and shape is not None and shape[0] != shape[1] and any(int(v) & TC_TTA_TRANSPOSE for v in tta.views):
         raise ValueError(f"a transposed view (>= 4) needs square slices, got {shape[0]} x {shape[1]}")
 
 
-_TC_DTYPES = {torch.float32: TC_F32, torch.bfloat16: TC_BF16, torch.float16: TC_F16}
-
-
-def _tta_view_logits(L, model, src: torch.Tensor, H: int, W: int, v: int, stream):
-    """(logits, C): view `v` of the fp32 [n,H,W] batch `src`, normalised (tc_tta_view), through `model`; the logits contiguous and in a dtype
-    of the library."""
-    n = src.shape[0]
-    x = torch.empty((n, 1, W, H) if v & TC_TTA_TRANSPOSE else (n, 1, H, W), dtype=torch.float32, device=src.device)
-    L.tc_tta_view(src.data_ptr(), x.data_ptr(), n, H, W, v, 0.5, 0.5, stream)
-    lg = model(x)
-    if lg.dtype not in _TC_DTYPES:
-        lg = lg.float()
-    lg = lg.contiguous()
-    C = lg.shape[1]
-    if lg.shape != x.shape[:1] + (C,) + x.shape[2:]:
-        raise ValueError(f"the model returned logits of shape {tuple(lg.shape)} for a view of shape {tuple(x.shape)}")
-    return lg, C
-
-
-RESAMPLE_MODES = ("labels", "scores")
-
-
-def _check_resample(resample, host_zoom: bool = False) -> None:
-    if not isinstance(resample, str) or resample not in RESAMPLE_MODES:
+def _check_options(postprocess, tta, resample, host_zoom: bool = False, patch=None) -> None:
+    """The options of `evaluate_volume` and `inference`, before anything runs; `patch`: (H, W) of the network's slices, where known."""
+    if not VALID_OPTION["resample"](resample):
         raise ValueError(f"resample must be one of {RESAMPLE_MODES}, got {resample!r}")
     if resample == "scores" and host_zoom:
         raise ValueError('resample="scores" runs on the device; host_zoom=True is the reference\'s path (order-0 zoom of the labels on the host)')
+    if not VALID_OPTION["postprocess"](postprocess):
+        raise ValueError(f"postprocess must be None or a PostProcess, got {postprocess!r}")
+    _check_tta(tta, patch)
 
 
 def _check_out_size(out_size) -> Optional[Tuple[int, int]]:
@@ -473,7 +454,7 @@ def resample_scores(src: torch.Tensor, size: Tuple[int, int], *, scores: bool = 
     Nothing is synchronised."""
     if not src.is_cuda:
         raise RuntimeError(NO_CPU)
-    if src.dim() != 4 or src.dtype not in _TC_DTYPES:
+    if src.dim() != 4 or src.dtype not in TC_DTYPE:
         raise ValueError("class scores are a [N,C,h,w] tensor of float32, bfloat16 or float16")
     H, W = _check_out_size(size)
     scores, pred = scores or scores_out is not None, pred or pred_out is not None
@@ -488,56 +469,80 @@ def resample_scores(src: torch.Tensor, size: Tuple[int, int], *, scores: bool = 
     for t, dt, shape in ((scores_out, torch.float32, (N, C, H, W)), (pred_out, torch.uint8, (N, H, W))):
         if t is not None and (not t.is_cuda or t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous()):
             raise ValueError(f"an output of resample_scores is a contiguous CUDA {dt} tensor of shape {shape}")
-    lib().tc_resample_scores(src.data_ptr(), _TC_DTYPES[src.dtype], scores_out.data_ptr() if scores else None,
+    lib().tc_resample_scores(src.data_ptr(), TC_DTYPE[src.dtype], scores_out.data_ptr() if scores else None,
                              pred_out.data_ptr() if pred else None, N, C, h, w, H, W, torch.cuda.current_stream(src.device).cuda_stream)
     return (scores_out if scores else None), (pred_out if pred else None)
 
 
-def _tta_batches(model, slices: torch.Tensor, batch: int, tta: TTA, labels: Optional[torch.Tensor],
-                 out_size: Optional[Tuple[int, int]] = None) -> Optional[torch.Tensor]:
-    """The views of every batch of `slices` through `model` and tc_tta_accumulate, in the order given.  With `labels` (uint8 [N,H,W]) the last
-    view writes the labels and one fp32 [batch,C,H,W] accumulator, allocated at the first logits (none for a single view), holds the views
-    before it.  Without, every view is added into the batch's part of an fp32 [N,C,H,W] tensor of sums, which is returned.
-    `out_size` = (X, Y): every view, the last included, is added into the [batch,C,H,W] accumulator, which tc_resample_scores then takes to
-    (X, Y): to `labels` (uint8 [N,X,Y]) or, without, to the batch's part of the returned fp32 [N,C,X,Y] sums."""
+def _library_dtype(logits: torch.Tensor) -> torch.Tensor:
+    """The logits as they are in a dtype the library takes, else as float32."""
+    return logits if logits.dtype in TC_DTYPE else logits.float()
+
+
+def _tta_view_logits(L, model, src: torch.Tensor, H: int, W: int, v: int, stream) -> torch.Tensor:
+    """View `v` of the fp32 [n,H,W] batch `src`, normalised (tc_tta_view), through `model`: the logits, contiguous and in a dtype of the library."""
+    n = src.shape[0]
+    x = torch.empty((n, 1, W, H) if v & TC_TTA_TRANSPOSE else (n, 1, H, W), dtype=torch.float32, device=src.device)
+    L.tc_tta_view(src.data_ptr(), x.data_ptr(), n, H, W, v, 0.5, 0.5, stream)
+    lg = _library_dtype(model(x)).contiguous()
+    if lg.shape != x.shape[:1] + lg.shape[1:2] + x.shape[2:]:
+        raise ValueError(f"the model returned logits of shape {tuple(lg.shape)} for a view of shape {tuple(x.shape)}")
+    return lg
+
+
+@contextlib.contextmanager
+def _eval_mode(model):
+    """`model` in eval mode (BatchNorm by its running statistics, utils.py:78), and back to what it was."""
+    was_training = model.training
+    model.eval()
+    try:
+        yield
+    finally:
+        model.train(was_training)
+
+
+def _predict(model, slices: torch.Tensor, batch: int, views: Optional[Tuple[int, ...]], out_size: Optional[Tuple[int, int]],
+             labels: bool) -> torch.Tensor:
+    """The one batch loop of `predict_slices` (`labels`: uint8 [N,X,Y]) and `predict_probs` (else: the fp32 [N,C,X,Y] sums over the views), `model` in
+    eval mode; (X, Y) is `out_size`, and None or (H, W) is the scores' own size.  How a batch's class scores are made: `views` None (labels
+    only) -- the torch normalisation, and the scores are the logits; else per view, in the order given, tc_tta_view, `model`,
+    tc_tta_accumulate.  Where they go: at their own size the labels come from tc_argmax_counts or from the last tc_tta_accumulate, and the
+    sums are added in place in the returned tensor; at another size tc_resample_scores writes either.  One fp32 [batch,C,H,W] accumulator,
+    allocated at the first logits, holds the views that do not go into the result: none for a single view that writes labels at its own size."""
     if not slices.is_cuda:
         raise RuntimeError(NO_CPU)
     N, H, W = slices.shape
-    _check_tta(tta, (H, W))
-    views = tta.views
-    L, stream = lib(), torch.cuda.current_stream(slices.device).cuda_stream
-    acc, out = None, None
-    if out_size is not None:
+    if out_size == (H, W):
+        out_size = None
+    in_place = out_size is None and not labels                   # the views are added into the returned sums themselves
+    need_acc = views is not None and not in_place and (out_size is not None or len(views) > 1)
+    L, stream, acc = lib(), torch.cuda.current_stream(slices.device).cuda_stream, None
+    out = torch.empty((N,) + (out_size or (H, W)), dtype=torch.uint8, device=slices.device) if labels else None
+    with _eval_mode(model):
         for i in range(0, N, batch):
-            src = slices[i:i + batch].float().contiguous()
+            src = slices[i:i + batch].float()
             n = src.shape[0]
-            for j, v in enumerate(views):
-                lg, C = _tta_view_logits(L, model, src, H, W, int(v), stream)
-                if acc is None:
-                    acc = torch.empty((batch, C, H, W), dtype=torch.float32, device=src.device)
-                    if labels is None:
-                        out = torch.empty((N, C) + tuple(out_size), dtype=torch.float32, device=src.device)
-                L.tc_tta_accumulate(lg.data_ptr(), _TC_DTYPES[lg.dtype], acc.data_ptr(), None, n, C, H, W, int(v), int(j == 0), stream)
-            if labels is None:
-                resample_scores(acc[:n], out_size, pred=False, scores_out=out[i:i + n])
+            if views is None:
+                scores = _library_dtype(model(((src - 0.5) / 0.5).unsqueeze(1)))
             else:
-                resample_scores(acc[:n], out_size, pred_out=labels[i:i + n])
-        return out
-    for i in range(0, N, batch):
-        src = slices[i:i + batch].float().contiguous()
-        n = src.shape[0]
-        for j, v in enumerate(views):
-            lg, C = _tta_view_logits(L, model, src, H, W, int(v), stream)
-            first, last = int(j == 0), j == len(views) - 1
-            if labels is None:
-                if out is None:
-                    out = torch.empty((N, C, H, W), dtype=torch.float32, device=src.device)
-                L.tc_tta_accumulate(lg.data_ptr(), _TC_DTYPES[lg.dtype], out[i:i + n].data_ptr(), None, n, C, H, W, int(v), first, stream)
-                continue
-            if acc is None and len(views) > 1:
-                acc = torch.empty((batch, C, H, W), dtype=torch.float32, device=src.device)
-            L.tc_tta_accumulate(lg.data_ptr(), _TC_DTYPES[lg.dtype], acc.data_ptr() if acc is not None else None,
-                                labels[i:i + n].data_ptr() if last else None, n, C, H, W, int(v), first, stream)
+                src = src.contiguous()
+                for j, v in enumerate(views):
+                    lg = _tta_view_logits(L, model, src, H, W, v, stream)
+                    C = lg.shape[1]
+                    if need_acc and acc is None:
+                        acc = torch.empty((batch, C, H, W), dtype=torch.float32, device=src.device)
+                    if out is None:
+                        out = torch.empty((N, C) + (out_size or (H, W)), dtype=torch.float32, device=src.device)
+                    sums = out[i:i + n] if in_place else acc
+                    last = labels and out_size is None and j == len(views) - 1
+                    L.tc_tta_accumulate(lg.data_ptr(), TC_DTYPE[lg.dtype], sums.data_ptr() if sums is not None else None,
+                                        out[i:i + n].data_ptr() if last else None, n, C, H, W, v, int(j == 0), stream)
+                scores = acc[:n] if out_size is not None else None
+            if out_size is not None:
+                resample_scores(scores, out_size, pred=labels, pred_out=out[i:i + n] if labels else None, scores_out=None if labels else out[i:i + n])
+            elif views is None:
+                out[i:i + n] = argmax_counts(scores)[0]
+            del scores                                           # a batch's logits do not live through the next batch's forward
     return out
 
 
@@ -550,28 +555,8 @@ def predict_slices(model, slices: torch.Tensor, batch: int = 16, tta: Optional[T
     `out_size` = (X, Y) other than (H, W): uint8 [N,X,Y] labels, the argmax of the class scores resampled bilinearly to that size
     (tc_resample_scores) -- each batch's logits in their own dtype, or with `tta` the summed probabilities of all its views.  None or
     (H, W): the calls above, unchanged."""
-    _check_tta(tta)
-    out_size = _check_out_size(out_size)
-    if out_size == tuple(slices.shape[1:]):
-        out_size = None
-    was_training = model.training
-    model.eval()
-    out = torch.empty(slices.shape if out_size is None else slices.shape[:1] + out_size, dtype=torch.uint8, device=slices.device)
-    try:
-        if tta is not None:
-            _tta_batches(model, slices, batch, tta, out, out_size)
-        elif out_size is not None:
-            for i in range(0, slices.shape[0], batch):
-                x = ((slices[i:i + batch].float() - 0.5) / 0.5).unsqueeze(1)
-                lg = model(x)
-                resample_scores(lg if lg.dtype in _TC_DTYPES else lg.float(), out_size, pred_out=out[i:i + batch])
-        else:
-            for i in range(0, slices.shape[0], batch):
-                x = ((slices[i:i + batch].float() - 0.5) / 0.5).unsqueeze(1)
-                out[i:i + batch] = argmax_counts(model(x))[0]
-    finally:
-        model.train(was_training)
-    return out
+    _check_tta(tta, tuple(slices.shape[1:]))
+    return _predict(model, slices, batch, None if tta is None else tuple(map(int, tta.views)), _check_out_size(out_size), labels=True)
 
 
 @torch.no_grad()
@@ -579,20 +564,13 @@ def predict_probs(model, slices: torch.Tensor, batch: int = 16, tta: Optional[TT
     """The class probabilities of `predict_slices`' input averaged over the views of `tta` (None: the single view 0): fp32 [N,C,H,W], the
     accumulator of tc_tta_accumulate divided by the number of views.  `out_size` = (X, Y) other than (H, W): fp32 [N,C,X,Y], the accumulator
     resampled bilinearly (the `scores` output of tc_resample_scores) and then divided."""
-    _check_tta(tta)
+    _check_tta(tta, tuple(slices.shape[1:]))
     out_size = _check_out_size(out_size)
-    if out_size == tuple(slices.shape[1:]):
-        out_size = None
-    tta = tta if tta is not None else TTA((0,))
     if slices.shape[0] == 0:
         raise ValueError("predict_probs needs at least one slice")
-    was_training = model.training
-    model.eval()
-    try:
-        out = _tta_batches(model, slices, batch, tta, None, out_size)
-    finally:
-        model.train(was_training)
-    return out.div_(len(tta.views)) if len(tta.views) > 1 else out
+    views = (0,) if tta is None else tuple(map(int, tta.views))
+    out = _predict(model, slices, batch, views, out_size, labels=False)
+    return out.div_(len(views)) if len(views) > 1 else out
 
 
 @torch.no_grad()
@@ -626,6 +604,50 @@ def zoom_labels(pred: torch.Tensor, size: Tuple[int, int]) -> torch.Tensor:
     return y.to(torch.uint8)
 
 
+def _predict_volume_host(model, image: np.ndarray, dev, classes, patch_size, batch, postprocess, tta) -> np.ndarray:
+    """Prediction at `image`'s resolution, as the reference makes it: scipy's zooms per slice, `postprocess` on the host.  uint8 NumPy [D,X,Y]."""
+    from scipy.ndimage import zoom
+    D, X, Y = image.shape
+    resize = (X, Y) != tuple(patch_size)
+    sl = np.stack([zoom(image[d], (patch_size[0] / X, patch_size[1] / Y), order=3) if resize else image[d] for d in range(D)])
+    pred = predict_slices(model, torch.from_numpy(sl.astype(np.float32)).to(dev), batch, tta).cpu().numpy()
+    if resize:
+        pred = np.stack([zoom(pred[d], (X / patch_size[0], Y / patch_size[1]), order=0) for d in range(D)])
+    return pred if postprocess is None else postprocess_host(pred, classes, postprocess)
+
+
+def _predict_volume_device(model, image: np.ndarray, dev, classes, patch_size, batch, postprocess, tta, resample) -> torch.Tensor:
+    """The same on the device: one upload, both zooms (resample="scores": the resampled class scores), `postprocess`.  uint8 CUDA tensor [D,X,Y]."""
+    D, X, Y = image.shape
+    resize = (X, Y) != tuple(patch_size)
+    vol = torch.from_numpy(np.ascontiguousarray(image, np.float32)).to(dev)
+    sl = zoom_volume_to_network(vol, tuple(patch_size)) if resize else vol
+    if resize and resample == "scores":
+        pred = predict_slices(model, sl, batch, tta, out_size=(X, Y))
+    else:
+        pred = predict_slices(model, sl, batch, tta)
+        pred = zoom_labels(pred, (X, Y)) if resize else pred
+    return pred if postprocess is None else postprocess_device(pred, classes, postprocess, out=pred)
+
+
+def _dice_counts_host(pred: np.ndarray, label: np.ndarray, classes: int) -> np.ndarray:
+    """float64 [classes,3]: (|P==k & G==k|, |P==k|, |G==k|), what `surfaces_counts` counts on the device."""
+    return np.array([(np.logical_and(pred == k, label == k).sum(), (pred == k).sum(), (label == k).sum()) for k in range(classes)], dtype=np.float64)
+
+
+def _score_host(pred: np.ndarray, label: np.ndarray, classes: int, with_hd95: bool, voxelspacing):
+    if with_hd95:
+        return [calculate_metric_percase(pred == k, label == k, voxelspacing) for k in range(1, classes)]
+    return dice_from_counts(_dice_counts_host(pred, label, classes))
+
+
+def _score_device(pred: torch.Tensor, label: np.ndarray, classes: int, with_hd95: bool, voxelspacing):
+    label_t = torch.from_numpy(np.ascontiguousarray(label).astype(np.uint8)).to(pred.device)
+    if with_hd95:
+        return metrics_device(pred, label_t, classes, voxelspacing)
+    return dice_from_counts(surfaces_counts(pred, label_t, classes)[2].cpu().numpy())
+
+
 @torch.no_grad()
 def evaluate_volume(model, image: np.ndarray, label: np.ndarray, classes: int = 9, patch_size=(224, 224),
                     batch: int = 16, with_hd95: bool = False, host_zoom: bool = False, device_metrics: bool = False, voxelspacing=None,
@@ -644,48 +666,17 @@ def evaluate_volume(model, image: np.ndarray, label: np.ndarray, classes: int = 
     `F.interpolate(outputs, ..., mode='bilinear')` (utils.py:81) -- fused in tc_resample_scores, so that only the uint8 labels exist at
     `label`'s size; `postprocess` and both metric paths follow as before.  Without a resize both values run the same calls; "scores" with
     `host_zoom=True` is a ValueError."""
-    _check_resample(resample, host_zoom)
-    if postprocess is not None and not isinstance(postprocess, PostProcess):
-        raise ValueError(f"postprocess must be None or a PostProcess, got {postprocess!r}")
-    _check_tta(tta, tuple(patch_size))
+    _check_options(postprocess, tta, resample, host_zoom, tuple(patch_size))
     dev = next(model.parameters()).device
     if device_metrics and dev.type != "cuda":
         raise RuntimeError(NO_CPU)
-    D, X, Y = image.shape
-    resize = (X, Y) != tuple(patch_size)
     if host_zoom:
-        from scipy.ndimage import zoom
-        sl = np.stack([zoom(image[d], (patch_size[0] / X, patch_size[1] / Y), order=3) if resize else image[d] for d in range(D)])
-        pred = predict_slices(model, torch.from_numpy(sl.astype(np.float32)).to(dev), batch, tta).cpu().numpy()
-        if resize:
-            pred = np.stack([zoom(pred[d], (X / patch_size[0], Y / patch_size[1]), order=0) for d in range(D)])
-        if postprocess is not None:
-            pred = postprocess_host(pred, classes, postprocess)
+        on_host = _predict_volume_host(model, image, dev, classes, patch_size, batch, postprocess, tta)
+        pred = torch.from_numpy(on_host).to(dev) if device_metrics else on_host
     else:
-        vol = torch.from_numpy(np.ascontiguousarray(image, np.float32)).to(dev)
-        sl = zoom_volume_to_network(vol, tuple(patch_size)) if resize else vol
-        if resize and resample == "scores":
-            pred = predict_slices(model, sl, batch, tta, out_size=(X, Y))
-        else:
-            pred_d = predict_slices(model, sl, batch, tta)
-            pred = zoom_labels(pred_d, (X, Y)) if resize else pred_d
-        if postprocess is not None:
-            pred = postprocess_device(pred, classes, postprocess, out=pred)
-        if not device_metrics:
-            pred = pred.cpu().numpy()
-    if device_metrics:
-        pred_t = torch.from_numpy(pred).to(dev) if host_zoom else pred
-        label_t = torch.from_numpy(np.ascontiguousarray(label).astype(np.uint8)).to(dev)
-        if with_hd95:
-            return metrics_device(pred_t, label_t, classes, voxelspacing)
-        return dice_from_counts(surfaces_counts(pred_t, label_t, classes)[2].cpu().numpy())
-    if with_hd95:
-        return [calculate_metric_percase(pred == k, label == k, voxelspacing) for k in range(1, classes)]
-    counts = np.zeros((classes, 3), dtype=np.float64)
-    for k in range(classes):
-        p, g = pred == k, label == k
-        counts[k] = (np.logical_and(p, g).sum(), p.sum(), g.sum())
-    return dice_from_counts(counts)
+        on_device = _predict_volume_device(model, image, dev, classes, patch_size, batch, postprocess, tta, resample)
+        pred = on_device if device_metrics else on_device.cpu().numpy()
+    return (_score_device if device_metrics else _score_host)(pred, label, classes, with_hd95, voxelspacing)
 
 
 def inference(model, volumes, classes: int = 9, img_size: int = 224, batch: int = 16, log=None,
@@ -693,8 +684,7 @@ def inference(model, volumes, classes: int = 9, img_size: int = 224, batch: int 
               tta: Optional[TTA] = None, *, resample: str = "labels") -> Tuple[float, float]:
     """trainer.py:25-47: mean Dice and mean HD95 over `volumes` = iterable of (image [D,H,W] in [0,1], label [D,H,W], case name).
     `device_metrics`, `voxelspacing` (one spacing for every volume), `postprocess`, `tta`, `resample`: as in `evaluate_volume`."""
-    _check_tta(tta)
-    _check_resample(resample)
+    _check_options(postprocess, tta, resample)
     total, n = 0.0, 0
     for i, (image, label, name) in enumerate(volumes):
         m = np.array(evaluate_volume(model, np.asarray(image), np.asarray(label), classes, (img_size, img_size), batch, with_hd95=True,
@@ -713,3 +703,4 @@ def inference(model, volumes, classes: int = 9, img_size: int = 224, batch: int 
     if log:
         log('Testing performance in best val model: mean_dice : %f mean_hd95 : %f' % (performance, mean_hd95))
     return performance, mean_hd95
+

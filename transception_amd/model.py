@@ -22,8 +22,8 @@ from typing import Dict, List, Optional, Tuple
 import torch
 import torch.nn as nn
 
-from ._lib import ACT_COORD, ACT_GELU, ACT_HSWISH, ACT_NONE, ACT_RELU, ACT_SIGMOID, TC_BF16, TC_F16, TC_F32, lib
-from .engine import Graph, P, Var
+from ._lib import ACT_COORD, ACT_GELU, ACT_HSWISH, ACT_NONE, ACT_RELU, ACT_SIGMOID, TC_F32, lib
+from .engine import TC_DTYPE, Graph, P, Var
 
 DIMS = (64, 128, 320, 512)
 LAYERS = (3, 8, 3)
@@ -477,7 +477,7 @@ class MSTransception(nn.Module):
         return self
 
     def _tc_dtype(self) -> int:
-        return {torch.float32: TC_F32, torch.bfloat16: TC_BF16, torch.float16: TC_F16}[self.compute_dtype]
+        return TC_DTYPE[self.compute_dtype]
 
     def _ensure_flat(self, device):
         uniq = list(self.parameters())

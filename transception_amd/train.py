@@ -20,11 +20,12 @@ from typing import Optional, Union
 import torch
 import torch.distributed as dist
 
-from ._lib import TC_BF16, TC_F16, TC_F32, TC_IGNORE_NONE, lib
+from ._lib import TC_IGNORE_NONE, lib
+from .engine import TC_DTYPE
 
 
 def _dt(t: torch.Tensor) -> int:
-    return {torch.float32: TC_F32, torch.bfloat16: TC_BF16, torch.float16: TC_F16}[t.dtype]
+    return TC_DTYPE[t.dtype]
 
 
 COMM_AT_WORLD_1 = os.environ.get("TC_COMM_WORLD1", "0") == "1"

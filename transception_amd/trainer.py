@@ -27,7 +27,7 @@ import torch
 import torch.distributed as dist
 
 from .data import DeviceLoader, SynapseSlices
-from .evaluate import RESAMPLE_MODES, TTA, PostProcess, inference
+from .evaluate import RESAMPLE_MODES, TTA, VALID_OPTION, PostProcess, inference
 from .train import (DynamicLossScale, FusedAdamW, FusedSGD, GraphedStep, SegLoss, WeightEMA, check_class_weights, check_ema_decay,
                     check_ignore_index, cosine_lr, train_step)
 
@@ -91,11 +91,11 @@ class TrainConfig:
             raise ValueError(f'no_decay must be None or "norm_bias", got {self.no_decay!r}')
         if self.no_decay is not None and self.optimizer == "sgd":
             raise ValueError("no_decay needs optimizer=\"adamw\" or \"adam\": the SGD kernel takes one decay for all segments")
-        if self.postprocess is not None and not isinstance(self.postprocess, PostProcess):
+        if not VALID_OPTION["postprocess"](self.postprocess):
             raise ValueError(f"postprocess must be None or an evaluate.PostProcess, got {self.postprocess!r}")
-        if self.tta is not None and not isinstance(self.tta, TTA):
+        if not VALID_OPTION["tta"](self.tta):
             raise ValueError(f"tta must be None or an evaluate.TTA, got {self.tta!r}")
-        if not isinstance(self.resample, str) or self.resample not in RESAMPLE_MODES:
+        if not VALID_OPTION["resample"](self.resample):
             raise ValueError(f"resample must be one of {RESAMPLE_MODES}, got {self.resample!r}")
         make_loss_scale(self.loss_scale)
         check_class_weights("class_weights", self.class_weights, self.num_classes, need_positive=True)
