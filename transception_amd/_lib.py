@@ -23,7 +23,7 @@ ABI = _header.load()
 SIGNATURES = {name: f.argtypes for name, f in ABI.functions.items()}     # every pointer is a c_void_p: byref(), arrays, addresses, None
 K, S = ABI.constants, ABI.structs
 SIDE = {s.attr: _header.load(s.path) for s in _header.SIDE_HEADERS}       # the headers of their own: one line each in _header.SIDE_HEADERS
-POST, EMA, TTA, RESAMPLE = SIDE["POST"], SIDE["EMA"], SIDE["TTA"], SIDE["RESAMPLE"]
+POST, EMA, TTA, RESAMPLE, BRIDGE = SIDE["POST"], SIDE["EMA"], SIDE["TTA"], SIDE["RESAMPLE"], SIDE["BRIDGE"]
 
 ABI_VERSION = K["TC_ABI_VERSION"]
 TC_F32, TC_BF16, TC_F16 = K["TC_F32"], K["TC_BF16"], K["TC_F16"]
@@ -36,13 +36,15 @@ TC_AUG_SKIP, TC_AUG_FROM_RAW = K["TC_AUG_SKIP"], K["TC_AUG_FROM_RAW"]
 ATTN_DKV_SPLITS = K["TC_ATTN_DKV_SPLITS"]
 TC_METRIC_NO_SOURCE, TC_METRIC_SELECT_WORK_BYTES = K["TC_METRIC_NO_SOURCE"], K["TC_METRIC_SELECT_WORK_BYTES"]
 TC_IGNORE_NONE = K["TC_IGNORE_NONE"]
-POST_ABI_VERSION, EMA_ABI_VERSION, TTA_ABI_VERSION, RESAMPLE_ABI_VERSION = (SIDE[s.attr].constants[s.version] for s in _header.SIDE_HEADERS)
+POST_ABI_VERSION, EMA_ABI_VERSION, TTA_ABI_VERSION, RESAMPLE_ABI_VERSION, BRIDGE_ABI_VERSION = (SIDE[s.attr].constants[s.version] for s in _header.SIDE_HEADERS)
 TC_CC_LARGEST, TC_CC_MIN_VOXELS = POST.constants["TC_CC_LARGEST"], POST.constants["TC_CC_MIN_VOXELS"]
 TC_RESAMPLE_MAX_EXTENT = RESAMPLE.constants["TC_RESAMPLE_MAX_EXTENT"]
 TC_TTA_FLIP_H, TC_TTA_FLIP_W, TC_TTA_TRANSPOSE = TTA.constants["TC_TTA_FLIP_H"], TTA.constants["TC_TTA_FLIP_W"], TTA.constants["TC_TTA_TRANSPOSE"]
 
 TcGemm, TcLnFold, TcDwFold, TcDwSeg, TcFfnSeg = S["TcGemm"], S["TcLnFold"], S["TcDwFold"], S["TcDwSeg"], S["TcFfnSeg"]
 TcFfnFused, TcFfnBwd, TcEffAtt, TcEwSeg, TcSliceAug = S["TcFfnFused"], S["TcFfnBwd"], S["TcEffAtt"], S["TcEwSeg"], S["TcSliceAug"]
+TcSrSrc, TcLnSeg = BRIDGE.structs["TcSrSrc"], BRIDGE.structs["TcLnSeg"]
+SR_LN_MAX, LN_MULTI_MAX = BRIDGE.constants["TC_SR_LN_MAX"], BRIDGE.constants["TC_LN_MULTI_MAX"]
 
 
 class TcError(RuntimeError):

@@ -417,7 +417,8 @@ __global__ void sr_deinterleave_kernel(const T* in, T* out, long long sbo, int l
 
 // Up to TC_EW_MULTI_MAX independent layout moves (patchify / de-interleave / strided copy) in ONE launch: blockIdx.y picks the segment.
 // Scale_reduce (MSTr.py:2225-2249) is three patchifies, three convolutions as GEMMs, three de-interleaves and a copy on maps of a few
-// hundred KB: each of them alone sits at the ~4.5 us floor of a launch.
+// hundred KB: each of them alone sits at the ~4.5 us floor of a launch.  (16-bit storage: the de-interleaves and the copy now happen in the
+// row loader of the LayerNorm behind them, norm.hip tc_sr_ln_*; this launch remains for the patchifies and the fp32 / grouped paths.)
 struct EwMultiDev { TcEwSeg s[TC_EW_MULTI_MAX]; };
 template <typename T>
 __global__ void ew_multi_kernel(EwMultiDev q) {

@@ -2,6 +2,7 @@
 // HBM-bound kernels: one wavefront per LayerNorm row with the row held in registers (two-pass statistics via
 // wave shuffles); BatchNorm statistics as deterministic per-chunk partials that the apply kernel folds itself.
 #include "tc_common.h"
+#include "../../include/transception_bridge.h"
 #include <cstdlib>
 
 namespace {
@@ -37,6 +38,90 @@ __device__ __forceinline__ long long ln_row_off(int row, const LnMap& m, int ld,
 
 // RPT consecutive rows per lane group and iteration: their loads are all issued before the first reduction (narrow rows are
 // 128-256 bytes: one row per group per iteration left a single 8-byte load per lane in flight and ran at ~2 TB/s).
+// A value the compiler may not look through: a product that passes here is rounded as a product, whatever add consumes it (-ffp-contract=fast
+// fuses in the back end, by heuristics that depend on the surrounding kernel).  No instruction.
+__device__ __forceinline__ float ln_pin(float v) { asm volatile("" : "+v"(v)); return v; }
+
+// Where the rows of a LayerNorm come from (and, in the backward, where their gradients go): LnRows is a matrix with a row stride, optionally
+// seen through a pixel shuffle; SrRows (below) gathers the rows of the Scale_reduce tail from their sources.  The kernel bodies are written
+// once over either, so the arithmetic per row is the same instructions whichever way the row arrives.
+template <typename T> struct LnRows {
+    const T* x; int ld, C; LnMap map;
+    __device__ __forceinline__ float4 load4(int row, int q) const { return ld4<T>(x + ln_row_off(row, map, ld, C) + q * 4); }
+};
+
+// (bx, nbx): the workgroup's index and count along the rows -- blockIdx.x / gridDim.x, or a segment's own count inside a multi-segment launch
+template <typename T, int GS, int NV, int RPT, typename Src>
+__device__ __forceinline__ void ln_fwd_body(const Src& src, const T* __restrict__ gamma, const T* __restrict__ beta, T* __restrict__ y, int ldy,
+                                            float* __restrict__ mean, float* __restrict__ rstd, const int sst, int rows, int C, float eps, int act,
+                                            const int bx, const int nbx) {
+    // Which products fuse with an add is written out below (fmaf, or ln_pin where a product must stay a product): left to the compiler it
+    // depends on the kernel the body is inlined into -- it differed between the pieces of one row -- and the launches that share this body
+    // must agree to the bit.
+    static_assert(!std::is_same<T, float>::value, "16-bit storage: fp32 keeps ln_fwd_kernel");
+    constexpr int RPB = 256 / GS;
+    const int gl = threadIdx.x % GS, gi = threadIdx.x / GS;
+    const int nv = C >> 2;
+    const float invC = 1.0f / (float)C;
+    float4 g[NV], b[NV];
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        const int q = gl + i * GS;
+        if (q < nv) { g[i] = ld4<T>(gamma + q * 4); b[i] = ld4<T>(beta + q * 4); }
+    }
+    for (int row0 = (bx * RPB + gi) * RPT; row0 < rows; row0 += nbx * RPB * RPT) {
+        float4 v[RPT][NV];
+        float mu[RPT], rs[RPT];
+#pragma unroll
+        for (int r = 0; r < RPT; ++r) {
+            const int row = min(row0 + r, rows - 1);              // rows past the end re-read the last row (no divergent loads)
+#pragma unroll
+            for (int i = 0; i < NV; ++i) {
+                const int q = gl + i * GS;
+                v[r][i] = q < nv ? src.load4(row, q) : make_float4(0.f, 0.f, 0.f, 0.f);
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < RPT; ++r) {
+            float s = 0.f;
+#pragma unroll
+            for (int i = 0; i < NV; ++i) s += v[r][i].x + v[r][i].y + v[r][i].z + v[r][i].w;
+            mu[r] = ln_pin(tc_group_sum<GS>(s) * invC);
+            float s2 = 0.f;
+#pragma unroll
+            for (int i = 0; i < NV; ++i) {
+                const int q = gl + i * GS;
+                if (q < nv) {
+                    const float a = v[r][i].x - mu[r], bb = v[r][i].y - mu[r], c = v[r][i].z - mu[r], d = v[r][i].w - mu[r];
+                    s2 += fmaf(d, d, fmaf(c, c, fmaf(bb, bb, a * a)));
+                }
+            }
+            rs[r] = rsqrtf(fmaf(tc_group_sum<GS>(s2), invC, eps));
+        }
+#pragma unroll
+        for (int r = 0; r < RPT; ++r) {
+            const int row = row0 + r;
+            if (row >= rows) break;
+            if (gl == 0) { mean[(long long)row * sst] = mu[r]; rstd[(long long)row * sst] = rs[r]; }
+            T* yr = y + (long long)row * ldy;
+#pragma unroll
+            for (int i = 0; i < NV; ++i) {
+                const int q = gl + i * GS;
+                if (q < nv) {
+                    float4 o;
+                    o.x = fmaf((v[r][i].x - mu[r]) * rs[r], g[i].x, b[i].x); o.y = fmaf((v[r][i].y - mu[r]) * rs[r], g[i].y, b[i].y);
+                    o.z = fmaf((v[r][i].z - mu[r]) * rs[r], g[i].z, b[i].z); o.w = fmaf((v[r][i].w - mu[r]) * rs[r], g[i].w, b[i].w);
+                    if (act == TC_ACT_GELU) { o.x = gelu_fT<T>(o.x); o.y = gelu_fT<T>(o.y); o.z = gelu_fT<T>(o.z); o.w = gelu_fT<T>(o.w); }
+                    st4<T>(yr + q * 4, o);
+                }
+            }
+        }
+    }
+}
+
+// fp32 storage (the parity path) runs the kernel as it has always been written: its fixtures sit within an ulp of their bounds, and hipcc's choice
+// of FMAs moves when the same expressions are compiled inside another function.  16-bit storage runs ln_fwd_kernel16 = ln_fwd_body, whose
+// fusions are written out, so that every launch sharing the body (tc_layernorm_fwd, tc_layernorm_fwd_multi, tc_sr_ln_fwd) agrees to the bit.
 template <typename T, int GS, int NV, int RPT>
 __global__ __launch_bounds__(256) void ln_fwd_kernel(const T* __restrict__ x, int ldx, const T* __restrict__ gamma,
                                                      const T* __restrict__ beta, T* __restrict__ y, int ldy,
@@ -106,6 +191,19 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const T* __restrict__ x, in
             }
         }
     }
+}
+
+template <typename T, int GS, int NV, int RPT>
+__global__ __launch_bounds__(256) void ln_fwd_kernel16(const T* __restrict__ x, int ldx, const T* __restrict__ gamma,
+                                                     const T* __restrict__ beta, T* __restrict__ y, int ldy,
+                                                     float* __restrict__ mean, float* __restrict__ rstd, int rows,
+                                                     int C, float eps, int act, long long pstride, LnMap map) {
+    const int sst = (rstd == mean + 1) ? 2 : 1;                  // interleaved statistics: [rows][2] (mean, rstd) pairs
+    {   // group = blockIdx.y: `rows` rows each, parameters pstride apart
+        const long long g = blockIdx.y;
+        x += g * rows * ldx; y += g * rows * ldy; mean += g * rows * sst; rstd += g * rows * sst; gamma += g * pstride; beta += g * pstride;
+    }
+    ln_fwd_body<T, GS, NV, RPT>(LnRows<T>{x, ldx, C, map}, gamma, beta, y, ldy, mean, rstd, sst, rows, C, eps, act, blockIdx.x, gridDim.x);
 }
 
 // The parameter-gradient tail of the LayerNorm backward kernels: the workgroup's per-lane-group column sums (red[RPB][2][C], filled by the
@@ -281,23 +379,22 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const T* __restrict__ dy, i
 // stage at 1.4 TB/s (56 us a launch).  The raw pieces of all RPT rows are requested before the first one is unpacked.  Same arithmetic in the
 // same order per row as ln_bwd_kernel (statistics over the group by the same shuffles), same parameter-gradient tail.
 typedef unsigned lnu4 __attribute__((ext_vector_type(4)));
-template <typename T, int GS, int RPT>
-__global__ __launch_bounds__(256) void ln_bwd_v8_kernel(const T* __restrict__ dy, int lddy, const T* __restrict__ x, int ldx,
-                                                        const T* __restrict__ gamma, const T* __restrict__ beta,
-                                                        const float* __restrict__ mean, const float* __restrict__ rstd,
-                                                        T* __restrict__ dx, int lddx, const T* __restrict__ dres, int ldres,
-                                                        float* __restrict__ dgamma, float* __restrict__ dbeta, int rows,
-                                                        long long pstride, float* __restrict__ partial, int* __restrict__ cnt, LnMap map, int defer) {
+// (the 16-byte pieces of LnRows: x rows in, dx rows out)
+template <typename T> struct LnRows8 {
+    const T* x; int ldx; T* dx; int lddx; int C; LnMap map;
+    __device__ __forceinline__ lnu4 load8(int row, int gl) const { return *reinterpret_cast<const lnu4*>(x + ln_row_off(row, map, ldx, C) + gl * 8); }
+    __device__ __forceinline__ void store8(int row, int gl, const lnu4 w) const { *reinterpret_cast<lnu4*>(dx + ln_row_off(row, map, lddx, C) + gl * 8) = w; }
+};
+template <typename T, int GS, int RPT, typename Rows>
+__device__ __forceinline__ void ln_bwd_v8_body(const Rows& xr, const T* __restrict__ dy, int lddy, const T* __restrict__ gamma,
+                                               const float* __restrict__ mean, const float* __restrict__ rstd,
+                                               const T* __restrict__ dres, int ldres, LnMap map,
+                                               float* __restrict__ dgamma, float* __restrict__ dbeta, int rows,
+                                               float* __restrict__ partial, int* __restrict__ cnt, int defer) {
+    // (fmaf / ln_pin as in ln_fwd_body: the same bits from every kernel that shares this body)
     constexpr int RPB = 256 / GS, C = GS * 8;
     extern __shared__ float red[];           // [RPB][2][C]
     const int gl = threadIdx.x % GS, gi = threadIdx.x / GS;
-    {
-        const long long g = blockIdx.y;
-        dy += g * rows * lddy; x += g * rows * ldx; dx += g * rows * lddx; mean += g * rows; rstd += g * rows;
-        if (dres) dres += g * rows * ldres;
-        gamma += g * pstride; beta += g * pstride;
-        if (dgamma) { dgamma += g * pstride; dbeta += g * pstride; }
-    }
     float g[8], ag[8], ab[8];
     tc_unpack16<T>(*reinterpret_cast<const lnu4*>(gamma + gl * 8), g);
 #pragma unroll
@@ -310,7 +407,7 @@ __global__ __launch_bounds__(256) void ln_bwd_v8_kernel(const T* __restrict__ dy
 #pragma unroll
         for (int r = 0; r < RPT; ++r) {
             const int row = min(row0 + r, rows - 1);
-            rx[r] = *reinterpret_cast<const lnu4*>(x + ln_row_off(row, map, ldx, C) + gl * 8);
+            rx[r] = xr.load8(row, gl);
             rd[r] = *reinterpret_cast<const lnu4*>(dy + (long long)row * lddy + gl * 8);
             if (has_res) rr[r] = *reinterpret_cast<const lnu4*>(dres + ln_row_off(row, map, ldres, C) + gl * 8);
             mu[r] = mean[row]; rs[r] = rstd[row];
@@ -325,26 +422,30 @@ __global__ __launch_bounds__(256) void ln_bwd_v8_kernel(const T* __restrict__ dy
             for (int j = 0; j < 8; ++j) xv[j] = (xv[j] - mu[r]) * rs[r];
             if (dgamma && live) {
 #pragma unroll
-                for (int j = 0; j < 8; ++j) { ag[j] += d[j] * xv[j]; ab[j] += d[j]; }
+                for (int j = 0; j < 8; ++j) { ag[j] = fmaf(d[j], xv[j], ag[j]); ab[j] += d[j]; }
             }
 #pragma unroll
-            for (int j = 0; j < 8; ++j) d[j] *= g[j];
+            for (int j = 0; j < 8; ++j) d[j] = ln_pin(d[j] * g[j]);
             // (the 4-wide kernel's order: a lane adds its four values of a piece, pieces in turn)
             s1 = ((d[0] + d[1]) + d[2]) + d[3]; s1 += ((d[4] + d[5]) + d[6]) + d[7];
-            s2 = ((d[0] * xv[0] + d[1] * xv[1]) + d[2] * xv[2]) + d[3] * xv[3]; s2 += ((d[4] * xv[4] + d[5] * xv[5]) + d[6] * xv[6]) + d[7] * xv[7];
-            s1 = tc_group_sum<GS>(s1) * invC; s2 = tc_group_sum<GS>(s2) * invC;
+            s2 = fmaf(d[3], xv[3], fmaf(d[2], xv[2], fmaf(d[1], xv[1], d[0] * xv[0])));
+            s2 += fmaf(d[7], xv[7], fmaf(d[6], xv[6], fmaf(d[5], xv[5], d[4] * xv[4])));
+            s1 = ln_pin(tc_group_sum<GS>(s1) * invC); s2 = ln_pin(tc_group_sum<GS>(s2) * invC);
             if (!live) continue;
             float o[8];
 #pragma unroll
-            for (int j = 0; j < 8; ++j) o[j] = rs[r] * (d[j] - s1 - xv[j] * s2);
-            if (has_res) {
+            for (int j = 0; j < 8; ++j) o[j] = fmaf(-xv[j], s2, d[j] - s1);
+            if (has_res) {                                   // the residual rows join in the same rounding as the scale by rstd
                 float q[8];
                 tc_unpack16<T>(rr[r], q);
 #pragma unroll
-                for (int j = 0; j < 8; ++j) o[j] += q[j];
+                for (int j = 0; j < 8; ++j) o[j] = fmaf(rs[r], o[j], q[j]);
+            } else {
+#pragma unroll
+                for (int j = 0; j < 8; ++j) o[j] *= rs[r];
             }
             const lnu4 w = tc_pack16<T, lnu4>(o);
-            *reinterpret_cast<lnu4*>(dx + ln_row_off(row0 + r, map, lddx, C) + gl * 8) = w;
+            xr.store8(row0 + r, gl, w);
         }
     }
     if (!dgamma) return;
@@ -354,6 +455,23 @@ __global__ __launch_bounds__(256) void ln_bwd_v8_kernel(const T* __restrict__ dy
         red[(gi * 2 + 1) * C + gl * 8 + j] = ab[j];
     }
     ln_bwd_param_tail<RPB>(red, C, dgamma, dbeta, partial, cnt, defer);
+}
+template <typename T, int GS, int RPT>
+__global__ __launch_bounds__(256) void ln_bwd_v8_kernel(const T* __restrict__ dy, int lddy, const T* __restrict__ x, int ldx,
+                                                        const T* __restrict__ gamma, const T* __restrict__ beta,
+                                                        const float* __restrict__ mean, const float* __restrict__ rstd,
+                                                        T* __restrict__ dx, int lddx, const T* __restrict__ dres, int ldres,
+                                                        float* __restrict__ dgamma, float* __restrict__ dbeta, int rows,
+                                                        long long pstride, float* __restrict__ partial, int* __restrict__ cnt, LnMap map, int defer) {
+    {
+        const long long g = blockIdx.y;
+        dy += g * rows * lddy; x += g * rows * ldx; dx += g * rows * lddx; mean += g * rows; rstd += g * rows;
+        if (dres) dres += g * rows * ldres;
+        gamma += g * pstride; beta += g * pstride;
+        if (dgamma) { dgamma += g * pstride; dbeta += g * pstride; }
+    }
+    ln_bwd_v8_body<T, GS, RPT>(LnRows8<T>{x, ldx, dx, lddx, GS * 8, map}, dy, lddy, gamma, mean, rstd, dres, ldres, map, dgamma, dbeta, rows, partial,
+                               cnt, defer);
 }
 
 // The forward on the same rows (16-bit, C = 64 / 128 / 256 / 512, no activation): eight channels per lane, RPT rows per lane group in flight
@@ -725,6 +843,107 @@ __global__ __launch_bounds__(256) void ln_fold_kernel(const LnFoldDev q) {
     }
 }
 
+// ---------------------------------------------------------------------------------------------- Scale_reduce tail (tc_sr_ln_*)
+// The rows of the LayerNorm at the end of Scale_reduce (MSTr.py:2236-2249) are gathered by the row loader from the three convolution outputs
+// (channel de-interleave) and the stage-4 tokens (row block), and their gradients scattered back the same way: the [B * Nk, 64] matrix and its
+// gradient are never stored, and the de-interleave / copy launch in front of the LayerNorm (and behind its backward) is gone.  450 k elements:
+// the strided 2-byte accesses do not matter, the launch did (3-4 us at its head, 10-13 us in all).
+struct SrSrcDev { const void* src; void* dsrc; long long sb; int mult, P, ld, off, end, acc; };
+struct SrDev { SrSrcDev s[TC_SR_LN_MAX]; int n, Nk; };
+template <typename T> struct SrRows {
+    SrDev d;
+    // the source of a row, its image and its row inside the source
+    __device__ __forceinline__ SrSrcDev locate(int row, int& b, int& r) const {
+        b = row / d.Nk;
+        const int lr = row - b * d.Nk;
+        SrSrcDev t = d.s[0];                                                  // (sorted by off, tiling [0, Nk); selected, not indexed: the
+#pragma unroll                                                                //  argument block stays in scalar registers)
+        for (int i = 1; i < TC_SR_LN_MAX; ++i) if (i < d.n && lr >= d.s[i].off) t = d.s[i];
+        r = lr - t.off;
+        return t;
+    }
+    // element offset of channel c0 of a de-interleaved row (channel c is c * mult further on)
+    static __device__ __forceinline__ long long deint_off(const SrSrcDev& t, int b, int r, int c0) {
+        const int g = r / t.P, pos = r - g * t.P;
+        return ((long long)b * t.P + pos) * (64 * t.mult) + c0 * t.mult + g;
+    }
+    __device__ __forceinline__ float4 load4(int row, int q) const {
+        int b, r;
+        const SrSrcDev t = locate(row, b, r);
+        if (t.mult == 0) return ld4<T>((const T*)t.src + b * t.sb + (long long)r * t.ld + q * 4);
+        const T* p = (const T*)t.src + deint_off(t, b, r, q * 4);
+        return make_float4(ldf<T>(p), ldf<T>(p + t.mult), ldf<T>(p + 2 * t.mult), ldf<T>(p + 3 * t.mult));
+    }
+    __device__ __forceinline__ lnu4 load8(int row, int gl) const {
+        int b, r;
+        const SrSrcDev t = locate(row, b, r);
+        if (t.mult == 0) return *reinterpret_cast<const lnu4*>((const T*)t.src + b * t.sb + (long long)r * t.ld + gl * 8);
+        const unsigned short* p = reinterpret_cast<const unsigned short*>(t.src) + deint_off(t, b, r, gl * 8);
+        unsigned h[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) h[j] = p[j * t.mult];
+        lnu4 w;
+        w.x = h[0] | (h[1] << 16); w.y = h[2] | (h[3] << 16); w.z = h[4] | (h[5] << 16); w.w = h[6] | (h[7] << 16);
+        return w;
+    }
+    __device__ __forceinline__ void store8(int row, int gl, lnu4 w) const {
+        int b, r;
+        const SrSrcDev t = locate(row, b, r);
+        if (t.mult == 0) {
+            T* p = (T*)t.dsrc + b * t.sb + (long long)r * t.ld + gl * 8;
+            if (t.acc) {                                     // rounded dx + what is there, rounded again: a copy launch with its accumulate flag
+                float a[8], o[8];
+                tc_unpack16<T>(w, a); tc_unpack16<T>(*reinterpret_cast<const lnu4*>(p), o);
+#pragma unroll
+                for (int j = 0; j < 8; ++j) a[j] += o[j];
+                w = tc_pack16<T, lnu4>(a);
+            }
+            *reinterpret_cast<lnu4*>(p) = w;
+            return;
+        }
+        unsigned short* p = reinterpret_cast<unsigned short*>(t.dsrc) + deint_off(t, b, r, gl * 8);
+        const unsigned ws[4] = {w.x, w.y, w.z, w.w};
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            p[(2 * e) * t.mult] = (unsigned short)(ws[e] & 0xffffu);
+            p[(2 * e + 1) * t.mult] = (unsigned short)(ws[e] >> 16);
+        }
+    }
+};
+// forward: tc_layernorm_fwd's kernel for C = 64 (16 lanes a row, 4 channels a lane) over the gathered rows
+template <typename T, int RPT>
+__global__ __launch_bounds__(256) void sr_ln_fwd_kernel(const SrRows<T> src, const T* __restrict__ gamma, const T* __restrict__ beta, T* __restrict__ y,
+                                                        int ldy, float* __restrict__ mean, float* __restrict__ rstd, int rows, float eps) {
+    ln_fwd_body<T, 16, 1, RPT>(src, gamma, beta, y, ldy, mean, rstd, 1, rows, 64, eps, TC_ACT_NONE, blockIdx.x, gridDim.x);
+}
+// backward: tc_layernorm_bwd_defer's kernel for 16-bit rows of 64 (8 lanes a row, 8 channels a lane), partials parked for tc_layernorm_fold
+template <typename T>
+__global__ __launch_bounds__(256) void sr_ln_bwd_kernel(const SrRows<T> src, const T* __restrict__ dy, int lddy, const T* __restrict__ gamma,
+                                                        const float* __restrict__ mean, const float* __restrict__ rstd, float* __restrict__ part,
+                                                        int rows) {
+    // (dgamma / dbeta of the body only say "with parameter gradients": deferred partials never touch them)
+    ln_bwd_v8_body<T, 8, 1>(src, dy, lddy, gamma, mean, rstd, (const T*)nullptr, 0, LnMap{0, 0, 0}, part, part, rows, part, (int*)nullptr, 1);
+}
+
+// ---------------------------------------------------------------------------------------------- several forwards, one launch
+// blockIdx.y picks the segment (as ew_multi_kernel does); each runs the body and the lane-group shape tc_layernorm_fwd picks for its width
+// below 4096 rows, over its own workgroup count -- the stand-alone LayerNorm + GELU of the two wide MixFFN sites of a bridge layer (3136 x 1280
+// and 784 x 2048) were two launches of 10 us behind one another.
+struct LnMultiDev { TcLnSeg s[TC_LN_MULTI_MAX]; int nb[TC_LN_MULTI_MAX]; };
+template <typename T>
+__global__ __launch_bounds__(256) void ln_fwd_multi_kernel(const LnMultiDev q) {
+    const TcLnSeg& t = q.s[blockIdx.y];
+    const int nbx = q.nb[blockIdx.y];
+    if ((int)blockIdx.x >= nbx) return;
+    float* mean = t.mean; float* rstd = t.rstd;
+    const int sst = (rstd == mean + 1) ? 2 : 1;
+    const LnRows<T> src{(const T*)t.x, t.ldx, t.C, LnMap{0, 0, 0}};
+#define TC_LNM(GS, NV) ln_fwd_body<T, GS, NV, 1>(src, (const T*)t.gamma, (const T*)t.beta, (T*)t.y, t.ldy, mean, rstd, sst, t.rows, t.C, t.eps, t.act, \
+                                                  (int)blockIdx.x, nbx)
+    TC_LN_DISPATCH(t.C >> 2, TC_LNM)
+#undef TC_LNM
+}
+
 // workgroups of the fused dx + parameter-gradient launch (one place: the launch and the size of a deferred partial buffer)
 inline int ln_bwd_nblk(int rows, int C, bool with_params, bool deferred) {
     const int quads = C >> 2;
@@ -737,6 +956,12 @@ inline int ln_bwd_nblk(int rows, int C, bool with_params, bool deferred) {
 }
 
 }  // namespace
+
+template <typename T, int GS, int NV, int RPT, typename... A>
+static void ln_fwd_launch(dim3 grid, hipStream_t s, A... a) {
+    if constexpr (std::is_same<T, float>::value) hipLaunchKernelGGL((ln_fwd_kernel<T, GS, NV, RPT>), grid, dim3(256), 0, s, a...);
+    else hipLaunchKernelGGL((ln_fwd_kernel16<T, GS, NV, RPT>), grid, dim3(256), 0, s, a...);
+}
 
 static int ln_fwd_impl(const void* x, int ldx, const void* gamma, const void* beta, void* y, int ldy,
                        float* mean, float* rstd, int rows, int C, float eps, int act, int groups, long long pstride, int dtype,
@@ -762,11 +987,11 @@ static int ln_fwd_impl(const void* x, int ldx, const void* gamma, const void* be
 #define TC_LNF(GS, NV) {                                                                                                                  \
         constexpr int RPT = NV == 1 ? 4 : (NV == 2 ? 2 : 1);       /* narrow rows: several rows in flight per lane group */                   \
         if (rows >= 4096)                                                                                                                     \
-            hipLaunchKernelGGL((ln_fwd_kernel<T, GS, NV, RPT>), dim3(tc_blocks(rows, (256 / GS) * RPT, 2048), groups), dim3(256), 0, s,       \
-                               (const T*)x, ldx, (const T*)gamma, (const T*)beta, (T*)y, ldy, mean, rstd, rows, C, eps, act, pstride, map);  \
+            ln_fwd_launch<T, GS, NV, RPT>(dim3(tc_blocks(rows, (256 / GS) * RPT, 2048), groups), s, (const T*)x, ldx, (const T*)gamma,        \
+                                          (const T*)beta, (T*)y, ldy, mean, rstd, rows, C, eps, act, pstride, map);                           \
         else                                                                                                                                  \
-            hipLaunchKernelGGL((ln_fwd_kernel<T, GS, NV, 1>), dim3(tc_blocks(rows, 256 / GS, 2048), groups), dim3(256), 0, s, (const T*)x,    \
-                               ldx, (const T*)gamma, (const T*)beta, (T*)y, ldy, mean, rstd, rows, C, eps, act, pstride, map); }
+            ln_fwd_launch<T, GS, NV, 1>(dim3(tc_blocks(rows, 256 / GS, 2048), groups), s, (const T*)x, ldx, (const T*)gamma, (const T*)beta,  \
+                                        (T*)y, ldy, mean, rstd, rows, C, eps, act, pstride, map); }
     TC_DISPATCH_DTYPE(dtype, { TC_LN_DISPATCH(quads, TC_LNF) });
 #undef TC_LNF
     return tc_launch_status();
@@ -923,6 +1148,115 @@ extern "C" int tc_layernorm_bwd_params(const void* dy, int lddy, const void* x, 
     TC_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((ln_param_grad_kernel<T>), grid, dim3(256), 0, (hipStream_t)stream, (const T*)dy, lddy,
                                                 (const T*)x, ldx, (const T*)gamma, (const T*)beta, mean, rstd, dgamma, dbeta, rows, C, act,
                                                 pstride));
+    return tc_launch_status();
+}
+
+// ---- include/transception_bridge.h
+extern "C" int tc_bridge_abi_version(void) { return TC_BRIDGE_ABI_VERSION; }
+
+extern "C" int tc_sr_ln_supported(int rows, int C, int dtype) {
+    // (below 131072 rows tc_layernorm_bwd_defer keeps one row per lane group and iteration: the only shape sr_ln_bwd_kernel is built for)
+    return C == 64 && (dtype == TC_BF16 || dtype == TC_F16) && rows > 0 && rows < 131072;
+}
+
+// the sources in row order, checked: they tile [0, Nk), and every address the kernels form is aligned
+static int sr_ln_sources(const TcSrSrc* srcs, int nsrc, int B, int Nk, bool bwd, SrDev& d) {
+    if (!srcs || nsrc < 1 || nsrc > TC_SR_LN_MAX || B <= 0 || Nk <= 0 || (long long)B * Nk >= 131072) return TC_ERR_ARG;
+    d.n = nsrc; d.Nk = Nk;
+    for (int i = 0; i < nsrc; ++i) {
+        const TcSrSrc& t = srcs[i];
+        if (!t.src || (bwd && !t.dsrc) || t.mult < 0 || t.off < 0) return TC_ERR_ARG;
+        if (((uintptr_t)t.src | (bwd ? (uintptr_t)t.dsrc : 0)) & 15) return TC_ERR_ARG;
+        int nrows;
+        if (t.mult > 0) {
+            if (t.P <= 0 || t.mult > 64) return TC_ERR_ARG;
+            nrows = t.mult * t.P;
+        } else {
+            if (t.rows <= 0 || t.ld < 64 || (t.ld & 7) || (t.sb & 7) || t.sb < 0) return TC_ERR_ARG;
+            nrows = t.rows;
+        }
+        if ((long long)t.off + nrows > Nk) return TC_ERR_ARG;
+        SrSrcDev v{t.src, bwd ? t.dsrc : nullptr, t.mult > 0 ? 0 : t.sb, t.mult, t.mult > 0 ? t.P : 0, t.mult > 0 ? 0 : t.ld, t.off, t.off + nrows,
+                   (bwd && t.mult == 0 && t.acc) ? 1 : 0};
+        int k = i;
+        for (; k > 0 && d.s[k - 1].off > v.off; --k) d.s[k] = d.s[k - 1];
+        d.s[k] = v;
+    }
+    int at = 0;
+    for (int i = 0; i < nsrc; ++i) {
+        if (d.s[i].off != at) return TC_ERR_ARG;
+        at = d.s[i].end;
+    }
+    return at == Nk ? TC_OK : TC_ERR_ARG;
+}
+
+extern "C" int tc_sr_ln_fwd(const TcSrSrc* srcs, int nsrc, int B, int Nk, const void* gamma, const void* beta, void* y, int ldy, float* mean,
+                            float* rstd, float eps, int dtype, void* stream) {
+    if ((dtype != TC_BF16 && dtype != TC_F16) || !gamma || !beta || !y || !mean || !rstd || ldy < 64 || (ldy & 7) ||
+        (((uintptr_t)gamma | (uintptr_t)beta | (uintptr_t)y) & 15))
+        return TC_ERR_ARG;
+    SrDev d;
+    if (sr_ln_sources(srcs, nsrc, B, Nk, false, d) != TC_OK) return TC_ERR_ARG;
+    const int rows = B * Nk;
+    hipStream_t s = (hipStream_t)stream;
+    // tc_layernorm_fwd's launch shapes for C = 64
+#define TC_SRF(T_)                                                                                                                             \
+    if (rows >= 4096) hipLaunchKernelGGL((sr_ln_fwd_kernel<T_, 4>), dim3(tc_blocks(rows, 16 * 4, 2048)), dim3(256), 0, s, SrRows<T_>{d},          \
+                                         (const T_*)gamma, (const T_*)beta, (T_*)y, ldy, mean, rstd, rows, eps);                                 \
+    else hipLaunchKernelGGL((sr_ln_fwd_kernel<T_, 1>), dim3(tc_blocks(rows, 16, 2048)), dim3(256), 0, s, SrRows<T_>{d}, (const T_*)gamma,       \
+                            (const T_*)beta, (T_*)y, ldy, mean, rstd, rows, eps);
+    if (dtype == TC_BF16) { TC_SRF(bf16_t) } else { TC_SRF(f16_t) }
+#undef TC_SRF
+    return tc_launch_status();
+}
+
+extern "C" int tc_sr_ln_bwd(const TcSrSrc* srcs, int nsrc, int B, int Nk, const void* dy, int lddy, const void* gamma, const float* mean,
+                            const float* rstd, float* part, long long part_floats, int dtype, void* stream) {
+    if ((dtype != TC_BF16 && dtype != TC_F16) || !dy || !gamma || !mean || !rstd || !part || lddy < 64 || (lddy & 7) ||
+        (((uintptr_t)dy | (uintptr_t)gamma) & 15))
+        return TC_ERR_ARG;
+    SrDev d;
+    if (sr_ln_sources(srcs, nsrc, B, Nk, true, d) != TC_OK) return TC_ERR_ARG;
+    const int rows = B * Nk;
+    const int nblk = ln_bwd_nblk(rows, 64, true, true);             // tc_layernorm_bwd_defer's workgroups: the same rows in each, the same partials
+    if (part_floats < (long long)nblk * 2 * 64 || rows >= 2LL * nblk * 32) return TC_ERR_ARG;
+    hipStream_t s = (hipStream_t)stream;
+    if (dtype == TC_BF16)
+        hipLaunchKernelGGL((sr_ln_bwd_kernel<bf16_t>), dim3(nblk), dim3(256), (size_t)32 * 2 * 64 * sizeof(float), s, SrRows<bf16_t>{d},
+                           (const bf16_t*)dy, lddy, (const bf16_t*)gamma, mean, rstd, part, rows);
+    else
+        hipLaunchKernelGGL((sr_ln_bwd_kernel<f16_t>), dim3(nblk), dim3(256), (size_t)32 * 2 * 64 * sizeof(float), s, SrRows<f16_t>{d},
+                           (const f16_t*)dy, lddy, (const f16_t*)gamma, mean, rstd, part, rows);
+    return tc_launch_status();
+}
+
+extern "C" int tc_layernorm_fwd_multi(const TcLnSeg* segs, int n, int dtype, void* stream) {
+    if (!segs || n < 1 || n > TC_LN_MULTI_MAX || (dtype != TC_F32 && dtype != TC_BF16 && dtype != TC_F16)) return TC_ERR_ARG;
+    bool one = dtype != TC_F32 && n > 1;
+    LnMultiDev q;
+    int nbmax = 0;
+    for (int i = 0; i < n; ++i) {
+        const TcLnSeg& t = segs[i];
+        if (!t.x || !t.y || !t.gamma || !t.beta || !t.mean || !t.rstd || t.rows <= 0 || t.C <= 0 || (t.C & 3) || t.C > LN_MAXC || (t.ldx & 3) ||
+            (t.ldy & 3) || (t.act != TC_ACT_NONE && t.act != TC_ACT_GELU))
+            return TC_ERR_ARG;                                     // ln_fwd_impl's conditions, for every segment before anything is launched
+        one = one && t.rows < 4096;
+        const int quads = t.C >> 2, GS = quads <= 16 ? 16 : (quads <= 32 ? 32 : 64);
+        q.s[i] = t;
+        q.nb[i] = tc_blocks(t.rows, 256 / GS, 2048);
+        nbmax = q.nb[i] > nbmax ? q.nb[i] : nbmax;
+    }
+    if (!one) {
+        for (int i = 0; i < n; ++i) {
+            const TcLnSeg& t = segs[i];
+            const int rc = ln_fwd_impl(t.x, t.ldx, t.gamma, t.beta, t.y, t.ldy, t.mean, t.rstd, t.rows, t.C, t.eps, t.act, 1, 0, dtype, stream,
+                                       LnMap{0, 0, 0});
+            if (rc != TC_OK) return rc;
+        }
+        return TC_OK;
+    }
+    if (dtype == TC_BF16) hipLaunchKernelGGL((ln_fwd_multi_kernel<bf16_t>), dim3(nbmax, n), dim3(256), 0, (hipStream_t)stream, q);
+    else hipLaunchKernelGGL((ln_fwd_multi_kernel<f16_t>), dim3(nbmax, n), dim3(256), 0, (hipStream_t)stream, q);
     return tc_launch_status();
 }
 

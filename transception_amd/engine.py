@@ -19,7 +19,7 @@ from typing import Callable, Dict, List, Optional, Tuple
 import torch
 
 from ._lib import (ATTN_DKV_SPLITS, EW_COPY, EW_DEINTERLEAVE, EW_PATCHIFY, TcEffAtt, TcEwSeg, TcFfnBwd, TcFfnFused, ACT_COORD, ACT_GELU, ACT_HSWISH, ACT_NONE, ACT_SCALE, ACT_SIGMOID, FFN_EP, FFN_LN_A, FFN_LN_B, TC_BF16, TC_F16, TC_F32, TcDwFold, TcDwSeg, TcFfnSeg,
-                   TcGemm, TcLnFold, lib)
+                   TcGemm, TcLnFold, TcLnSeg, TcSrSrc, LN_MULTI_MAX, lib)
 
 TC_DTYPE = {torch.float32: TC_F32, torch.bfloat16: TC_BF16, torch.float16: TC_F16}     # the storage dtypes, as the library's codes
 
@@ -82,7 +82,7 @@ class Var:
 
     Children made by colslice()/rowslice()/reshape() share the root's storage *and* the root's gradient buffer;
     every view knows the rectangle of the root it covers so that gradient writes from overlapping views accumulate."""
-    __slots__ = ("data", "root", "path", "kids", "grad_t", "whole_written", "written", "requires_grad", "region", "reshaped", "covered", "bn_part")
+    __slots__ = ("data", "root", "path", "kids", "grad_t", "whole_written", "written", "requires_grad", "region", "reshaped", "covered", "bn_part", "pending")
 
     def __init__(self, data: torch.Tensor, root: "Var" = None, path=None, requires_grad: bool = True, region=None,
                  reshaped: bool = False):
@@ -97,6 +97,7 @@ class Var:
         self.requires_grad = requires_grad
         self.region = region if region is not None else (0, data.shape[0], 0, data.shape[1])   # in root coordinates
         self.covered = False                           # root only: slice writers are known to cover the whole gradient before any read
+        self.pending: List[tuple] = []                 # root only: residual gradients that are pure copies, not yet made (Graph._defer_residual)
         self.reshaped = reshaped
 
     rows = property(lambda s: s.data.shape[0])
@@ -184,6 +185,9 @@ _EFFATT_FUSED = os.environ.get("TC_EFFATT_FUSED", "1") != "0"        # Efficient
 # measured a wash -- 13.12 vs 13.08 ms per step with it on: the tiled kernels are VALU-bound, so the +17 us (backward) / +2 us (forward)
 # the in-kernel LayerNorm costs per site cancel the two memory-bound launches it removes (negative results).
 _FFN_PRE_LN = os.environ.get("TC_FFN_PRE_LN", "0") != "0"
+_SR_LN_FUSED = os.environ.get("TC_SR_LN_FUSED", "1") != "0"          # Scale_reduce tail: de-interleaves + stage-4 copy + LayerNorm as one launch each way (tc_sr_ln_*)
+_LN_MULTI = os.environ.get("TC_LN_MULTI", "1") != "0"                # the stand-alone LayerNorm + GELU of all wide MixFFN sites of a call in one launch (tc_layernorm_fwd_multi)
+_PENDING_RES = os.environ.get("TC_PENDING_RES", "1") != "0"          # residual gradients that are pure copies reach the LayerNorm backward as its `dres` rows instead of being copied first
 _LIN_LN_FUSED = os.environ.get("TC_LIN_LN_FUSED", "1") != "0"       # square Linear + residual + LayerNorm (proj / reprojection + skip + norm2) as one forward launch (csrc/linln.hip)
 _RIPM_FUSED = os.environ.get("TC_RIPM_FUSED", "1") != "0"            # a DWConv2d_BN step of the RIPM stages per launch, BatchNorm applied by the consumer (csrc/ripm.hip)
 _LN_CLS_FUSED = os.environ.get("TC_LN_CLS_FUSED", "1") != "0"        # FinalPatchExpand_X4's rearrange + LayerNorm and the classifier as one forward / one backward launch (csrc/lncls.hip, round 6)
@@ -271,6 +275,7 @@ class Graph:
         self.tape: list = []                                 # backward closures, plus ("mark", name) cuts
         self._ln_pending: list = []                          # LayerNorm backward launches whose dgamma / dbeta partials wait for the leg's fold
         self._dw_pending: list = []                          # depthwise backward launches whose weight-gradient sums wait for the leg's fold
+        self._res_pending: List[Var] = []                    # roots with pending residual gradients (_defer_residual)
         self.cur = torch.cuda.current_stream(device) if torch.device(device).type == "cuda" else None
         self.stream = self.cur.cuda_stream if self.cur is not None else 0
         self.n_launch = 0
@@ -291,9 +296,63 @@ class Graph:
         return _empty(shape, torch.float32, self.dev)
 
     # ------------------------------------------------------------------ gradient bookkeeping
+    # A residual branch hands its gradient on unchanged: a copy of rows of the consumer's incoming gradient into the gradient of the block's
+    # input -- which the LayerNorm backward of the block then reads back as its `dres` rows and overwrites.  Where the copies of a root would
+    # reproduce consecutive rows of ONE tensor in the root's own layout (the four per-scale MixFFN residuals of a bridge layer: row groups of
+    # tx2's gradient; the per-scale `proj` residuals of the channel-attention layer), they are not made: they wait on the root as (rows,
+    # source) and the LayerNorm backward takes the source tensor itself as dres.  Everything else that touches the root's gradient first
+    # makes the copies, in one launch, as before -- nothing can observe a missing one.
+    def _defer_residual(self, v: Var, src: torch.Tensor, nelem: int) -> bool:
+        """Leave `v.grad = nelem dense elements at src` (whole rows of v's root, from v's first row) pending; False: the caller copies
+        (or, for a whole root, aliases: pass_grad)."""
+        r = v.root
+        cols = r.data.shape[1]
+        if not (_PENDING_RES and v.requires_grad and not v.is_whole and r.grad_t is None and not r.written and not r.whole_written and r.data.is_contiguous()
+                and v.region[2] == 0 and v.region[3] == cols and src.is_contiguous() and nelem % cols == 0):
+            return False
+        r0, r1 = v.region[0], v.region[0] + nelem // cols
+        if r1 > r.data.shape[0] or any(r0 < b and a < r1 for (a, b, _, _) in r.pending):
+            return False
+        r.pending.append((r0, r1, src.data_ptr(), src))
+        if not any(q is r for q in self._res_pending):
+            self._res_pending.append(r)
+        return True
+
+    def _materialise(self, r: Var):
+        """Make the pending copies of root r: one tc_ew_multi launch per four."""
+        pend, r.pending = r.pending, []
+        self._res_pending = [q for q in self._res_pending if q is not r]
+        cols, segs = r.data.shape[1], []
+        for (r0, r1, ptr, _) in pend:
+            g, acc = self.wgrad(r.rowslice(r0, r1))
+            segs.append(TcEwSeg(EW_COPY, acc, ptr, g.data_ptr(), 0, 0, cols, g.stride(0), 1, r1 - r0, cols, 0, 0, 0))
+        for c0 in range(0, len(segs), 4):
+            self._ew_multi(segs[c0:c0 + 4])
+
+    def _take_pending(self, x: Var):
+        """For a LayerNorm backward about to write the whole gradient of x: (dres pointer, row stride, the tensors to keep) if the pending
+        copies of x's root tile it with consecutive rows of one tensor; None otherwise (wgrad then makes them)."""
+        r = x.root
+        if not r.pending or not x.is_whole:
+            return None
+        pend = sorted(r.pending, key=lambda t: t[0])
+        cols, es, at = r.data.shape[1], r.data.element_size(), 0
+        p0 = pend[0][2] - pend[0][0] * cols * es
+        for (r0, r1, ptr, _) in pend:
+            if r0 != at or ptr != p0 + r0 * cols * es:
+                return None
+            at = r1
+        if at != r.data.shape[0] or p0 % 16:
+            return None
+        r.pending = []
+        self._res_pending = [q for q in self._res_pending if q is not r]
+        return p0, cols, [t[3] for t in pend]
+
     def grad_of(self, v: Var) -> Optional[torch.Tensor]:
         """Gradient view of v for READING (None if nothing was ever written to any part of it)."""
         r = v.root
+        if r.pending:
+            self._materialise(r)
         if r.grad_t is None:
             return None
         if not (r.whole_written or any(_overlap(v.region, w) for w in r.written)):
@@ -304,6 +363,8 @@ class Graph:
         """Gradient view of v for WRITING and whether the kernel must accumulate into it.  ext_rows: the kernel also
         writes that many root rows beyond the view (batch-strided launches whose view is batch 0)."""
         r = v.root
+        if r.pending:
+            self._materialise(r)
         whole = v.is_whole
         reg = (v.region[0], v.region[1] + ext_rows, v.region[2], v.region[3])
         if r.grad_t is None:
@@ -324,18 +385,25 @@ class Graph:
         """Mark `nelem` elements starting `off` elements into the (contiguous) root as gradient-carrying (the writer
         accumulates); returns the root gradient buffer, zero-initialised on first use."""
         assert root.data.is_contiguous()
+        if root.pending:
+            self._materialise(root)
         cols = root.data.shape[1]
         if root.grad_t is None:
             root.grad_t = self._zeros.zeros_like(root.data)
         root.written.append((off // cols, (off + nelem + cols - 1) // cols, 0, cols))
         return root.grad_t
 
-    def pass_grad(self, v: Var, src: torch.Tensor, defer: bool = False):
+    def pass_grad(self, v: Var, src: torch.Tensor, defer: bool = False, pending: bool = False):
         """v.grad (+)= src without a copy when v has no gradient yet (identity / residual branches).  defer: a copy that is needed
-        comes back as a tc_ew_multi segment (None otherwise) for the caller to merge with its neighbours' into one launch."""
+        comes back as a tc_ew_multi segment (None otherwise) for the caller to merge with its neighbours' into one launch.  pending: the
+        caller is a residual branch whose src is final -- the copy may wait on the root for a LayerNorm backward to take it (_defer_residual)."""
         if not v.requires_grad:
             return None
         r = v.root
+        if pending and self._defer_residual(v, src, src.numel()):
+            return None
+        if r.pending:
+            self._materialise(r)
         if v.is_whole and r.grad_t is None and src.stride() == r.data.stride() and src.shape == r.data.shape:
             r.grad_t = src                                   # alias: later contributions accumulate in place
             r.whole_written = True
@@ -391,8 +459,10 @@ class Graph:
             if callable(entry):
                 entry()
             elif entry[1] == until:                      # ("mark", name)
+                self._flush_pending_residuals()
                 self._flush_param_folds()
                 return False
+        self._flush_pending_residuals()
         self._flush_param_folds()
         self.tape = []
         self._zeros.close()
@@ -401,6 +471,11 @@ class Graph:
             with open(SEG_MARKS, "w") as f:
                 json.dump(SEG_LABELS, f)
         return True
+
+    def _flush_pending_residuals(self):
+        """A backward sweep stops or ends: whatever residual copy no LayerNorm backward took is made now."""
+        for r in list(self._res_pending):
+            self._materialise(r)
 
     def _dw_walkers(self, plan, launch, dests):
         """One depthwise weight-gradient launch.  plan(sites, offs) -> the floats its walkers would park, with sites[i]'s geometry and its
@@ -575,10 +650,11 @@ class Graph:
                 self.L.tc_colsum(_ptr(dz), M, N, dz.stride(0), nb, so, _ptr(b.grad), 1, self.dt, self.stream)
             if residual is not None:
                 if nb == 1 or (grouped and not side_by_side):
-                    self.pass_grad(residual, dy)
+                    self.pass_grad(residual, dy, pending=True)
                 else:
                     assert grouped or sr == so
-                    self._pass_grad_batched(residual, dy, nb, M, N, so, sr if grouped else so)
+                    if not (not grouped and self._dense_batches(residual, dy, nb, M, N, so, so) and self._defer_residual(residual, dy, nb * M * N)):
+                        self._pass_grad_batched(residual, dy, nb, M, N, so, sr if grouped else so)
         self._rec(bwd)
         return out
 
@@ -645,8 +721,8 @@ class Graph:
                                                use_ws=False))
                 if res is not None:
                     if nb == 1:
-                        self.pass_grad(res, dy)
-                    else:
+                        self.pass_grad(res, dy, pending=True)
+                    elif not (self._dense_batches(res, dy, nb, M, N, so, sr) and self._defer_residual(res, dy, nb * M * N)):
                         self._pass_grad_batched(res, dy, nb, M, N, so, sr)
             for wi, wv in enumerate(waves):              # (a later wave accumulates onto what an earlier one stored)
                 launch([d for _, d in wv] + (dws if wi == 0 else []))
@@ -838,9 +914,17 @@ class Graph:
             L.tc_dwconv_multi(arr, nold, 0, 1, 0, 1, 0, None, 0, self.dt, self.stream)
         # fc2 on GELU(LN(d)) (+ bias + residual)
         fw = []
+        # the sites whose LayerNorm + GELU is a launch of its own (lng above): all of them in one launch where there are several
+        wide = [t for t in st if not t["lng"]] if (_LN_MULTI and Gn == 1) else []
+        if len(wide) >= 2:
+            for c0 in range(0, len(wide), LN_MULTI_MAX):
+                chunk = wide[c0:c0 + LN_MULTI_MAX]
+                arr = (TcLnSeg * len(chunk))(*[TcLnSeg(_ptr(t["d"]), _ptr(t["lg"].data), _ptr(t["lb"].data), _ptr(t["a"]), _ptr(t["stat"]),
+                                                       t["stat"].data_ptr() + 4, t["C4"], t["C4"], t["M"], t["C4"], 1e-5, ACT_GELU) for t in chunk])
+                L.tc_layernorm_fwd_multi(arr, len(chunk), self.dt, self.stream)
         for i, t in enumerate(st):
             out, res = t["out"], t["res"]
-            if not t["lng"]:                                 # statistics land interleaved ([rows][2]) where the backward hooks read them
+            if not t["lng"] and len(wide) < 2:               # statistics land interleaved ([rows][2]) where the backward hooks read them
                 L.tc_layernorm_fwd(_ptr(t["d"]), t["C4"], _ptr(t["lg"].data), _ptr(t["lb"].data), _ptr(t["a"]), t["C4"], _ptr(t["stat"]),
                                    t["stat"].data_ptr() + 4, t["M"], t["C4"], 1e-5, ACT_GELU, Gn, gs, self.dt, self.stream)
             g = desc(i, _ptr(t["d"] if t["lng"] else t["a"]), t["C4"], _ptr(t["W2"].data), t["C4"], _ptr(out.data), out.ld, t["M"], t["Cin"], t["C4"],
@@ -887,7 +971,7 @@ class Graph:
                     if t["side"]:
                         copies.append(self._pass_grad_batched(t["res"], dy, Gn, t["M"], t["Cin"], t["so"], t["M"] * t["res"].ld, defer=True))
                     else:
-                        copies.append(self.pass_grad(t["res"], dy, defer=True))
+                        copies.append(self.pass_grad(t["res"], dy, defer=True, pending=True))
             copies = [c for c in copies if c is not None]
             for c0 in range(0, len(copies), 4):
                 self._ew_multi(copies[c0:c0 + 4])
@@ -949,6 +1033,11 @@ class Graph:
                     t.pop(k, None)
         self._rec(bwd)
         return [t["out"] for t in st_all]
+
+    @staticmethod
+    def _dense_batches(v: Var, src: torch.Tensor, nb: int, M: int, N: int, sb_src: int, sb_dst: int) -> bool:
+        """The nb batch-strided [M, N] blocks are one dense run of rows on both sides (a candidate for _defer_residual)."""
+        return sb_src == M * N and sb_dst == M * N and src.stride(0) == N and v.ld == N and N == v.root.data.shape[1]
 
     def _pass_grad_batched(self, v: Var, src: torch.Tensor, nb: int, M: int, N: int, sb_src: int, sb_dst: Optional[int] = None,
                            defer: bool = False):
@@ -1035,15 +1124,18 @@ class Graph:
             dy = self.grad_of(out)
             if dy is None or not x.requires_grad:
                 return
+            pend = self._take_pending(x)                 # residual gradients that are pure copies: read where they are (dres), never copied
             gx, acc = self.wgrad(x)
+            assert not (pend and acc)
+            dres, ldres = (pend[0], pend[1]) if pend else (_ptr(gx) if acc else None, gx.stride(0))
             fused = g.grad is not None
             nblk = int(self.L.tc_layernorm_bwd_nblk(rows, Cc)) if (fused and _LN_DEFER) else 0
             if nblk > 0:                                 # dx + per-workgroup dgamma / dbeta partials; the partials of ALL LayerNorms of a backward
                 nf = Gn * nblk * 2 * Cc                  # leg are added up by one launch when the leg ends (_flush_param_folds)
                 part = self.f32(nf)
-                _timed("hbm:layernorm_bwd", (3.0 + acc) * x.rows * Cc * es, lambda: self.L.tc_layernorm_bwd_defer(
+                _timed("hbm:layernorm_bwd", (3.0 + (dres is not None)) * x.rows * Cc * es, lambda: self.L.tc_layernorm_bwd_defer(
                     _ptr(dy), dy.stride(0), _ptr(x.data), x.ld, _ptr(g.data), _ptr(b.data), _ptr(mean), _ptr(rstd), _ptr(gx), gx.stride(0),
-                    _ptr(gx) if acc else None, gx.stride(0), _ptr(g.grad), _ptr(b.grad), rows, Cc, act, Gn, g.gs, _ptr(part), nf, self.dt,
+                    dres, ldres, _ptr(g.grad), _ptr(b.grad), rows, Cc, act, Gn, g.gs, _ptr(part), nf, self.dt,
                     self.stream))
                 self._ln_pending.append((part, g.grad, b.grad, g.gs, nblk, Cc, Gn))
                 if len(self._ln_pending) == 64:
@@ -1052,13 +1144,13 @@ class Graph:
             if fused:                                    # one pass: dx + per-workgroup dgamma/dbeta partials + a tiny folding launch
                 ws = _workspace(self.dev)
                 scratch, n = ws, ws.numel() // 4
-                _timed("hbm:layernorm_bwd", (3.0 + acc) * x.rows * Cc * es, lambda: self.L.tc_layernorm_bwd(
+                _timed("hbm:layernorm_bwd", (3.0 + (dres is not None)) * x.rows * Cc * es, lambda: self.L.tc_layernorm_bwd(
                     _ptr(dy), dy.stride(0), _ptr(x.data), x.ld, _ptr(g.data), _ptr(b.data), _ptr(mean), _ptr(rstd), _ptr(gx), gx.stride(0),
-                    _ptr(gx) if acc else None, gx.stride(0), _ptr(g.grad), _ptr(b.grad), rows, Cc, act, Gn, g.gs, _ptr(scratch), n, self.dt,
+                    dres, ldres, _ptr(g.grad), _ptr(b.grad), rows, Cc, act, Gn, g.gs, _ptr(scratch), n, self.dt,
                     self.stream))
                 return
             self.L.tc_layernorm_bwd(_ptr(dy), dy.stride(0), _ptr(x.data), x.ld, _ptr(g.data), _ptr(b.data), _ptr(mean),      # (frozen gamma / beta: dx alone)
-                                    _ptr(rstd), _ptr(gx), gx.stride(0), _ptr(gx) if acc else None, gx.stride(0),
+                                    _ptr(rstd), _ptr(gx), gx.stride(0), dres, ldres,
                                     None, None, rows, Cc, act, Gn, g.gs, None, 0, self.dt, self.stream)
         self._rec(bwd)
         return out
@@ -1854,6 +1946,71 @@ class Graph:
                                                                             1, self.dt, self.stream))
         self._rec(bwd)
 
+    def sr_ln_supported(self, parts, copy, B: int, Nk: int, g: P, b: P) -> bool:
+        """Whether sr_ln takes these operands (arguments as there): 16-bit storage, one weight group, whole contiguous sources whose pieces are
+        16-byte aligned, and -- when a backward is recorded -- LayerNorm parameters that take a gradient through the deferred fold."""
+        src, s_off, s_sb, _, rows = copy
+        cols = src.cols
+        return (_SR_LN_FUSED and self.ngroups == 1 and self.dt != TC_F32 and cols == 64 and len(parts) <= 3
+                and bool(self.L.tc_sr_ln_supported(B * Nk, cols, self.dt))
+                and (not self.record or (_LN_DEFER and g.grad is not None and b.grad is not None))
+                and all(x.is_whole and x.data.is_contiguous() and x.rows == B * Pn and x.cols == cols * mult and x.data.data_ptr() % 16 == 0
+                        for (x, _, Pn, mult) in parts)
+                and src.is_whole and src.data.is_contiguous() and src.ld % 8 == 0 and s_off % 8 == 0 and s_sb % 8 == 0
+                and src.data.data_ptr() % 16 == 0)
+
+    def sr_ln(self, parts, copy, B: int, Nk: int, g: P, b: P, eps: float = 1e-5) -> Var:
+        """LayerNorm of the Scale_reduce token set [B * Nk, 64] gathered by the kernel's row loader: sr_gather + layernorm without the
+        gathered matrix, ONE launch each way.  parts: (x, first row, Pn, mult) -- x [B * Pn, 64 * mult] de-interleaved into rows
+        first + g * Pn + pos of every image; copy: (src, src_off, src_sb, first row, rows) -- `rows` rows per image from element offset
+        src_off of src, batch stride src_sb.  The backward scatters the input gradient straight into the gradients of the x and into the
+        region gradient of src; dgamma / dbeta leave through the deferred fold like any LayerNorm's."""
+        assert self.sr_ln_supported(parts, copy, B, Nk, g, b)
+        src, s_off, s_sb, c_row, c_rows = copy
+        es, rows = src.data.element_size(), B * Nk
+        out = self.new(rows, 64)
+        mean, rstd = self.f32(rows), self.f32(rows)
+
+        def sources(grads):
+            arr = (TcSrSrc * (len(parts) + 1))()
+            for i, (x, row, Pn, mult) in enumerate(parts):
+                arr[i] = TcSrSrc(_ptr(x.data), grads[i][0] if grads else None, 0, mult, Pn, 0, 0, row, 0)
+            arr[len(parts)] = TcSrSrc(src.data.data_ptr() + s_off * es, grads[-1][0] if grads else None, s_sb, 0, 0, src.ld, c_rows, c_row,
+                                      grads[-1][1] if grads else 0)
+            return arr
+
+        _timed("hbm:sr_ln_fwd", 2.0 * rows * 64 * es, lambda: self.L.tc_sr_ln_fwd(
+            sources(None), len(parts) + 1, B, Nk, _ptr(g.data), _ptr(b.data), _ptr(out.data), out.ld, _ptr(mean), _ptr(rstd), eps, self.dt,
+            self.stream))
+
+        def bwd():
+            dy = self.grad_of(out)
+            if dy is None:
+                return
+            grads, late = [], []
+            for (x, row, Pn, mult) in parts:
+                gx, acc = self.wgrad(x)
+                if acc:                                          # (not on the model's path: x is the fresh output of a convolution)
+                    tmp = torch.empty((gx.shape[0], gx.shape[1]), dtype=gx.dtype, device=gx.device)
+                    late.append((gx, tmp))
+                    gx = tmp
+                grads.append((_ptr(gx), 0))
+            gt = self._region_grad(src.root, s_off, B * s_sb)
+            grads.append((gt.data_ptr() + s_off * es, 1))
+            nblk = int(self.L.tc_layernorm_bwd_nblk(rows, 64))
+            part = self.f32(nblk * 2 * 64)
+            _timed("hbm:sr_ln_bwd", 3.0 * rows * 64 * es, lambda: self.L.tc_sr_ln_bwd(
+                sources(grads), len(parts) + 1, B, Nk, _ptr(dy), dy.stride(0), _ptr(g.data), _ptr(mean), _ptr(rstd), _ptr(part), nblk * 2 * 64,
+                self.dt, self.stream))
+            self._ln_pending.append((part, g.grad, b.grad, g.gs, nblk, 64, 1))
+            if len(self._ln_pending) == 64:
+                self._flush_param_folds()
+            for gx, tmp in late:
+                self.L.tc_add(_ptr(gx), gx.stride(0), _ptr(tmp), tmp.stride(0), _ptr(gx), gx.stride(0), gx.shape[0], gx.shape[1], self.dt,
+                              self.stream)
+        self._rec(bwd)
+        return out
+
     def copy_rows(self, src: Var, src_off: int, src_sb: int, dst: Var, dst_off: int, dst_sb: int, nb: int, rows: int, cols: int):
         """dst[b, r, :] = src[b, r, :] for batch-strided row blocks (offsets/strides in elements of the contiguous roots)."""
         assert src.data.is_contiguous() and dst.data.is_contiguous() and src.is_whole and dst.is_whole
@@ -1925,6 +2082,8 @@ class Graph:
                 # scales' launches together cover it) -- a zero-filled buffer, always added to
                 r = src.root
                 assert src.is_whole
+                if r.pending:
+                    self._materialise(r)
                 if r.grad_t is None:
                     r.grad_t = self._zeros.zeros_like(r.data)
                 r.whole_written = True

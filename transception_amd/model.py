@@ -1129,6 +1129,12 @@ def _scale_reduce(M, G, n: Var, name: str, B: int, sides: List[int], ntok: List[
             xo = G.linear(extra[0], extra[1], extra[2], post_scale=extra[3])
     roffs = [0, MULT[0] * Pn, (MULT[0] + MULT[1]) * Pn, (MULT[0] + MULT[1] + MULT[2]) * Pn]
     if merged:
+        # the de-interleaves, the stage-4 copy and the LayerNorm as one launch (and one for the gradients) where the library takes the shapes
+        parts, copy = [(os_[s], roffs[s], Pn, MULT[s]) for s in range(3)], (n, R[3] * Cd, ntok[3] * Cd, roffs[3], ntok[3])
+        gn, bn = M._P(G, name + ".norm.weight"), M._P(G, name + ".norm.bias")
+        if G.sr_ln_supported(parts, copy, B, Nk, gn, bn):
+            rn = G.sr_ln(parts, copy, B, Nk, gn, bn)
+            return rn if extra is None else (rn, xo)
         G.sr_gather([(os_[s], roffs[s] * Cd, Nk * Cd, B, Pn, Cd, MULT[s]) for s in range(3)],
                     (n, R[3] * Cd, ntok[3] * Cd, roffs[3] * Cd, Nk * Cd, B, ntok[3], Cd), red)
     else:
