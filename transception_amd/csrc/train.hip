@@ -2,6 +2,7 @@
 // (trainer.py:141-143, utils.py:24-47), its class-weighted / ignore_index form (nn.CrossEntropyLoss(weight, ignore_index), trainer.py:141;
 // DiceLoss.forward(weight=...), utils.py:34-47) and the fused SGD-momentum update (trainer.py:125).
 #include "tc_common.h"
+#include "../../include/transception_loss.h"
 
 namespace {
 
@@ -48,10 +49,24 @@ template <typename T> __device__ __forceinline__ void tok_row_store(T* dp, int n
 // then Dice weights, NULL = all ones, staged in LDS once per workgroup; ignore: the label value whose pixels are left out of every sum and get an
 // exactly zero gradient (TC_IGNORE_NONE: no such label).  The forward needs the CE weights only -- I, Y, Z stay unweighted, so the sums vector
 // and its all-reduce are what they were, and the CE denominator sum_k w_ce[k] Y_k is formed from the (global) sums where it is needed.
-template <typename T, bool WEIGHTED>
+//
+// FT (focal CE and Tversky overlap, tc_seg_loss_*_ft; include/transception_loss.h has the definition) is a further variant, of the WEIGHTED
+// bodies: every line it adds sits under `if constexpr (FT)`, and its scalars travel in a last kernel argument that is an empty struct in the
+// other instantiations, which therefore keep their instruction sequence too.  gamma and the overlap mode are run-time values.
+template <bool FT> struct LossOpts {};
+template <> struct LossOpts<true> { float gamma; int tversky; float alpha, beta; };
+
+// the focal CE factor of a pixel: q^gamma, with gamma = 0 giving 1 for every q (q = 0 included)
+__device__ __forceinline__ float focal_pow(float q, float gamma) { return gamma == 0.f ? 1.f : powf(q, gamma); }
+// log max(p_t, 1e-38) of the focal variant.  p_t = 1 - q, so above p_t = 3/4 it is log1p(-q): p_t rounds to 1 for q below 6e-8 and its
+// logarithm to 0, where the true value is -q.  Below, the logarithm of the clamped p_t as the other variants take it
+__device__ __forceinline__ float focal_log_pt(float pt, float q) { return q < 0.25f ? log1pf(-q) : logf(fmaxf(pt, 1e-38f)); }
+
+template <typename T, bool WEIGHTED, bool FT = false>
 __global__ __launch_bounds__(256) void seg_loss_fwd_kernel(const T* __restrict__ logits, const long long* __restrict__ labels,
                                                            float* __restrict__ prob, float* __restrict__ sums, int B, int ncls, int HW, int ld,
-                                                           const float* __restrict__ weights, int ignore) {
+                                                           const float* __restrict__ weights, int ignore, LossOpts<FT> ft) {
+    static_assert(WEIGHTED || !FT, "FT extends the WEIGHTED variant");
     __shared__ float red[4][1 + 3 * MAXCLS];
     __shared__ float wce[WEIGHTED ? MAXCLS : 1];
     if constexpr (WEIGHTED) {
@@ -83,6 +98,23 @@ __global__ __launch_bounds__(256) void seg_loss_fwd_kernel(const T* __restrict__
         const float inv = 1.f / s;
         const int lab = (int)labels[i];
         float* pp = prob + (long long)b * ncls * HW + p;
+        if constexpr (FT) {
+            // q = 1 - p_t as the sum of the other classes' probabilities, in class order (the backward forms it the same way); the third
+            // per-class sum is P_k = sum p under Tversky, Z_k = sum p^2 under Dice
+            const bool counted = lab != ignore;
+            float q = 0.f, pt = 1.f;
+#pragma unroll
+            for (int k = 0; k < MAXCLS; ++k) if (k < ncls) {
+                const float pk = v[k] * inv;
+                if (prob) pp[(long long)k * HW] = pk;
+                if (counted) {
+                    Z[k] += ft.tversky ? pk : pk * pk;
+                    if (k == lab) { I[k] += pk; Y[k] += 1.f; pt = pk; } else q += pk;
+                }
+            }
+            if (counted && (unsigned)lab < (unsigned)ncls) ce -= wce[lab] * focal_pow(q, ft.gamma) * focal_log_pt(pt, q);
+            continue;
+        }
         if constexpr (WEIGHTED) {
             const bool counted = lab != ignore;                    // one test per pixel; an ignored pixel still writes its probabilities
 #pragma unroll
@@ -121,11 +153,16 @@ __global__ __launch_bounds__(256) void seg_loss_fwd_kernel(const T* __restrict__
 // whole numbers, exact in fp32 below 2^24 counted pixels in all) and folds w_dice[k] into ca / cb; per pixel the CE factor is
 // (w_ce / n_eff) * w_ce[lab] in that order, which with all-ones weights is w_ce / n_pix to the bit.  n_eff = 0 (every pixel ignored, or only
 // zero-weight classes present): the CE term has no gradient.  An ignored pixel's gradient is WRITTEN as zeros (dlogits is uninitialised memory).
-template <typename T, bool WEIGHTED>
+//
+// FT: under Tversky ca / cb are the coefficients of g_k = ca_k [k = lab] + cb_k (cb is NOT multiplied by p_k) from I, Y and P = sums[3 + 3k];
+// per pixel the CE factor is additionally multiplied by m = q^gamma (1 - gamma p_t log p_t / q), and p_t - 1 is taken as -q.
+template <typename T, bool WEIGHTED, bool FT = false>
 __global__ __launch_bounds__(256) void seg_loss_bwd_kernel(const float* __restrict__ prob, const long long* __restrict__ labels,
                                                            const float* __restrict__ sums, T* __restrict__ dlogits, int B, int ncls,
                                                            int HW, float w_ce, float w_dice, float n_pix, float gscale, const float* __restrict__ gscale_dev, int ld,
-                                                           const T* __restrict__ logits, int ldl, const float* __restrict__ weights, int ignore) {
+                                                           const T* __restrict__ logits, int ldl, const float* __restrict__ weights, int ignore,
+                                                           LossOpts<FT> ft) {
+    static_assert(WEIGHTED || !FT, "FT extends the WEIGHTED variant");
     if (gscale_dev) gscale *= *gscale_dev;
     const bool vin = !prob && !(ldl & 7) && ldl >= ((ncls + 7) & ~7) && !((uintptr_t)logits & 15);
     const bool vout = ld > 0 && !(ld & 7) && ld >= ((ncls + 7) & ~7) && !((uintptr_t)dlogits & 15);
@@ -142,6 +179,14 @@ __global__ __launch_bounds__(256) void seg_loss_bwd_kernel(const float* __restri
             cb[threadIdx.x] *= wd;
             wce[threadIdx.x] = wc;
             wy[threadIdx.x] = wc * Y;
+            if constexpr (FT) {
+                if (ft.tversky) {                                   // Z is P = sum p here
+                    const float r = 1.f - ft.alpha - ft.beta, tn = I + 1e-5f;
+                    const float D = r * I + ft.alpha * Z + ft.beta * Y + 1e-5f;
+                    ca[threadIdx.x] = -w_dice / (float)ncls * wd * (D - tn * r) / (D * D);
+                    cb[threadIdx.x] = w_dice / (float)ncls * wd * tn * ft.alpha / (D * D);
+                }
+            }
         }
     }
     __syncthreads();
@@ -178,6 +223,35 @@ __global__ __launch_bounds__(256) void seg_loss_bwd_kernel(const float* __restri
             const float inv = 1.f / ssum;
 #pragma unroll
             for (int k = 0; k < MAXCLS; ++k) if (k < ncls) pk[k] *= inv;
+        }
+        if constexpr (FT) {
+            float q = 0.f, pt = 1.f;                               // as the forward forms them
+#pragma unroll
+            for (int k = 0; k < MAXCLS; ++k) if (k < ncls) {
+                g[k] = (k == lab ? ca[k] : 0.f) + (ft.tversky ? cb[k] : cb[k] * pk[k]);
+                dot += g[k] * pk[k];
+                if (k == lab) pt = pk[k]; else q += pk[k];
+            }
+            // m = q^(gamma - 1) (q - gamma p_t log p_t) as q^gamma (1 - gamma p_t log p_t / q): no power of q overflows, and p_t near 1
+            // has -log p_t of the order of q.  gamma = 0: 1; q = 0 under gamma > 0: 0
+            float mod = 1.f;
+            if (ft.gamma != 0.f) mod = q > 0.f ? powf(q, ft.gamma) * (1.f - ft.gamma * pt * focal_log_pt(pt, q) / q) : 0.f;
+            const bool counted = lab != ignore;
+            const float cw = cew * ((unsigned)lab < (unsigned)ncls ? wce[lab] : 1.f) * mod;
+            T* dp = ld ? dlogits + i * ld : dlogits + (long long)b * ncls * HW + p;
+            const long long ks = ld ? 1 : HW;
+            if (sizeof(T) == 2 && vout) {
+                float o[MAXCLS];
+#pragma unroll
+                for (int k = 0; k < MAXCLS; ++k)
+                    o[k] = (k < ncls && counted) ? gscale * (cw * (k == lab ? -q : pk[k]) + pk[k] * (g[k] - dot)) : 0.f;
+                tok_row_store<T>(dp, ncls, o);
+            } else {
+#pragma unroll
+                for (int k = 0; k < MAXCLS; ++k) if (k < ncls)
+                    stf<T>(dp + k * ks, counted ? gscale * (cw * (k == lab ? -q : pk[k]) + pk[k] * (g[k] - dot)) : 0.f);
+            }
+            continue;
         }
 #pragma unroll
         for (int k = 0; k < MAXCLS; ++k) if (k < ncls) {
@@ -465,7 +539,7 @@ extern "C" int tc_seg_loss_fwd(const void* logits, const long long* labels, floa
     if (!logits || !labels || !prob || !sums || B <= 0 || ncls <= 0 || ncls > MAXCLS || HW <= 0 || (long long)B * HW >= 0x7fffffffLL) return TC_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
     TC_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((seg_loss_fwd_kernel<T, false>), dim3(tc_blocks((long long)B * HW, 256, 1024)), dim3(256), 0, s,
-                                                (const T*)logits, labels, prob, sums, B, ncls, HW, 0, (const float*)nullptr, 0));
+                                                (const T*)logits, labels, prob, sums, B, ncls, HW, 0, (const float*)nullptr, 0, LossOpts<false>{}));
     return tc_launch_status();
 }
 
@@ -474,7 +548,7 @@ extern "C" int tc_seg_loss_fwd_tok(const void* logits, int ld, const long long* 
     if (!logits || !labels || !sums || B <= 0 || ncls <= 0 || ncls > MAXCLS || HW <= 0 || ld < ncls || (long long)B * HW >= 0x7fffffffLL) return TC_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
     TC_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((seg_loss_fwd_kernel<T, false>), dim3(tc_blocks((long long)B * HW, 256, 1024)), dim3(256), 0, s,
-                                                (const T*)logits, labels, prob, sums, B, ncls, HW, ld, (const float*)nullptr, 0));
+                                                (const T*)logits, labels, prob, sums, B, ncls, HW, ld, (const float*)nullptr, 0, LossOpts<false>{}));
     return tc_launch_status();
 }
 
@@ -535,7 +609,7 @@ extern "C" int tc_seg_loss_fwd_w(const void* logits, int ld, const long long* la
         return TC_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
     TC_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((seg_loss_fwd_kernel<T, true>), dim3(tc_blocks((long long)B * HW, 256, 1024)), dim3(256), 0, s,
-                                                (const T*)logits, labels, prob, sums, B, ncls, HW, ld, weights, ignore_index));
+                                                (const T*)logits, labels, prob, sums, B, ncls, HW, ld, weights, ignore_index, LossOpts<false>{}));
     return tc_launch_status();
 }
 
@@ -550,7 +624,72 @@ extern "C" int tc_seg_loss_bwd_w(const float* prob, const void* logits, int ldl,
     hipStream_t s = (hipStream_t)stream;
     TC_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((seg_loss_bwd_kernel<T, true>), dim3(tc_blocks((long long)B * HW, 256, 2048)), dim3(256), 0, s,
                                                 prob, labels, sums, (T*)dlogits, B, ncls, HW, w_ce, w_dice, 0.f, gscale, gscale_dev, ld,
-                                                (const T*)logits, ldl, weights, ignore_index));
+                                                (const T*)logits, ldl, weights, ignore_index, LossOpts<false>{}));
+    return tc_launch_status();
+}
+
+// ---- focal CE and Tversky overlap (include/transception_loss.h): the FT variant of the two kernels above and a value kernel of its own
+extern "C" int tc_loss_abi_version(void) { return TC_LOSS_ABI_VERSION; }
+
+// gamma >= 0 and finite; an overlap constant; under Tversky alpha, beta >= 0, finite and not both 0 (the comparisons are false for a NaN)
+static bool loss_opts_ok(double gamma, int overlap, double alpha, double beta) {
+    if (!(gamma >= 0.0 && gamma < (double)INFINITY)) return false;
+    if (overlap == TC_OVERLAP_DICE) return true;
+    return overlap == TC_OVERLAP_TVERSKY && alpha >= 0.0 && alpha < (double)INFINITY && beta >= 0.0 && beta < (double)INFINITY && alpha + beta > 0.0;
+}
+
+extern "C" int tc_seg_loss_fwd_ft(const void* logits, int ld, const long long* labels, const float* weights, int ignore_index, float gamma,
+                                  int overlap, float* prob, float* sums, int B, int ncls, int HW, int dtype, void* stream) {
+    if (!logits || !labels || !sums || B <= 0 || ncls <= 0 || ncls > MAXCLS || HW <= 0 || (ld != 0 && ld < ncls) || (ld == 0 && !prob) ||
+        (ignore_index >= 0 && ignore_index < ncls) || (long long)B * HW >= 0x7fffffffLL || !loss_opts_ok(gamma, overlap, 0.5, 0.5))
+        return TC_ERR_ARG;
+    hipStream_t s = (hipStream_t)stream;
+    const LossOpts<true> ft{gamma, overlap == TC_OVERLAP_TVERSKY, 0.f, 0.f};
+    TC_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((seg_loss_fwd_kernel<T, true, true>), dim3(tc_blocks((long long)B * HW, 256, 1024)), dim3(256), 0, s,
+                                                (const T*)logits, labels, prob, sums, B, ncls, HW, ld, weights, ignore_index, ft));
+    return tc_launch_status();
+}
+
+// tc_seg_loss_value_w's expression with the overlap term chosen by `overlap`; sums[0] already carries the focal factor
+__global__ void seg_loss_value_ft_kernel(const float* __restrict__ sums, const float* __restrict__ weights, int ncls, double w_ce, double w_dice,
+                                         int tversky, double alpha, double beta, float* __restrict__ out3) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    double acc = 0.0, n_eff = 0.0;
+    for (int c = 0; c < ncls; ++c) {
+        const double inter = sums[1 + 3 * c], ysum = sums[2 + 3 * c], zsum = sums[3 + 3 * c];      // zsum: P = sum p under Tversky
+        const double wc = weights ? (double)weights[c] : 1.0, wd = weights ? (double)weights[ncls + c] : 1.0;
+        n_eff += wc * ysum;
+        if (tversky) acc += wd * (1.0 - (inter + 1e-5) / ((1.0 - alpha - beta) * inter + alpha * zsum + beta * ysum + 1e-5));
+        else acc += wd * (1.0 - (2.0 * inter + 1e-5) / (zsum + ysum + 1e-5));
+    }
+    const double ce = n_eff > 0.0 ? (double)sums[0] / n_eff : 0.0;
+    const double ov = acc / (double)ncls;
+    out3[0] = (float)(w_ce * ce + w_dice * ov);
+    out3[1] = (float)ce;
+    out3[2] = (float)ov;
+}
+
+extern "C" int tc_seg_loss_value_ft(const float* sums, const float* weights, int ncls, double w_ce, double w_dice, int overlap, double alpha,
+                                    double beta, float* out3, void* stream) {
+    if (!sums || !out3 || ncls <= 0 || ncls > MAXCLS || !loss_opts_ok(0.0, overlap, alpha, beta)) return TC_ERR_ARG;
+    hipLaunchKernelGGL(seg_loss_value_ft_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, sums, weights, ncls, w_ce, w_dice,
+                       (int)(overlap == TC_OVERLAP_TVERSKY), alpha, beta, out3);
+    return tc_launch_status();
+}
+
+extern "C" int tc_seg_loss_bwd_ft(const float* prob, const void* logits, int ldl, const long long* labels, const float* weights, int ignore_index,
+                                  const float* sums, void* dlogits, int ld, int B, int ncls, int HW, float w_ce, float w_dice, float gamma,
+                                  int overlap, float alpha, float beta, float gscale, const float* gscale_dev, int dtype, void* stream) {
+    if ((!prob && (!logits || ldl < ncls || ld == 0)) || !labels || !sums || !dlogits || B <= 0 || ncls <= 0 || ncls > MAXCLS || HW <= 0 ||
+        (ld != 0 && ld < ncls) || (ignore_index >= 0 && ignore_index < ncls) || (long long)B * HW >= 0x7fffffffLL ||
+        !loss_opts_ok(gamma, overlap, alpha, beta))
+        return TC_ERR_ARG;
+    hipStream_t s = (hipStream_t)stream;
+    const bool tv = overlap == TC_OVERLAP_TVERSKY;
+    const LossOpts<true> ft{gamma, tv, tv ? alpha : 0.f, tv ? beta : 0.f};
+    TC_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((seg_loss_bwd_kernel<T, true, true>), dim3(tc_blocks((long long)B * HW, 256, 2048)), dim3(256), 0, s,
+                                                prob, labels, sums, (T*)dlogits, B, ncls, HW, w_ce, w_dice, 0.f, gscale, gscale_dev, ld,
+                                                (const T*)logits, ldl, weights, ignore_index, ft));
     return tc_launch_status();
 }
 
@@ -569,7 +708,7 @@ extern "C" int tc_seg_loss_bwd(const float* prob, const long long* labels, const
     hipStream_t s = (hipStream_t)stream;
     TC_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((seg_loss_bwd_kernel<T, false>), dim3(tc_blocks((long long)B * HW, 256, 2048)), dim3(256), 0, s,
                                                 prob, labels, sums, (T*)dlogits, B, ncls, HW, w_ce, w_dice, n_pix_global, gscale, gscale_dev, 0, (const T*)nullptr, 0,
-                                                (const float*)nullptr, 0));
+                                                (const float*)nullptr, 0, LossOpts<false>{}));
     return tc_launch_status();
 }
 
@@ -582,7 +721,7 @@ extern "C" int tc_seg_loss_bwd_tok(const float* prob, const void* logits, int ld
     hipStream_t s = (hipStream_t)stream;
     TC_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((seg_loss_bwd_kernel<T, false>), dim3(tc_blocks((long long)B * HW, 256, 2048)), dim3(256), 0, s,
                                                 prob, labels, sums, (T*)dlogits, B, ncls, HW, w_ce, w_dice, n_pix_global, gscale, gscale_dev, ld, (const T*)logits, ldl,
-                                                (const float*)nullptr, 0));
+                                                (const float*)nullptr, 0, LossOpts<false>{}));
     return tc_launch_status();
 }
 

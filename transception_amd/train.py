@@ -14,13 +14,14 @@ from __future__ import annotations
 
 import contextlib
 import math
+import numbers
 import os
 from typing import Optional, Union
 
 import torch
 import torch.distributed as dist
 
-from ._lib import TC_IGNORE_NONE, lib
+from ._lib import TC_IGNORE_NONE, TC_OVERLAP_DICE, TC_OVERLAP_TVERSKY, lib
 from .engine import TC_DTYPE
 
 
@@ -51,25 +52,45 @@ def seg_sums_allreduce(sums: torch.Tensor, n_pix: float, group=None):
     return sums, n_pix * world, world
 
 
-def loss_from_sums(sums: torch.Tensor, n_pix: float, w_ce: float, w_dice: float, weights: Optional[torch.Tensor] = None):
+OVERLAPS = {"dice": TC_OVERLAP_DICE, "tversky": TC_OVERLAP_TVERSKY}     # SegLoss(overlap=...) -> the constant of include/transception_loss.h
+
+
+def loss_from_sums(sums: torch.Tensor, n_pix: float, w_ce: float, w_dice: float, weights: Optional[torch.Tensor] = None, *,
+                   overlap: str = "dice", tversky_alpha: float = 0.5, tversky_beta: float = 0.5):
     """0.4*CE + 0.6*Dice from the (global) sums: trainer.py:141-143, utils.py:34-47 (smooth 1e-5, mean over classes).
     Device sums: one tc_seg_loss_value launch.  Host sums (the gloo tests): the same expression in torch, double.
 
     weights (the class-weighted / ignoring loss, SegLoss._route): [2 * classes] floats, CE weights then Dice weights, on the device
     of `sums`.  sums[0] is then sum_i w[y_i] nll_i and the CE denominator is sum_k w_ce[k] Y_k, taken from the sums themselves
-    (n_pix is not used); a zero denominator gives CE = 0, not NaN.  Dice = sum_k w_dice[k] (1 - ...) / classes (utils.py:42-46)."""
+    (n_pix is not used); a zero denominator gives CE = 0, not NaN.  Dice = sum_k w_dice[k] (1 - ...) / classes (utils.py:42-46).
+
+    overlap="tversky" (sums of the tc_seg_loss_fwd_ft forward under TC_OVERLAP_TVERSKY: the third per-class sum is P_k = sum p): the
+    second term is sum_k w_dice[k] (1 - (I_k + 1e-5) / ((1 - a - b) I_k + a P_k + b Y_k + 1e-5)) / classes with a, b = tversky_alpha,
+    tversky_beta, and the CE denominator is sum_k w_ce[k] Y_k whether weights are given or not.  A focal gamma needs nothing here:
+    sums[0] carries the factor already."""
     ncls = (sums.numel() - 1) // 3
+    if overlap not in OVERLAPS:
+        raise ValueError(f"overlap must be one of {tuple(OVERLAPS)}, got {overlap!r}")
     if sums.is_cuda:
         out3 = torch.empty(3, dtype=torch.float32, device=sums.device)
         stream = torch.cuda.current_stream(sums.device).cuda_stream
-        if weights is None:
+        if overlap != "dice":
+            lib().tc_seg_loss_value_ft(sums.data_ptr(), None if weights is None else weights.data_ptr(), ncls, float(w_ce), float(w_dice),
+                                       OVERLAPS[overlap], float(tversky_alpha), float(tversky_beta), out3.data_ptr(), stream)
+        elif weights is None:
             lib().tc_seg_loss_value(sums.data_ptr(), ncls, float(n_pix), float(w_ce), float(w_dice), out3.data_ptr(), stream)
         else:
             lib().tc_seg_loss_value_w(sums.data_ptr(), weights.data_ptr(), ncls, float(w_ce), float(w_dice), out3.data_ptr(), stream)
         return out3[0], out3[1], out3[2]
     s = sums.double()
     inter, ysum, zsum = s[1::3], s[2::3], s[3::3]
-    per_class = 1.0 - (2.0 * inter + 1e-5) / (zsum + ysum + 1e-5)
+    if overlap == "dice":
+        per_class = 1.0 - (2.0 * inter + 1e-5) / (zsum + ysum + 1e-5)
+    else:
+        a, b = float(tversky_alpha), float(tversky_beta)
+        per_class = 1.0 - (inter + 1e-5) / ((1.0 - a - b) * inter + a * zsum + b * ysum + 1e-5)
+        if weights is None:
+            weights = torch.ones(2 * ncls, dtype=torch.float64)
     if weights is None:
         ce = s[0] / n_pix
         dice = per_class.mean()
@@ -116,6 +137,23 @@ def check_ignore_index(ii, ncls: int) -> Optional[int]:
     if not IGNORE_NONE < ii < 2 ** 31:
         raise ValueError(f"ignore_index {ii} does not fit the kernels' 32-bit label compare")
     return ii
+
+
+def check_focal_tversky(gamma, overlap, alpha, beta) -> tuple:
+    """(focal_gamma, overlap, tversky_alpha, tversky_beta) as (float, str, float, float).  gamma: a finite number >= 0; overlap: "dice" or
+    "tversky"; alpha, beta: finite numbers >= 0, not both 0 -- and, under overlap="dice", left at their default 0.5, so that a Tversky
+    setting without overlap="tversky" does not train on Dice unnoticed.  A number is any numbers.Real but a bool (numpy scalars from a sweep
+    included).  Anything else is a ValueError."""
+    for name, v in (("focal_gamma", gamma), ("tversky_alpha", alpha), ("tversky_beta", beta)):
+        if isinstance(v, bool) or not isinstance(v, numbers.Real) or not math.isfinite(v) or v < 0:
+            raise ValueError(f"{name} must be a finite number >= 0, got {v!r}")
+    if not isinstance(overlap, str) or overlap not in OVERLAPS:
+        raise ValueError(f"overlap must be one of {tuple(OVERLAPS)}, got {overlap!r}")
+    if overlap == "dice" and (alpha != 0.5 or beta != 0.5):
+        raise ValueError(f'tversky_alpha / tversky_beta are read under overlap="tversky" only, got {alpha!r}, {beta!r} with overlap="dice"')
+    if alpha + beta == 0:
+        raise ValueError("tversky_alpha + tversky_beta must be > 0")
+    return float(gamma), overlap, float(alpha), float(beta)
 
 
 class DynamicLossScale:
@@ -211,11 +249,18 @@ def _wire_loss_scale(loss_fn, opt, device) -> None:
         opt.loss_scaler, opt.grad_scale = None, 1.0 / ls
 
 
+def _overlap_of(route) -> dict:
+    """loss_from_sums' overlap keywords for a SegLoss._route: none for the plain and the class-weighted loss."""
+    if route is None or len(route) == 2:
+        return {}
+    return {"overlap": route[3], "tversky_alpha": route[4], "tversky_beta": route[5]}
+
+
 class _SegLossFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, logits, labels, ncls, w_ce, w_dice, group, loss_scale=1.0, route=None):
         """route: None (the plain loss), or SegLoss._route's (weights tensor or None, ignore_index as the kernels take it) -- the
-        class-weighted / ignoring entries, NCHW through ld = 0."""
+        class-weighted / ignoring entries, NCHW through ld = 0 -- or its six-element form, for the tc_seg_loss_*_ft entries."""
         L = lib()
         logits = logits.contiguous()
         B, C, H, W = logits.shape
@@ -226,11 +271,14 @@ class _SegLossFn(torch.autograd.Function):
         labels = labels.contiguous()
         if route is None:
             L.tc_seg_loss_fwd(logits.data_ptr(), labels.data_ptr(), prob.data_ptr(), sums.data_ptr(), B, ncls, H * W, _dt(logits), stream)
-        else:
+        elif len(route) == 2:
             L.tc_seg_loss_fwd_w(logits.data_ptr(), 0, labels.data_ptr(), route[0].data_ptr(), route[1], prob.data_ptr(), sums.data_ptr(),
                                 B, ncls, H * W, _dt(logits), stream)
+        else:                                  # focal CE / Tversky overlap: (weights, ignore_index, gamma, overlap, alpha, beta)
+            L.tc_seg_loss_fwd_ft(logits.data_ptr(), 0, labels.data_ptr(), route[0].data_ptr(), route[1], route[2], OVERLAPS[route[3]],
+                                 prob.data_ptr(), sums.data_ptr(), B, ncls, H * W, _dt(logits), stream)
         sums, n_pix, world = seg_sums_allreduce(sums, float(B * H * W), group)
-        loss, ce, dice = loss_from_sums(sums, n_pix, w_ce, w_dice, None if route is None else route[0])
+        loss, ce, dice = loss_from_sums(sums, n_pix, w_ce, w_dice, None if route is None else route[0], **_overlap_of(route))
         ctx.save_for_backward(prob, labels, sums)
         ctx.meta = (ncls, w_ce, w_dice, n_pix, world, logits.dtype, loss_scale if isinstance(loss_scale, DynamicLossScale) else float(loss_scale))
         ctx.route = route
@@ -253,9 +301,13 @@ class _SegLossFn(torch.autograd.Function):
         if ctx.route is None:
             L.tc_seg_loss_bwd(prob.data_ptr(), labels.data_ptr(), sums.data_ptr(), d.data_ptr(), B, ncls, H * W, float(w_ce), float(w_dice),
                               float(n_pix), loss_scale, gl.data_ptr(), _dt(d), stream)
-        else:
+        elif len(ctx.route) == 2:
             L.tc_seg_loss_bwd_w(prob.data_ptr(), None, 0, labels.data_ptr(), ctx.route[0].data_ptr(), ctx.route[1], sums.data_ptr(),
                                 d.data_ptr(), 0, B, ncls, H * W, float(w_ce), float(w_dice), loss_scale, gl.data_ptr(), _dt(d), stream)
+        else:
+            w, ii, gamma, overlap, alpha, beta = ctx.route
+            L.tc_seg_loss_bwd_ft(prob.data_ptr(), None, 0, labels.data_ptr(), w.data_ptr(), ii, sums.data_ptr(), d.data_ptr(), 0, B, ncls, H * W,
+                                 float(w_ce), float(w_dice), gamma, OVERLAPS[overlap], alpha, beta, loss_scale, gl.data_ptr(), _dt(d), stream)
         return d, None, None, None, None, None, None, None
 
 
@@ -272,10 +324,21 @@ class SegLoss(torch.nn.Module):
     The gradient at an ignored pixel is exactly zero in every class.  The weights live in one small device tensor per device
     (weights(device): CE weights, then Dice weights), created on first use and never replaced: captured launches hold its address, so
     new values are written IN PLACE (weights(device).copy_(...)) and are seen by the next replay.  The CE denominator is taken from the fp32 per-class pixel counts of the
-    sums vector, which are exact while the global number of counted pixels is below 2^24."""
+    sums vector, which are exact while the global number of counted pixels is below 2^24.
+
+    focal_gamma / overlap / tversky_alpha / tversky_beta (0.0, "dice", 0.5, 0.5: the loss above, through the same calls as ever;
+    include/transception_loss.h has the definition and the gradient):
+      CE      = sum_i w[y_i] q_i^gamma nll_i / sum_i w[y_i] with q_i = 1 - p_t, the focal modulation of every pixel's term (the denominator
+                is not modulated);
+      overlap = "tversky": sum_k dice_weight[k] (1 - (I_k + 1e-5) / (I_k + alpha FP_k + beta FN_k + 1e-5)) / n_classes, with FP_k = sum p_k
+                off class k and FN_k = sum (1 - p_k) on it.  alpha = beta = 0.5 is the LINEAR Dice 2 I / (P + Y), not the reference's squared
+                one, which overlap="dice" stays.
+    The returned triple is then (loss, focal CE, overlap term).  These four are scalars, not device memory: a captured step (GraphedStep)
+    keeps the values it was captured with, and changing them needs a new GraphedStep."""
 
     def __init__(self, n_classes: int = 9, w_ce: float = 0.4, w_dice: float = 0.6, group=None,
-                 loss_scale: Union[float, DynamicLossScale] = 1.0, ce_weight=None, dice_weight=None, ignore_index: Optional[int] = None):
+                 loss_scale: Union[float, DynamicLossScale] = 1.0, ce_weight=None, dice_weight=None, ignore_index: Optional[int] = None,
+                 focal_gamma: float = 0.0, overlap: str = "dice", tversky_alpha: float = 0.5, tversky_beta: float = 0.5):
         """loss_scale: the gradient that leaves this loss is multiplied by it (the reported loss is not) -- loss scaling for float16
         storage; FusedSGD.step divides it out again (train_step wires the two together).  A float is a static scale; a
         DynamicLossScale is read from device memory by the backward kernel and adjusts itself after every update.
@@ -287,14 +350,22 @@ class SegLoss(torch.nn.Module):
         self.ce_weight = check_class_weights("ce_weight", ce_weight, n_classes, need_positive=True)
         self.dice_weight = check_class_weights("dice_weight", dice_weight, n_classes, need_positive=False)
         self.ignore_index = check_ignore_index(ignore_index, n_classes)
+        self.focal_gamma, self.overlap, self.tversky_alpha, self.tversky_beta = check_focal_tversky(focal_gamma, overlap, tversky_alpha, tversky_beta)
         if self.weighted and n_classes > 16:
             raise ValueError(f"the class-weighted loss kernels take at most 16 classes, got {n_classes}")
+        if self.focal_tversky and n_classes > 16:
+            raise ValueError(f"the focal / Tversky loss kernels take at most 16 classes, got {n_classes}")
         self._weights = {}                               # device -> fp32 [2 * n_classes]
 
     @property
     def weighted(self) -> bool:
         """True when the class-weighted / ignoring kernels are used (any of the three arguments set)."""
         return self.ce_weight is not None or self.dice_weight is not None or self.ignore_index is not None
+
+    @property
+    def focal_tversky(self) -> bool:
+        """True when the focal / Tversky kernels are used (a focal_gamma above 0 or overlap="tversky")."""
+        return self.focal_gamma != 0.0 or self.overlap != "dice"
 
     def _host_weights(self) -> torch.Tensor:
         ones = (1.0,) * self.n_classes
@@ -310,10 +381,15 @@ class SegLoss(torch.nn.Module):
         return self._weights[d]
 
     def _route(self, device):
-        """None for the plain loss; else (weights tensor, ignore_index or the kernels' "off" value) for the tc_seg_loss_*_w entries."""
-        if not self.weighted:
+        """None for the plain loss; else (weights tensor, ignore_index or the kernels' "off" value) for the tc_seg_loss_*_w entries; with
+        a focal_gamma above 0 or overlap="tversky" that pair followed by (focal_gamma, overlap, tversky_alpha, tversky_beta), for the
+        tc_seg_loss_*_ft entries."""
+        if not self.weighted and not self.focal_tversky:
             return None
-        return self.weights(device), IGNORE_NONE if self.ignore_index is None else self.ignore_index
+        pair = self.weights(device), IGNORE_NONE if self.ignore_index is None else self.ignore_index
+        if not self.focal_tversky:
+            return pair
+        return (*pair, self.focal_gamma, self.overlap, self.tversky_alpha, self.tversky_beta)
 
     def forward(self, logits: torch.Tensor, labels: torch.Tensor):
         route = self._route(logits.device)
@@ -959,7 +1035,8 @@ def _instantiate(g):
 class GraphedStep:
     """A whole training step captured into hipGraphs and replayed: ~1800 kernel launches per step become graph launches,
     removing the host from the loop.  Inputs are copied into static buffers; the learning rate is a device scalar
-    (FusedSGD.set_lr).
+    (FusedSGD.set_lr).  The loss's scalars -- w_ce, w_dice, focal_gamma, overlap, tversky_alpha, tversky_beta -- are kernel arguments
+    and keep the values of the capture: changing them needs a new GraphedStep (the class weights live in device memory and do not).
 
     world == 1: ONE graph = zero_grad + forward + loss + backward + SGD (through torch.autograd).
     world  > 1: no collective is ever captured.  Three graphs with the two RCCL all-reduces between them, driven through
@@ -1054,9 +1131,12 @@ class GraphedStep:
         if route is None:
             L.tc_seg_loss_fwd_tok(logits.data_ptr(), logits.stride(0), self.y.data_ptr(), None, self._sums.data_ptr(), B, C, H * W,
                                   _dt(logits), stream)
-        else:
+        elif len(route) == 2:
             L.tc_seg_loss_fwd_w(logits.data_ptr(), logits.stride(0), self.y.data_ptr(), route[0].data_ptr(), route[1], None,
                                 self._sums.data_ptr(), B, C, H * W, _dt(logits), stream)
+        else:                                  # focal CE / Tversky overlap: the scalars are baked into the captured launches
+            L.tc_seg_loss_fwd_ft(logits.data_ptr(), logits.stride(0), self.y.data_ptr(), route[0].data_ptr(), route[1], route[2],
+                                 OVERLAPS[route[3]], None, self._sums.data_ptr(), B, C, H * W, _dt(logits), stream)
         self._npix_local = float(B * H * W)
 
     def _reduce_sums(self):
@@ -1067,7 +1147,8 @@ class GraphedStep:
         B, C, H, W = self._shape
         lf, lg = self.loss_fn, self._logits
         route = lf._route(lg.device)
-        self.out = tuple(t.float() for t in loss_from_sums(self._sums, self._npix, lf.w_ce, lf.w_dice, None if route is None else route[0]))
+        self.out = tuple(t.float() for t in loss_from_sums(self._sums, self._npix, lf.w_ce, lf.w_dice, None if route is None else route[0],
+                                                           **_overlap_of(route)))
         stream = torch.cuda.current_stream(lg.device).cuda_stream
         # the gradient of the token-major logits, in the logits' own layout (their rows are padded to 16 bytes when the fused LayerNorm +
         # classifier produced them: Graph.ln_cls)
@@ -1078,9 +1159,14 @@ class GraphedStep:
         if route is None:
             L.tc_seg_loss_bwd_tok(None, lg.data_ptr(), lg.stride(0), self.y.data_ptr(), self._sums.data_ptr(), d.data_ptr(), d.stride(0), B, C,
                                   H * W, float(lf.w_ce), float(lf.w_dice), float(self._npix), gscale, gscale_dev, _dt(d), stream)
-        else:                                  # the CE denominator comes from the (all-reduced) sums: no pixel count is passed
+        elif len(route) == 2:                  # the CE denominator comes from the (all-reduced) sums: no pixel count is passed
             L.tc_seg_loss_bwd_w(None, lg.data_ptr(), lg.stride(0), self.y.data_ptr(), route[0].data_ptr(), route[1], self._sums.data_ptr(),
                                 d.data_ptr(), d.stride(0), B, C, H * W, float(lf.w_ce), float(lf.w_dice), gscale, gscale_dev, _dt(d), stream)
+        else:
+            w, ii, gamma, overlap, alpha, beta = route
+            L.tc_seg_loss_bwd_ft(None, lg.data_ptr(), lg.stride(0), self.y.data_ptr(), w.data_ptr(), ii, self._sums.data_ptr(), d.data_ptr(),
+                                 d.stride(0), B, C, H * W, float(lf.w_ce), float(lf.w_dice), gamma, OVERLAPS[overlap], alpha, beta, gscale,
+                                 gscale_dev, _dt(d), stream)
         M._backward(self._G, self._out_var, d, until="encoder_done")     # loss gradient, decoders, bridge
 
     def _bwd_leg(self, until: Optional[str]):

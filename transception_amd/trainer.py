@@ -4,7 +4,8 @@ training step in place of the per-iteration Python loop body.
 
 What is kept from the reference loop:
   * global batch = batch_size * n_gpu (trainer.py:86) -- here batch_size per rank, one process per GPU;
-  * loss 0.4 CE + 0.6 Dice (trainer.py:141-143), SGD(momentum 0.9, weight_decay 1e-4) (:125) -- or, by TrainConfig.optimizer, AdamW / Adam
+  * loss 0.4 CE + 0.6 Dice (trainer.py:141-143) -- with focal_gamma / overlap="tversky" set, 0.4 focal CE + 0.6 Tversky, and the log line's
+    loss_ce / loss_dice are then those two terms --, SGD(momentum 0.9, weight_decay 1e-4) (:125) -- or, by TrainConfig.optimizer, AdamW / Adam
     (train.FusedAdamW) under the same schedule, clipping, loss scale and skip logging; base_lr is used as given, and its default 0.05 is SGD's value;
   * CosineAnnealingLR(T_max = max_epochs * len(loader)) stepped every iteration (:126-127,151-153), or the polynomial decay
     base_lr (1 - iter/max_iter)^0.9 when use_scheduler is off (:154-157); optional clip_grad_norm_(5) (:147-148);
@@ -29,7 +30,7 @@ import torch.distributed as dist
 from .data import DeviceLoader, SynapseSlices
 from .evaluate import RESAMPLE_MODES, TTA, VALID_OPTION, PostProcess, inference
 from .train import (DynamicLossScale, FusedAdamW, FusedSGD, GraphedStep, SegLoss, WeightEMA, check_class_weights, check_ema_decay,
-                    check_ignore_index, cosine_lr, train_step)
+                    check_focal_tversky, check_ignore_index, cosine_lr, train_step)
 
 OPTIMIZERS = ("sgd", "adamw", "adam")
 
@@ -97,6 +98,7 @@ class TrainConfig:
             raise ValueError(f"tta must be None or an evaluate.TTA, got {self.tta!r}")
         if not VALID_OPTION["resample"](self.resample):
             raise ValueError(f"resample must be one of {RESAMPLE_MODES}, got {self.resample!r}")
+        check_focal_tversky(self.focal_gamma, self.overlap, self.tversky_alpha, self.tversky_beta)
         make_loss_scale(self.loss_scale)
         check_class_weights("class_weights", self.class_weights, self.num_classes, need_positive=True)
         check_ignore_index(self.ignore_index, self.num_classes)
@@ -104,27 +106,46 @@ class TrainConfig:
             check_ema_decay(self.ema_decay)
 
 
-def _keyword_only_resample(cls):
-    """`TrainConfig(..., resample="labels")`: what the evaluation resamples to the label's size (evaluate.evaluate_volume: "labels", the
-    reference's order-0 zoom of the argmax, or "scores", bilinear class scores and then the argmax).  Keyword-only, validated in
-    `__post_init__` and kept as a plain attribute beside the dataclass fields: the field list -- the positional order, repr and eq of the
-    configuration, which ends with the ema_* fields -- is what it was."""
-    init = cls.__init__
+# Options that are keyword-only, validated in `__post_init__` and kept as plain attributes beside the dataclass fields: the field list -- the
+# positional order and eq of the configuration, which ends with the ema_* fields -- is what it was.  (name, type, default), in the
+# order of the signature, which ends with `resample`.  What follows from that: `==` compares the fields only, so two configurations that differ
+# in these options alone compare equal, and `dataclasses.replace` / `asdict` do not carry them (a replaced copy has the defaults: pass them
+# again).  `repr` does show them, after the fields.
+#   focal_gamma, overlap, tversky_alpha, tversky_beta: the loss (train.SegLoss has the definition) -- the focal exponent of the
+#     cross-entropy, "dice" or "tversky" for the overlap term, and the Tversky weights of false positives and false negatives;
+#   resample: what the evaluation resamples to the label's size (evaluate.evaluate_volume: "labels", the reference's order-0 zoom of the
+#     argmax, or "scores", bilinear class scores and then the argmax).
+KEYWORD_OPTIONS = (("focal_gamma", float, 0.0), ("overlap", str, "dice"), ("tversky_alpha", float, 0.5), ("tversky_beta", float, 0.5),
+                   ("resample", str, "labels"))
 
-    def __init__(self, *args, resample: str = "labels", **kwargs):
-        self.resample = resample
+
+def _keyword_only_options(cls):
+    """`TrainConfig(..., focal_gamma=2.0, overlap="tversky", resample="scores")`: KEYWORD_OPTIONS on the dataclass's `__init__`."""
+    init = cls.__init__
+    defaults = {name: default for name, _, default in KEYWORD_OPTIONS}
+
+    def __init__(self, *args, **kwargs):
+        for name, default in defaults.items():
+            setattr(self, name, kwargs.pop(name, default))
         init(self, *args, **kwargs)
 
     sig = inspect.signature(init)
-    extra = inspect.Parameter("resample", inspect.Parameter.KEYWORD_ONLY, default="labels", annotation=str)
-    __init__.__signature__ = sig.replace(parameters=[*sig.parameters.values(), extra])
+    extra = [inspect.Parameter(name, inspect.Parameter.KEYWORD_ONLY, default=default, annotation=t) for name, t, default in KEYWORD_OPTIONS]
+    __init__.__signature__ = sig.replace(parameters=[*sig.parameters.values(), *extra])
     __init__.__qualname__ = init.__qualname__
     cls.__init__ = __init__
-    cls.resample = "labels"                       # the default, readable on the class as a field's would be
+    fields_repr = cls.__repr__
+
+    def __repr__(self):
+        return fields_repr(self)[:-1] + "".join(f", {name}={getattr(self, name)!r}" for name in defaults) + ")"
+
+    cls.__repr__ = __repr__
+    for name, default in defaults.items():
+        setattr(cls, name, default)               # the defaults, readable on the class as a field's would be
     return cls
 
 
-TrainConfig = _keyword_only_resample(TrainConfig)
+TrainConfig = _keyword_only_options(TrainConfig)
 
 
 def make_loss_scale(spec) -> Union[float, DynamicLossScale]:
@@ -187,7 +208,8 @@ def trainer_synapse(cfg: TrainConfig, model, snapshot_path: str, volumes: Option
     loss_scale = make_loss_scale(cfg.loss_scale)
     scaler = loss_scale if isinstance(loss_scale, DynamicLossScale) else None
     loss_fn = SegLoss(cfg.num_classes, group=group, loss_scale=loss_scale, ce_weight=cfg.class_weights, dice_weight=cfg.class_weights,
-                      ignore_index=cfg.ignore_index)
+                      ignore_index=cfg.ignore_index, focal_gamma=cfg.focal_gamma, overlap=cfg.overlap, tversky_alpha=cfg.tversky_alpha,
+                      tversky_beta=cfg.tversky_beta)
     opt = make_optimizer(cfg, model)
     ema = None
     if cfg.ema_decay is not None:
