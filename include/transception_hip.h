@@ -244,7 +244,8 @@ int tc_dwconv_bwd(const void* dy, int lddy, const void* x, int ldx, const void* 
  * mode 0: y = conv(x) (+bias) (+x); mode 1: y (= dx) = conv^T(x (= dy)) (+x) (+y when accumulate); mode 2: dw / db += gradients
  * from x and dy; mode 3: both gradients in the one launch -- y (= dx) = conv^T(dy) (+dy) (+y when accumulate) and dw / db += gradients
  * from x and dy (tc_dwconv_bwd per segment).  Every segment carries its own geometry and row strides; groups / wstride are common (see tc_dwconv_fwd);
- * ws as in tc_dwconv_bwd_weight. */
+ * ws as in tc_dwconv_bwd_weight.  Deferred sums (ws_bytes < 0, modes 2 / 3) need every segment on the 16-byte tile kernels: with one that is
+ * not, TC_ERR_ARG before anything is launched. */
 typedef struct TcDwSeg {
     const void* x; const void* w; const void* bias; void* y; const void* dy; float* dw; float* db;
     int C; int k; int ldx; int ldy; int lddy; int B; int H; int W;
@@ -265,7 +266,9 @@ TC_QUERY long long tc_dwconv_multi_plan(const TcDwSeg* segs, int nseg, int group
 /* channels per statistics chunk of tc_ffn_dw_fwd for a C-channel map of this dtype (C must be a multiple of it) */
 TC_QUERY int tc_ffn_chunk(int C, int dtype);
 /* y = dw3x3(x) + bias + x on `groups` stacked sets of B images (parameters of set g at + g*wstride), and
- * stat[((g*B + b)*H*W + pixel) * (C / tc_ffn_chunk) + chunk] = float2(sum, squared deviations from the chunk mean) of y's channels. */
+ * stat[((g*B + b)*H*W + pixel) * (C / tc_ffn_chunk) + chunk] = float2(sum, squared deviations from the chunk mean) of the chunk's channels,
+ * computed from the fp32 result BEFORE it is rounded to y's storage type (in 16-bit storage they are not the statistics of the stored y).
+ * stat may be NULL; with stat, C must be a multiple of tc_ffn_chunk (TC_ERR_ARG otherwise). */
 int tc_ffn_dw_fwd(const void* x, int ldx, const void* w, const void* bias, void* y, int ldy, float* stat, int B, int H, int W,
                   int C, int groups, long long wstride, int dtype, void* stream);
 /* One launch for up to four MixFFN sites (the four scales of a bridge layer):

@@ -1594,7 +1594,8 @@ extern "C" int tc_dw_fold(const TcDwFold* sites, int n, void* stream) {
 extern "C" int tc_dwconv_bwd(const void* dy, int lddy, const void* x, int ldx, const void* w, void* dx, int lddx, float* dw, float* db, int B, int H,
                              int W, int C, int k, int add_input, int accumulate, int groups, long long wstride, void* ws, long long ws_bytes,
                              int dtype, void* stream) {
-    if (!dy || !x || !w || !dx || !dw || (lddy & 3) || (lddx & 3) || groups < 1 || !dw_args_ok(B, H, W, C, k, 1, add_input)) return TC_ERR_ARG;
+    if (!dy || !x || !w || !dx || !dw || (lddy & 3) || (lddx & 3) || (ldx & 3) || groups < 1 || !dw_args_ok(B, H, W, C, k, 1, add_input))
+        return TC_ERR_ARG;
     TC_DISPATCH_DTYPE(dtype, {
         if (dw_tile_ok<T>(dy, lddy, dx, lddx, C) && dw_tile_ok<T>(x, ldx, dy, lddy, C))
             return (launch_tile_bwd<T>(dy, lddy, w, dx, lddx, x, ldx, dw, db, B, H, W, C, k, add_input, accumulate, groups, wstride, (hipStream_t)stream,
@@ -1608,7 +1609,8 @@ extern "C" int tc_dwconv_bwd(const void* dy, int lddy, const void* x, int ldx, c
 extern "C" int tc_dwconv_bwd_weight(const void* dy, int lddy, const void* x, int ldx, float* dw, float* db, int B, int H,
                                     int W, int C, int k, int stride, int groups, long long wstride, void* ws, long long ws_bytes,
                                     int dtype, void* stream) {
-    if (!dy || !x || !dw || groups < 1 || (groups > 1 && stride != 1) || !dw_args_ok(B, H, W, C, k, stride, 0)) return TC_ERR_ARG;
+    if (!dy || !x || !dw || (lddy & 3) || (ldx & 3) || groups < 1 || (groups > 1 && stride != 1) || !dw_args_ok(B, H, W, C, k, stride, 0))
+        return TC_ERR_ARG;
     if (stride == 1)
         TC_DISPATCH_DTYPE(dtype, {
             if (dw_tile_ok<T>(x, ldx, dy, lddy, C))
@@ -1644,6 +1646,7 @@ extern "C" int tc_dwconv_multi(const TcDwSeg* segs, int nseg, int mode, int add_
         const TcDwSeg& g = segs[i];
         if (!g.x || !dw_args_ok(g.B, g.H, g.W, g.C, g.k, 1, add_input) || (mode != 2 && (!g.w || !g.y)) || (mode >= 2 && (!g.dy || !g.dw)))
             return TC_ERR_ARG;
+        if ((g.ldx & 3) || (mode != 2 && (g.ldy & 3)) || (mode >= 2 && (g.lddy & 3))) return TC_ERR_ARG;     // (as the single entries: before any launch)
         const void* second = mode >= 2 ? g.dy : g.y;
         const int ld2 = mode >= 2 ? g.lddy : g.ldy;
         if (dtype == TC_F32) tile_ok = tile_ok && dw_tile_ok<float>(g.x, g.ldx, second, ld2, g.C);
@@ -1653,6 +1656,10 @@ extern "C" int tc_dwconv_multi(const TcDwSeg* segs, int nseg, int mode, int add_
             else tile_ok = tile_ok && dw_tile_ok<bf16_t>(g.dy, g.lddy, g.y, g.ldy, g.C);
         }
     }
+    // Deferred sums exist only in the one launch of the tile kernels, at the offsets of tc_dwconv_multi_plan: refused here, before the first segment
+    // is launched (through the single entries an eligible segment would park its sums in the single launch's layout, at offset 0, and write its dx
+    // before an ineligible one is refused)
+    if (mode >= 2 && ws_bytes < 0 && !tile_ok) return TC_ERR_ARG;
     if (mode == 3 && !tile_ok) {                               // both gradients, one segment at a time through the single entry
         for (int i = 0; i < nseg; ++i) {
             const TcDwSeg& g = segs[i];

@@ -1345,8 +1345,13 @@ class Graph:
                 sg = segs([_ptr(x.data) for x in xs], wd, none, [_ptr(t) for t, _ in g], [_ptr(d) for d in dys],
                           [_ptr(w.grad) for w in ws], [_ptr(b.grad) if b is not None else None for b in bs],
                           [x.ld for x in xs], [t.stride(0) for t, _ in g], ldd)
+                # only the one launch of the tile kernels parks its sums: dw_tile_ok (dwconv.hip) restated for every segment's three maps, as
+                # tc_dwconv_multi applies it (with one ineligible segment it refuses a deferred buffer)
+                vec = 16 // xs[0].data.element_size()
+                tile_ok = not any(x.cols % vec or x.ld % vec or d.stride(0) % vec or t.stride(0) % vec or _ptr(x.data) % 16 or _ptr(d) % 16 or _ptr(t) % 16
+                                  for x, d, (t, _) in zip(xs, dys, g))
                 self._dw_walkers(
-                    (lambda sites, offs: self.L.tc_dwconv_multi_plan(sg, n, Gn, self.dt, sites, offs)) if _DW_DEFER else None,
+                    (lambda sites, offs: self.L.tc_dwconv_multi_plan(sg, n, Gn, self.dt, sites, offs)) if _DW_DEFER and tile_ok else None,
                     lambda wsp, wsb: self.L.tc_dwconv_multi(sg, n, 3, int(add_input), acc, Gn, gs, wsp, wsb, self.dt, self.stream),
                     [(_ptr(w.grad), _ptr(b.grad) if b is not None else None, None, None, gs) for w, b in zip(ws, bs)])
                 return
