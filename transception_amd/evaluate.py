@@ -36,19 +36,27 @@ Evaluation at label resolution (`resample="scores"`; the reference carries it as
 argmax with order 0, the class scores -- the logits, or with `TTA` the summed probabilities -- are resampled bilinearly to the label's size and
 the argmax is taken there.  `tc_resample_scores` reads the small score maps once, interpolates in registers and writes only the uint8 label
 (csrc/resample.hip; include/transception_resample.h states the definition).  `resample="labels"`, the default everywhere, changes nothing.
+
+Surface metrics (`SurfaceMetrics`; the reference reports Dice and HD95 only): ASD in both directions, ASSD, the surface Dice at a tolerance
+and the full Hausdorff distance, with Jaccard, precision and recall from the counts.  `surface_metrics_device` runs `metrics_device`'s
+per-class loop and, on the same two distance maps of every class, tc_surface_stats: the directed count, sum of distances, count within
+the tolerance and largest squared distance (csrc/surface.hip; include/transception_surface.h states the definitions).
+`surface_metrics_host` is the same from scipy; `evaluate_volume_report` and `inference_report` are `evaluate_volume` and `inference` with
+these per-class dicts.  `evaluate_volume`, `inference` and the functions above them are what they were.
 """
 from __future__ import annotations
 
 import contextlib
 from dataclasses import dataclass
-from typing import Callable, List, Optional, Tuple
+from typing import Callable, Dict, List, Optional, Tuple, Union
 
 import math
 
 import numpy as np
 import torch
 
-from ._lib import TC_CC_LARGEST, TC_CC_MIN_VOXELS, TC_F32, TC_METRIC_SELECT_WORK_BYTES, TC_RESAMPLE_MAX_EXTENT, TC_TTA_TRANSPOSE, lib
+from ._lib import (TC_CC_LARGEST, TC_CC_MIN_VOXELS, TC_F32, TC_METRIC_SELECT_WORK_BYTES, TC_RESAMPLE_MAX_EXTENT, TC_SURFACE_WORK_BYTES,
+                   TC_TTA_TRANSPOSE, lib)
 from .engine import TC_DTYPE
 
 NO_CPU = "transception_amd.evaluate runs on MI355X only (no CPU fallback)"
@@ -204,19 +212,41 @@ def metrics_order_stats(pred: torch.Tensor, label: torch.Tensor, classes: int, v
     """int64 [2,classes,3] on the device: [0] the Dice counts, [1] (n, d2_lo, d2_hi) per class (tc_metric_select).  Allocates
     `metrics_scratch_bytes(pred.shape, classes, voxelspacing)`; the two distance maps are reused class by class.  Nothing is synchronised.
     With `voxelspacing` d2_lo and d2_hi are doubles (tc_metric_select_f64): read them with `result[1, :, 1:].view(torch.float64)`."""
+    return _class_loop(pred, label, classes, voxelspacing)[0]
+
+
+def _split_stats(both: torch.Tensor, classes: int):
+    """(res [2,classes,3], stats [classes,2,4]): the views of `_class_loop`'s flat int64 tensor, on the device or on the host."""
+    return both[:6 * classes].view(2, classes, 3), both[6 * classes:].view(classes, 2, 4)
+
+
+def _class_loop(pred: torch.Tensor, label: torch.Tensor, classes: int, voxelspacing=None, tol2: Optional[Tuple[float, ...]] = None):
+    """The per-class loop of the device metrics: (res, stats, both).  `res` is `metrics_order_stats`' tensor.  With `tol2` (one squared
+    tolerance per class 1..classes-1) every class's two distance maps, computed once, also feed tc_surface_stats / tc_surface_stats_f64,
+    and `stats` is its int64 [classes,2,4] output (include/transception_surface.h; class 0 stays zero); `res` and `stats` are then the
+    two views `_split_stats` takes of the flat int64 tensor `both`, so that one copy brings everything to the host.  Without `tol2`:
+    `stats` and `both` are None and nothing else runs.  Nothing is synchronised."""
     spaced = voxelspacing is not None
     spacing = _spacing3(voxelspacing, pred.dim())[3 - pred.dim():] if spaced else None
     sp, sg, counts = surfaces_counts(pred, label, classes)
     D, H, W = _shape3(pred.shape)
     dev = pred.device
     L, stream = lib(), torch.cuda.current_stream(dev).cuda_stream
+    stats = both = None
+    if tol2 is not None:
+        both = torch.zeros((6 + 8) * classes, dtype=torch.int64, device=dev)
+        res, stats = _split_stats(both, classes)
+        swork = torch.empty(TC_SURFACE_WORK_BYTES // 8, dtype=torch.int64, device=dev)
+        surface_entry = L.tc_surface_stats_f64 if spaced else L.tc_surface_stats
     if spaced:
         work = torch.empty(TC_METRIC_SELECT_WORK_BYTES, dtype=torch.uint8, device=dev)
-        res = torch.zeros((2, classes, 3), dtype=torch.int64, device=dev)             # class 0 is never selected: (0, 0.0, 0.0)
+        if stats is None:
+            res = torch.zeros((2, classes, 3), dtype=torch.int64, device=dev)         # class 0 is never selected: (0, 0.0, 0.0)
     else:
         nbins = metrics_hist_bins(pred.shape)
         hist = torch.zeros((classes, nbins), dtype=torch.int32, device=dev)           # uint32 to the library
-        res = torch.empty((2, classes, 3), dtype=torch.int64, device=dev)             # tc_metric_select writes every class
+        if stats is None:
+            res = torch.empty((2, classes, 3), dtype=torch.int64, device=dev)         # tc_metric_select writes every class
     dp, dg = (torch.empty(pred.shape, dtype=torch.float64 if spaced else torch.int32, device=dev) for _ in range(2))
     res[0] = counts
     for k in range(1, classes):
@@ -227,9 +257,12 @@ def metrics_order_stats(pred: torch.Tensor, label: torch.Tensor, classes: int, v
                                    res[1].data_ptr(), stream)
         else:
             L.tc_metric_hist(sp.data_ptr(), sg.data_ptr(), dp.data_ptr(), dg.data_ptr(), k, hist.data_ptr(), nbins, classes, D, H, W, stream)
+        if stats is not None:
+            surface_entry(sp.data_ptr(), sg.data_ptr(), dp.data_ptr(), dg.data_ptr(), k, classes, D, H, W, tol2[k - 1], swork.data_ptr(),
+                          stats.data_ptr(), stream)
     if not spaced:
         L.tc_metric_select(hist.data_ptr(), nbins, classes, res[1].data_ptr(), stream)
-    return res
+    return res, stats, both
 
 
 def _order_stats_to_host(res: torch.Tensor, spaced: bool):
@@ -260,6 +293,134 @@ def hd95_device(result: torch.Tensor, reference: torch.Tensor, voxelspacing=None
     if counts[1][1] == 0 or counts[1][2] == 0:
         raise RuntimeError("surface distances need non-empty masks")
     return hd95_from_order_stats(*sel[1])
+
+
+def _is_real(v) -> bool:
+    return not isinstance(v, (bool, np.bool_)) and isinstance(v, (int, float, np.integer, np.floating))
+
+
+@dataclass(frozen=True)
+class SurfaceMetrics:
+    """The surface metrics of the evaluation beside Dice and HD95 (include/transception_surface.h has the definitions): ASD in both
+    directions, ASSD, the full Hausdorff distance and the surface Dice (NSD) at `nsd_tolerance` -- one finite number >= 0 for every class, or
+    a sequence with one per class 1..classes-1 (organ-specific tolerances), in the units of `voxelspacing` (voxels without it).  The
+    tolerance is applied to squared distances: a surface voxel counts when d^2 <= tolerance * tolerance (the product formed once in fp64).
+    The length of a sequence is checked where `classes` is known (`tolerances`)."""
+    nsd_tolerance: Union[float, Tuple[float, ...]] = 1.0
+
+    def __post_init__(self):
+        t = self.nsd_tolerance
+        if isinstance(t, (str, bytes, dict, set)) or (not _is_real(t) and not hasattr(t, "__iter__")):
+            raise ValueError(f"nsd_tolerance must be a number >= 0 or a sequence of them, got {t!r}")
+        values = (t,) if _is_real(t) else tuple(t)
+        if not values or not all(_is_real(v) and math.isfinite(v) and v >= 0 for v in values):
+            raise ValueError(f"nsd_tolerance must be finite numbers >= 0 (no bool, no NaN), got {t!r}")
+        object.__setattr__(self, "nsd_tolerance", float(t) if _is_real(t) else tuple(float(v) for v in values))
+
+    def tolerances(self, classes: int) -> Tuple[float, ...]:
+        """One tolerance per class 1..classes-1."""
+        t = self.nsd_tolerance
+        if not isinstance(t, tuple):
+            return (t,) * (classes - 1)
+        if len(t) != classes - 1:
+            raise ValueError(f"nsd_tolerance has {len(t)} values for the {classes - 1} classes 1..{classes - 1}")
+        return t
+
+
+def _surface_tolerances(surface, classes: int) -> Tuple[float, ...]:
+    """The squared tolerances tau * tau per class 1..classes-1 of a `SurfaceMetrics`: a ValueError for anything else, before anything runs."""
+    if not isinstance(surface, SurfaceMetrics):
+        raise ValueError(f"surface must be a SurfaceMetrics, got {surface!r}")
+    if isinstance(classes, bool) or not isinstance(classes, (int, np.integer)) or not 2 <= classes <= 16:
+        raise ValueError("classes must be in 2..16")
+    return tuple(t * t for t in surface.tolerances(int(classes)))
+
+
+# what `surface_metrics_device` and `surface_metrics_host` return per class, beside `defined`
+SURFACE_KEYS = ("dice", "jaccard", "precision", "recall", "hd95", "hd", "asd_pred", "asd_gt", "assd", "nsd")
+
+
+def _percase_surface(inter: int, p: int, g: int, hd95_fn: Callable[[], float], records_fn: Callable[[], tuple]) -> Dict[str, object]:
+    """The reference's rule (`_percase`, utils.py:50-60) extended to the surface metrics, for one class of one volume from |P&G|, |P|, |G|
+    and, asked for only when both masks are non-empty, the two directed records (n, sum, within, max) of transception_surface.h.
+    Both non-empty: the measured values, defined=True.  Only the prediction non-empty: the reference's own (1, 0) -- every overlap score and
+    the surface Dice 1, every distance 0 --, defined=False.  Otherwise everything 0, defined=False."""
+    dice, h95 = _percase(inter, p, g, hd95_fn)
+    if p > 0 and g > 0:
+        (n0, s0, w0, m0), (n1, s1, w1, m1) = records_fn()
+        asd_pred, asd_gt = s0 / n0, s1 / n1
+        values = (dice, inter / (p + g - inter), inter / p, inter / g, h95, math.sqrt(max(m0, m1)), asd_pred, asd_gt,
+                  (asd_pred + asd_gt) / 2, (w0 + w1) / (n0 + n1))          # assd: medpy's mean of the directed means, not the pooled mean
+    else:
+        values = (dice,) * 4 + (0.0,) * 5 + (dice,)                        # dice is 1 or 0 here
+    out = {key: float(v) for key, v in zip(SURFACE_KEYS, values)}
+    out["defined"] = bool(p > 0 and g > 0)
+    return out
+
+
+def surface_metrics_device(pred: torch.Tensor, label: torch.Tensor, classes: int = 9, voxelspacing=None,
+                           surface: SurfaceMetrics = SurfaceMetrics()) -> List[Dict[str, object]]:
+    """One dict per class 1..classes-1 of two uint8 CUDA label volumes ([D,H,W], or [H,W]: true 2-D), keys SURFACE_KEYS and `defined`
+    (`_percase_surface` has the rule).  `dice` and `hd95` are `metrics_device`'s, from the same launches and expressions; jaccard, precision
+    and recall come from the same int64 counts; hd, asd_pred, asd_gt, assd and nsd from the directed statistics of tc_surface_stats /
+    tc_surface_stats_f64 (csrc/surface.hip), one more pass per class over the surface and distance maps `metrics_device` has in memory.
+    Scratch beside `metrics_scratch_bytes`: TC_SURFACE_WORK_BYTES and the [classes,2,4] result.  One copy of 14 * classes integers comes
+    back, and nothing is synchronised before it."""
+    tol2 = _surface_tolerances(surface, classes)
+    spaced = voxelspacing is not None
+    res, stats = _split_stats(_class_loop(pred, label, classes, voxelspacing, tol2)[2].cpu(), classes)
+    counts, sel = _order_stats_to_host(res, spaced)
+    rec = stats.tolist()
+    sums = stats[:, :, 1].contiguous().view(torch.float64).tolist()
+    maxs = stats[:, :, 3].contiguous().view(torch.float64).tolist() if spaced else None
+    out = []
+    for k in range(1, classes):
+        (inter, p, g), (n, lo, hi) = counts[k], sel[k]
+        records = tuple((rec[k][i][0], sums[k][i], rec[k][i][2], maxs[k][i] if spaced else rec[k][i][3]) for i in range(2))
+        out.append(_percase_surface(inter, p, g, lambda: hd95_from_order_stats(n, lo, hi), lambda: records))
+    return out
+
+
+def surface_stats_host(pred: np.ndarray, gt: np.ndarray, voxelspacing=None, tol2: float = 1.0) -> tuple:
+    """The two directed records ((n, sum, within, max) from the surface of `pred` to that of `gt`, then the reverse) of two non-empty
+    boolean masks, as transception_surface.h defines them, from scipy.  The squared distances come from the feature transform: the index
+    of the nearest surface voxel, then d2 = sum over the axes, in axis order, of (s_a (i_a - j_a))^2 -- exact integers (and an int `max`)
+    with unit spacing, float64 with `voxelspacing`.  `sum` is math.fsum of the square roots; `within` counts d2 <= tol2."""
+    from scipy.ndimage import binary_erosion, distance_transform_edt, generate_binary_structure
+    pred, gt = np.atleast_1d(np.asarray(pred) > 0), np.atleast_1d(np.asarray(gt) > 0)
+    if not pred.any() or not gt.any():
+        raise RuntimeError("surface distances need non-empty masks")
+    spacing = None if voxelspacing is None else _spacing3(voxelspacing, pred.ndim)[3 - pred.ndim:]
+    footprint = generate_binary_structure(pred.ndim, 1)
+    borders = [m ^ binary_erosion(m, structure=footprint, iterations=1) for m in (pred, gt)]
+    records = []
+    for src, dst in ((borders[0], borders[1]), (borders[1], borders[0])):
+        nearest = distance_transform_edt(~dst, sampling=spacing, return_distances=False, return_indices=True)
+        d2 = None
+        for a, pos in enumerate(np.nonzero(src)):
+            step = nearest[a][src].astype(np.int64) - pos
+            term = step * step if spacing is None else (spacing[a] * step) ** 2
+            d2 = term if d2 is None else d2 + term
+        d2f = d2.astype(np.float64)
+        records.append((int(d2.size), math.fsum(np.sqrt(d2f).tolist()), int(np.count_nonzero(d2f <= tol2)),
+                        int(d2.max()) if spacing is None else float(d2.max())))
+    return tuple(records)
+
+
+def surface_metrics_host(pred: np.ndarray, label: np.ndarray, classes: int = 9, voxelspacing=None,
+                         surface: SurfaceMetrics = SurfaceMetrics()) -> List[Dict[str, object]]:
+    """`surface_metrics_device`'s structure from scipy, for the host metric path: `dice` and `hd95` are `calculate_metric_percase`'s, the
+    rest comes from `surface_stats_host`.  With unit spacing the squared distances are exact integers and the tolerance test is the device's."""
+    tol2 = _surface_tolerances(surface, classes)
+    pred, label = np.asarray(pred), np.asarray(label)
+    if pred.shape != label.shape or pred.ndim not in (2, 3):
+        raise ValueError("surface metrics take two label volumes [D,H,W] or [H,W] of one shape")
+    out = []
+    for k in range(1, classes):
+        P, G = pred == k, label == k
+        out.append(_percase_surface(int(np.logical_and(P, G).sum()), int(P.sum()), int(G.sum()), lambda: hd95(P, G, voxelspacing),
+                                    lambda: surface_stats_host(P, G, voxelspacing, tol2[k - 1])))       # the first two as calculate_metric_percase
+    return out
 
 
 POST_MODES = ("largest", "min_voxels")
@@ -409,7 +570,8 @@ RESAMPLE_MODES = ("labels", "scores")
 # what an option of the evaluation may be: `_check_options` and `TrainConfig` apply these, each with its own message
 VALID_OPTION = {"postprocess": lambda v: v is None or isinstance(v, PostProcess),
                 "tta": lambda v: v is None or isinstance(v, TTA),
-                "resample": lambda v: isinstance(v, str) and v in RESAMPLE_MODES}
+                "resample": lambda v: isinstance(v, str) and v in RESAMPLE_MODES,
+                "surface": lambda v: v is None or isinstance(v, SurfaceMetrics)}
 
 
 def _check_tta(tta, shape=None) -> None:
@@ -667,16 +829,37 @@ def evaluate_volume(model, image: np.ndarray, label: np.ndarray, classes: int = 
     `label`'s size; `postprocess` and both metric paths follow as before.  Without a resize both values run the same calls; "scores" with
     `host_zoom=True` is a ValueError."""
     _check_options(postprocess, tta, resample, host_zoom, tuple(patch_size))
+    pred = _predict_volume(model, image, classes, patch_size, batch, host_zoom, device_metrics, postprocess, tta, resample)
+    return (_score_device if device_metrics else _score_host)(pred, label, classes, with_hd95, voxelspacing)
+
+
+def _predict_volume(model, image: np.ndarray, classes, patch_size, batch, host_zoom, device_metrics, postprocess, tta, resample):
+    """The prediction of `evaluate_volume` and `evaluate_volume_report` at `image`'s resolution, where the metric path wants it: a uint8 CUDA
+    tensor with `device_metrics`, else a NumPy array."""
     dev = next(model.parameters()).device
     if device_metrics and dev.type != "cuda":
         raise RuntimeError(NO_CPU)
     if host_zoom:
         on_host = _predict_volume_host(model, image, dev, classes, patch_size, batch, postprocess, tta)
-        pred = torch.from_numpy(on_host).to(dev) if device_metrics else on_host
-    else:
-        on_device = _predict_volume_device(model, image, dev, classes, patch_size, batch, postprocess, tta, resample)
-        pred = on_device if device_metrics else on_device.cpu().numpy()
-    return (_score_device if device_metrics else _score_host)(pred, label, classes, with_hd95, voxelspacing)
+        return torch.from_numpy(on_host).to(dev) if device_metrics else on_host
+    on_device = _predict_volume_device(model, image, dev, classes, patch_size, batch, postprocess, tta, resample)
+    return on_device if device_metrics else on_device.cpu().numpy()
+
+
+@torch.no_grad()
+def evaluate_volume_report(model, image: np.ndarray, label: np.ndarray, classes: int = 9, patch_size=(224, 224), batch: int = 16,
+                           host_zoom: bool = False, device_metrics: bool = False, voxelspacing=None, postprocess: Optional[PostProcess] = None,
+                           tta: Optional[TTA] = None, *, resample: str = "labels", surface: SurfaceMetrics = SurfaceMetrics()):
+    """`evaluate_volume`'s prediction of one [D,H,W] volume, scored with the surface metrics as well: one dict per class 1..classes-1 with the
+    keys SURFACE_KEYS and `defined`, from `surface_metrics_device` (`device_metrics=True`: the prediction stays on the GPU) or
+    `surface_metrics_host`.  `dice` and `hd95` are what `evaluate_volume(..., with_hd95=True)` returns; every other argument is its own."""
+    _check_options(postprocess, tta, resample, host_zoom, tuple(patch_size))
+    _surface_tolerances(surface, classes)
+    pred = _predict_volume(model, image, classes, patch_size, batch, host_zoom, device_metrics, postprocess, tta, resample)
+    if not device_metrics:
+        return surface_metrics_host(pred, label, classes, voxelspacing, surface)
+    label_t = torch.from_numpy(np.ascontiguousarray(label).astype(np.uint8)).to(pred.device)
+    return surface_metrics_device(pred, label_t, classes, voxelspacing, surface)
 
 
 def inference(model, volumes, classes: int = 9, img_size: int = 224, batch: int = 16, log=None,
@@ -704,3 +887,40 @@ def inference(model, volumes, classes: int = 9, img_size: int = 224, batch: int 
         log('Testing performance in best val model: mean_dice : %f mean_hd95 : %f' % (performance, mean_hd95))
     return performance, mean_hd95
 
+
+
+def inference_report(model, volumes, classes: int = 9, img_size: int = 224, batch: int = 16, log=None,
+                     device_metrics: bool = False, voxelspacing=None, postprocess: Optional[PostProcess] = None,
+                     tta: Optional[TTA] = None, *, resample: str = "labels", surface: SurfaceMetrics = SurfaceMetrics()) -> dict:
+    """`inference` with the surface metrics: `evaluate_volume_report` per volume, and
+        {"cases": [{"name", "classes": [dict per class]}], "mean": {key: [per class]}, "overall": {key: float}, "n_defined": [per class]}
+    over the keys SURFACE_KEYS.  The means are taken over ALL cases with the values of the per-case rule (`_percase_surface`), as
+    `inference` takes them, in its arithmetic: (overall["dice"], overall["hd95"]) is the pair `inference` returns.  `n_defined` counts, per
+    class, the cases in which both masks were non-empty -- the cases whose distances were measured."""
+    _check_options(postprocess, tta, resample)
+    _surface_tolerances(surface, classes)
+    cases, total = [], 0.0
+    for i, (image, label, name) in enumerate(volumes):
+        per_class = evaluate_volume_report(model, np.asarray(image), np.asarray(label), classes, (img_size, img_size), batch,
+                                           device_metrics=device_metrics, voxelspacing=voxelspacing, postprocess=postprocess, tta=tta,
+                                           resample=resample, surface=surface)
+        m = np.array([[c[key] for key in SURFACE_KEYS] for c in per_class])
+        total = total + m
+        cases.append({"name": name, "classes": per_class})
+        if log:
+            case = dict(zip(SURFACE_KEYS, m.mean(axis=0)))
+            log(' idx %d case %s mean_dice %f mean_hd95 %f' % (i, name, case["dice"], case["hd95"]))
+            log(' idx %d case %s mean_assd %f mean_hd %f mean_nsd %f' % (i, name, case["assd"], case["hd"], case["nsd"]))
+    if not cases:
+        raise ValueError("inference_report() needs at least one volume")
+    total = total / len(cases)
+    overall = {key: float(v) for key, v in zip(SURFACE_KEYS, total.mean(axis=0))}
+    if log:
+        for k in range(1, classes):
+            row = dict(zip(SURFACE_KEYS, total[k - 1]))
+            log('Mean class %d mean_dice %f mean_hd95 %f' % (k, row["dice"], row["hd95"]))
+            log('Mean class %d mean_assd %f mean_hd %f mean_nsd %f' % (k, row["assd"], row["hd"], row["nsd"]))
+        log('Testing performance in best val model: mean_dice : %f mean_hd95 : %f' % (overall["dice"], overall["hd95"]))
+        log('Testing performance in best val model: mean_assd : %f mean_hd : %f mean_nsd : %f' % (overall["assd"], overall["hd"], overall["nsd"]))
+    return {"cases": cases, "mean": {key: total[:, j].tolist() for j, key in enumerate(SURFACE_KEYS)}, "overall": overall,
+            "n_defined": [sum(bool(c["classes"][k]["defined"]) for c in cases) for k in range(classes - 1)]}

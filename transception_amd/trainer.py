@@ -28,7 +28,7 @@ import torch
 import torch.distributed as dist
 
 from .data import DeviceLoader, SynapseSlices
-from .evaluate import RESAMPLE_MODES, TTA, VALID_OPTION, PostProcess, inference
+from .evaluate import RESAMPLE_MODES, SURFACE_KEYS, TTA, VALID_OPTION, PostProcess, SurfaceMetrics, inference, inference_report
 from .train import (DynamicLossScale, FusedAdamW, FusedSGD, GraphedStep, SegLoss, WeightEMA, check_class_weights, check_ema_decay,
                     check_focal_tversky, check_ignore_index, cosine_lr, train_step)
 
@@ -98,6 +98,10 @@ class TrainConfig:
             raise ValueError(f"tta must be None or an evaluate.TTA, got {self.tta!r}")
         if not VALID_OPTION["resample"](self.resample):
             raise ValueError(f"resample must be one of {RESAMPLE_MODES}, got {self.resample!r}")
+        if not VALID_OPTION["surface"](self.surface_metrics):
+            raise ValueError(f"surface_metrics must be None or an evaluate.SurfaceMetrics, got {self.surface_metrics!r}")
+        if self.surface_metrics is not None:
+            self.surface_metrics.tolerances(self.num_classes)         # one tolerance, or one per class 1..num_classes-1
         check_focal_tversky(self.focal_gamma, self.overlap, self.tversky_alpha, self.tversky_beta)
         make_loss_scale(self.loss_scale)
         check_class_weights("class_weights", self.class_weights, self.num_classes, need_positive=True)
@@ -111,11 +115,14 @@ class TrainConfig:
 # order of the signature, which ends with `resample`.  What follows from that: `==` compares the fields only, so two configurations that differ
 # in these options alone compare equal, and `dataclasses.replace` / `asdict` do not carry them (a replaced copy has the defaults: pass them
 # again).  `repr` does show them, after the fields.
+#   surface_metrics: an evaluate.SurfaceMetrics -- the evaluation after a checkpoint then runs `inference_report` and `hist["surface"]` collects
+#     its overall ASD / ASSD / HD / surface Dice beside `hist["dice"]` and `hist["hd95"]`; None: `inference`, as before;
 #   focal_gamma, overlap, tversky_alpha, tversky_beta: the loss (train.SegLoss has the definition) -- the focal exponent of the
 #     cross-entropy, "dice" or "tversky" for the overlap term, and the Tversky weights of false positives and false negatives;
 #   resample: what the evaluation resamples to the label's size (evaluate.evaluate_volume: "labels", the reference's order-0 zoom of the
 #     argmax, or "scores", bilinear class scores and then the argmax).
-KEYWORD_OPTIONS = (("focal_gamma", float, 0.0), ("overlap", str, "dice"), ("tversky_alpha", float, 0.5), ("tversky_beta", float, 0.5),
+KEYWORD_OPTIONS = (("surface_metrics", Optional[SurfaceMetrics], None),
+                   ("focal_gamma", float, 0.0), ("overlap", str, "dice"), ("tversky_alpha", float, 0.5), ("tversky_beta", float, 0.5),
                    ("resample", str, "labels"))
 
 
@@ -238,6 +245,8 @@ def trainer_synapse(cfg: TrainConfig, model, snapshot_path: str, volumes: Option
         hist["ema_checkpoints"] = []
     if scaler is not None:
         hist["loss_scale"] = []                                   # the scale after the step of each log line
+    if cfg.surface_metrics is not None:
+        hist["surface"] = []                                      # per evaluation: inference_report's `overall`, {key: mean over cases and classes}
     step = None
     iter_num = 0
     for x, y in loader:
@@ -288,20 +297,28 @@ def trainer_synapse(cfg: TrainConfig, model, snapshot_path: str, volumes: Option
                         for buf in model.buffers():
                             dist.broadcast(buf, src=0, group=group)
                         vols = vols[rank::world]
-                    res = torch.zeros(3, dtype=torch.float64, device=dev)
+                    res = torch.zeros(3 + (len(SURFACE_KEYS) if cfg.surface_metrics is not None else 0), dtype=torch.float64, device=dev)
                     if vols:
                         if rank == 0:
                             log(f"Running Inference after epoch {epoch_num}")
                         # the averaged weights are swapped into the arenas for the evaluation and out again (every rank holds the same average)
                         with ema.swapped() if ema is not None and cfg.ema_eval else contextlib.nullcontext():
-                            mean_dice, mean_hd95 = inference(model, vols, cfg.num_classes, cfg.img_size, log=log, device_metrics=cfg.device_metrics,
-                                                            voxelspacing=cfg.voxelspacing, postprocess=cfg.postprocess, tta=cfg.tta, resample=cfg.resample)
+                            options = dict(log=log, device_metrics=cfg.device_metrics, voxelspacing=cfg.voxelspacing, postprocess=cfg.postprocess,
+                                           tta=cfg.tta, resample=cfg.resample)
+                            if cfg.surface_metrics is None:
+                                mean_dice, mean_hd95 = inference(model, vols, cfg.num_classes, cfg.img_size, **options)
+                            else:
+                                overall = inference_report(model, vols, cfg.num_classes, cfg.img_size, surface=cfg.surface_metrics, **options)["overall"]
+                                mean_dice, mean_hd95 = overall["dice"], overall["hd95"]
+                                res[3:] = torch.tensor([overall[key] * len(vols) for key in SURFACE_KEYS], dtype=torch.float64)
                         res[0], res[1], res[2] = mean_dice * len(vols), mean_hd95 * len(vols), len(vols)
                         model.train()
                     if distributed:
                         dist.all_reduce(res, group=group)
                     hist["dice"].append(float(res[0] / res[2].clamp(min=1)))
                     hist["hd95"].append(float(res[1] / res[2].clamp(min=1)))
+                    if cfg.surface_metrics is not None:           # all-reduced like the two means above
+                        hist["surface"].append(dict(zip(SURFACE_KEYS, (res[3:] / res[2].clamp(min=1)).tolist())))
     hist["iterations"] = iter_num
     if isinstance(opt, FusedAdamW):
         hist["optimizer_step"] = opt.device_step()                # updates applied, as the device counted them: iterations minus skipped
