@@ -157,9 +157,11 @@ int tc_layernorm_bwd_defer(const void* dy, int lddy, const void* x, int ldx, con
                            const float* mean, const float* rstd, void* dx, int lddx, const void* dres, int ldres,
                            float* dgamma, float* dbeta, int rows, int C, int act, int groups, long long pstride,
                            float* part, long long part_floats, int dtype, void* stream);
+/* (a site is what tc_layernorm_bwd_defer parks: C % 4 == 0, C <= 1024, nblk >= 1 -- anything else is TC_ERR_ARG before the launch) */
 int tc_layernorm_fold(const TcLnFold* sites, int n, void* stream);
 /* dgamma / dbeta may both be NULL above (dx only); this entry then produces them as a row-parallel column reduction, so the
- * host can run it on a second stream beside the activation-gradient chain. */
+ * host can run it on a second stream beside the activation-gradient chain.  Same argument tests as tc_layernorm_bwd (C % 4, C <= 2048,
+ * act TC_ACT_NONE or TC_ACT_GELU). */
 int tc_layernorm_bwd_params(const void* dy, int lddy, const void* x, int ldx, const void* gamma, const void* beta,
                             const float* mean, const float* rstd, float* dgamma, float* dbeta, int rows, int C, int act,
                             int groups, long long pstride, int dtype, void* stream);

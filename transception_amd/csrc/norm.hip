@@ -1018,7 +1018,7 @@ static int ln_bwd_impl(const void* dy, int lddy, const void* x, int ldx, const v
                        float* dgamma, float* dbeta, int rows, int C, int act, int groups, long long pstride,
                        float* scratch, long long scratch_floats, int dtype, void* stream, LnMap map, float* defer_part = nullptr) {
     if (!dy || !x || !gamma || !beta || !mean || !rstd || !dx || (!dgamma != !dbeta) || rows <= 0 || groups < 1 || C <= 0 || (C & 3) ||
-        C > LN_MAXC || (ldx & 3) || (lddy & 3) || (lddx & 3) || (dres && (ldres & 3)))
+        C > LN_MAXC || (ldx & 3) || (lddy & 3) || (lddx & 3) || (dres && (ldres & 3)) || (act != TC_ACT_NONE && act != TC_ACT_GELU))
         return TC_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
     const int quads = C >> 2;
@@ -1124,7 +1124,7 @@ extern "C" int tc_layernorm_fold(const TcLnFold* sites, int n, void* stream) {
     int blk = 0;
     for (int i = 0; i < n; ++i) {
         const TcLnFold& t = sites[i];
-        if (!t.part || !t.dgamma || !t.dbeta || t.nblk < 1 || t.C <= 0 || t.groups < 1) return TC_ERR_ARG;
+        if (!t.part || !t.dgamma || !t.dbeta || t.nblk < 1 || t.C <= 0 || (t.C & 3) || t.C > 1024 || t.groups < 1) return TC_ERR_ARG;   // what tc_layernorm_bwd_defer parks
         const int rsplit = (t.nblk + LN_FOLD_ROWS - 1) / LN_FOLD_ROWS;
         q.s[i] = LnFoldSite{t.part, t.dgamma, t.dbeta, t.pstride, t.nblk, t.C, t.groups, blk, rsplit};
         blk += t.groups * ((2 * t.C + 63) / 64) * rsplit;
@@ -1141,8 +1141,8 @@ extern "C" long long tc_layernorm_bwd_scratch_floats(int rows, int C, int groups
 extern "C" int tc_layernorm_bwd_params(const void* dy, int lddy, const void* x, int ldx, const void* gamma, const void* beta,
                                        const float* mean, const float* rstd, float* dgamma, float* dbeta, int rows, int C, int act,
                                        int groups, long long pstride, int dtype, void* stream) {
-    if (!dy || !x || !gamma || !beta || !mean || !rstd || !dgamma || !dbeta || rows <= 0 || groups < 1 || C <= 0 || (C & 3) || (ldx & 3) ||
-        (lddy & 3))
+    if (!dy || !x || !gamma || !beta || !mean || !rstd || !dgamma || !dbeta || rows <= 0 || groups < 1 || C <= 0 || (C & 3) || C > LN_MAXC ||
+        (ldx & 3) || (lddy & 3) || (act != TC_ACT_NONE && act != TC_ACT_GELU))
         return TC_ERR_ARG;
     dim3 grid(tc_blocks(rows, 16 * 8, 128), (C + 63) / 64, groups);
     TC_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((ln_param_grad_kernel<T>), grid, dim3(256), 0, (hipStream_t)stream, (const T*)dy, lddy,
