@@ -35,6 +35,7 @@ SIDE_HEADERS = (SideHeader("POST", "transception_post.h", "TC_POST_ABI_VERSION",
                 SideHeader("RESAMPLE", "transception_resample.h", "TC_RESAMPLE_ABI_VERSION", "tc_resample_abi_version", "score resampling"),
                 SideHeader("BRIDGE", "transception_bridge.h", "TC_BRIDGE_ABI_VERSION", "tc_bridge_abi_version", "bridge LayerNorm"),
                 SideHeader("SURFACE", "transception_surface.h", "TC_SURFACE_ABI_VERSION", "tc_surface_abi_version", "surface metrics"),
+                SideHeader("UNCERT", "transception_uncertainty.h", "TC_UNCERT_ABI_VERSION", "tc_uncert_abi_version", "uncertainty / calibration"),
                 SideHeader("LOSS", "transception_loss.h", "TC_LOSS_ABI_VERSION", "tc_loss_abi_version", "focal / Tversky loss"))
 
 SCALARS = {"int": C.c_int, "long long": C.c_longlong, "float": C.c_float, "double": C.c_double,

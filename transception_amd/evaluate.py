@@ -43,20 +43,30 @@ per-class loop and, on the same two distance maps of every class, tc_surface_sta
 the tolerance and largest squared distance (csrc/surface.hip; include/transception_surface.h states the definitions).
 `surface_metrics_host` is the same from scipy; `evaluate_volume_report` and `inference_report` are `evaluate_volume` and `inference` with
 these per-class dicts.  `evaluate_volume`, `inference` and the functions above them are what they were.
+
+Uncertainty and calibration (`predict_uncertainty`, `Calibration`; the reference reduces its scores to an argmax): a second use of the fp32
+probability accumulator of the views.  `tc_uncert_maps` reads class scores once -- a view's logits, or the summed probabilities -- and writes
+the normalised predictive entropy, the maximum-probability confidence, the label and, from the sum of the views' own entropies, the mutual
+information between the views.  `tc_calib_stats` reads scores and labels once and leaves the reliability table, the NLL and Brier sums and
+the per-predicted-class entropy sums as 8-byte slots, from which `calibration_from_stats` forms ECE, MCE, NLL, Brier and accuracy
+(csrc/uncertainty.hip; include/transception_uncertainty.h states the definitions).  Calibration is measured where the scores live, at the
+network size, against labels brought there by `zoom_labels`; `calibration_host` is the same from NumPy in float64.  `evaluate_volume_calibration`
+and `inference_calibration` are entries of their own: nothing above runs them, and `TrainConfig.calibration=None`, the default, changes nothing.
 """
 from __future__ import annotations
 
 import contextlib
 from dataclasses import dataclass
-from typing import Callable, Dict, List, Optional, Tuple, Union
+from typing import Callable, Dict, List, NamedTuple, Optional, Tuple, Union
 
 import math
 
 import numpy as np
 import torch
 
-from ._lib import (TC_CC_LARGEST, TC_CC_MIN_VOXELS, TC_F32, TC_METRIC_SELECT_WORK_BYTES, TC_RESAMPLE_MAX_EXTENT, TC_SURFACE_WORK_BYTES,
-                   TC_TTA_TRANSPOSE, lib)
+from ._lib import (TC_CALIB_FOREGROUND, TC_CALIB_MAX_BINS, TC_CC_LARGEST, TC_CC_MIN_VOXELS, TC_F32, TC_METRIC_SELECT_WORK_BYTES,
+                   TC_RESAMPLE_MAX_EXTENT, TC_SURFACE_WORK_BYTES, TC_TTA_FLIP_H, TC_TTA_FLIP_W, TC_TTA_TRANSPOSE, TC_UNCERT_LOGITS,
+                   TC_UNCERT_PROB_SUMS, lib)
 from .engine import TC_DTYPE
 
 NO_CPU = "transception_amd.evaluate runs on MI355X only (no CPU fallback)"
@@ -571,7 +581,8 @@ RESAMPLE_MODES = ("labels", "scores")
 VALID_OPTION = {"postprocess": lambda v: v is None or isinstance(v, PostProcess),
                 "tta": lambda v: v is None or isinstance(v, TTA),
                 "resample": lambda v: isinstance(v, str) and v in RESAMPLE_MODES,
-                "surface": lambda v: v is None or isinstance(v, SurfaceMetrics)}
+                "surface": lambda v: v is None or isinstance(v, SurfaceMetrics),
+                "calibration": lambda v: v is None or isinstance(v, Calibration)}
 
 
 def _check_tta(tta, shape=None) -> None:
@@ -663,14 +674,34 @@ def _eval_mode(model):
         model.train(was_training)
 
 
+def _view_entropy_add(L, lg: torch.Tensor, v: int, first: bool, ves: torch.Tensor, buf: torch.Tensor, stream) -> None:
+    """The normalised entropy of one view's logits (tc_uncert_maps on the logits, in view coordinates, into the flat fp32 scratch `buf`),
+    brought back to the un-transformed position -- the transpose undone, then the flips: plumbing on one [n,H,W] map -- and written (`first`)
+    or added into `ves`."""
+    n, C, Hv, Wv = lg.shape
+    h = buf[:n * Hv * Wv].view(n, Hv, Wv)
+    L.tc_uncert_maps(lg.data_ptr(), TC_DTYPE[lg.dtype], TC_UNCERT_LOGITS, 1.0, None, h.data_ptr(), None, None, None, n, C, Hv, Wv, stream)
+    if v & TC_TTA_TRANSPOSE:
+        h = h.transpose(-2, -1)
+    dims = [d for d, bit in ((-2, TC_TTA_FLIP_H), (-1, TC_TTA_FLIP_W)) if v & bit]
+    if dims:
+        h = h.flip(dims)
+    if first:
+        ves.copy_(h)
+    else:
+        ves.add_(h)
+
+
 def _predict(model, slices: torch.Tensor, batch: int, views: Optional[Tuple[int, ...]], out_size: Optional[Tuple[int, int]],
-             labels: bool) -> torch.Tensor:
+             labels: bool, ves: Optional[torch.Tensor] = None) -> torch.Tensor:
     """The one batch loop of `predict_slices` (`labels`: uint8 [N,X,Y]) and `predict_probs` (else: the fp32 [N,C,X,Y] sums over the views), `model` in
     eval mode; (X, Y) is `out_size`, and None or (H, W) is the scores' own size.  How a batch's class scores are made: `views` None (labels
     only) -- the torch normalisation, and the scores are the logits; else per view, in the order given, tc_tta_view, `model`,
     tc_tta_accumulate.  Where they go: at their own size the labels come from tc_argmax_counts or from the last tc_tta_accumulate, and the
     sums are added in place in the returned tensor; at another size tc_resample_scores writes either.  One fp32 [batch,C,H,W] accumulator,
-    allocated at the first logits, holds the views that do not go into the result: none for a single view that writes labels at its own size."""
+    allocated at the first logits, holds the views that do not go into the result: none for a single view that writes labels at its own size.
+    `ves` (`predict_uncertainty` alone; fp32 [N,H,W], with `views`): every view's own normalised entropy is summed into it at the un-transformed
+    position (`_view_entropy_add`: one more launch per view); None, as everywhere else: nothing more runs."""
     if not slices.is_cuda:
         raise RuntimeError(NO_CPU)
     N, H, W = slices.shape
@@ -678,7 +709,7 @@ def _predict(model, slices: torch.Tensor, batch: int, views: Optional[Tuple[int,
         out_size = None
     in_place = out_size is None and not labels                   # the views are added into the returned sums themselves
     need_acc = views is not None and not in_place and (out_size is not None or len(views) > 1)
-    L, stream, acc = lib(), torch.cuda.current_stream(slices.device).cuda_stream, None
+    L, stream, acc, hbuf = lib(), torch.cuda.current_stream(slices.device).cuda_stream, None, None
     out = torch.empty((N,) + (out_size or (H, W)), dtype=torch.uint8, device=slices.device) if labels else None
     with _eval_mode(model):
         for i in range(0, N, batch):
@@ -699,6 +730,10 @@ def _predict(model, slices: torch.Tensor, batch: int, views: Optional[Tuple[int,
                     last = labels and out_size is None and j == len(views) - 1
                     L.tc_tta_accumulate(lg.data_ptr(), TC_DTYPE[lg.dtype], sums.data_ptr() if sums is not None else None,
                                         out[i:i + n].data_ptr() if last else None, n, C, H, W, v, int(j == 0), stream)
+                    if ves is not None:
+                        if hbuf is None:                         # one view's entropy map: allocated once, as the accumulator is
+                            hbuf = torch.empty(batch * H * W, dtype=torch.float32, device=src.device)
+                        _view_entropy_add(L, lg, v, j == 0, ves[i:i + n], hbuf, stream)
                 scores = acc[:n] if out_size is not None else None
             if out_size is not None:
                 resample_scores(scores, out_size, pred=labels, pred_out=out[i:i + n] if labels else None, scores_out=None if labels else out[i:i + n])
@@ -924,3 +959,296 @@ def inference_report(model, volumes, classes: int = 9, img_size: int = 224, batc
         log('Testing performance in best val model: mean_assd : %f mean_hd : %f mean_nsd : %f' % (overall["assd"], overall["hd"], overall["nsd"]))
     return {"cases": cases, "mean": {key: total[:, j].tolist() for j, key in enumerate(SURFACE_KEYS)}, "overall": overall,
             "n_defined": [sum(bool(c["classes"][k]["defined"]) for c in cases) for k in range(classes - 1)]}
+
+
+# ------------------------------------------------------------------------------------------------ uncertainty maps and calibration
+UNCERT_KINDS = {"logits": TC_UNCERT_LOGITS, "prob_sums": TC_UNCERT_PROB_SUMS}
+
+
+class Uncertainty(NamedTuple):
+    """Per-pixel maps of `uncertainty_maps` and `predict_uncertainty` (include/transception_uncertainty.h): the uint8 label, the predictive
+    entropy normalised to [0, 1] by log(classes), the maximum class probability, and the mutual information between the views (the entropy of
+    the averaged probabilities minus the average of the views' entropies, >= 0).  What was not asked for, or does not exist, is None."""
+    pred: Optional[torch.Tensor]
+    entropy: Optional[torch.Tensor]
+    confidence: Optional[torch.Tensor]
+    mutual_information: Optional[torch.Tensor]
+
+
+@dataclass(frozen=True)
+class Calibration:
+    """Calibration statistics of the evaluation (include/transception_uncertainty.h): `bins` equal-width confidence bins (1..32) of the
+    reliability table behind ECE and MCE; `foreground_only`: count a pixel only where its label or its prediction is not background (class 0
+    dominates a CT slice, and its confident pixels hide everything else); `ignore_index`: a label value 0..255 whose pixels are not counted
+    (labels >= classes never are)."""
+    bins: int = 15
+    foreground_only: bool = False
+    ignore_index: Optional[int] = None
+
+    def __post_init__(self):
+        b, i = self.bins, self.ignore_index
+        if isinstance(b, bool) or not isinstance(b, (int, np.integer)) or not 1 <= b <= TC_CALIB_MAX_BINS:
+            raise ValueError(f"bins must be an integer in 1..{TC_CALIB_MAX_BINS}, got {b!r}")
+        if not isinstance(self.foreground_only, (bool, np.bool_)):
+            raise ValueError(f"foreground_only must be a bool, got {self.foreground_only!r}")
+        if i is not None and (isinstance(i, bool) or not isinstance(i, (int, np.integer)) or not 0 <= i <= 255):
+            raise ValueError(f"ignore_index must be None or an integer in 0..255 (labels are uint8), got {i!r}")
+        object.__setattr__(self, "bins", int(b))
+        object.__setattr__(self, "foreground_only", bool(self.foreground_only))
+        object.__setattr__(self, "ignore_index", None if i is None else int(i))
+
+
+def _check_calibration(calibration, classes) -> None:
+    if not isinstance(calibration, Calibration):
+        raise ValueError(f"calibration must be a Calibration, got {calibration!r}")
+    if isinstance(classes, bool) or not isinstance(classes, (int, np.integer)) or not 1 <= classes <= 16:
+        raise ValueError("classes must be in 1..16")
+
+
+def _check_views(views) -> float:
+    """The fp32 factor (float)(1.0 / V) of V views."""
+    if isinstance(views, bool) or not isinstance(views, (int, np.integer)) or views < 1:
+        raise ValueError(f"views must be an integer >= 1, got {views!r}")
+    return float(np.float32(1.0 / int(views)))
+
+
+def _check_scores(scores: torch.Tensor, kind: str) -> torch.Tensor:
+    if kind not in UNCERT_KINDS:
+        raise ValueError(f"kind must be one of {tuple(UNCERT_KINDS)}, got {kind!r}")
+    if not scores.is_cuda:
+        raise RuntimeError(NO_CPU)
+    if scores.dim() != 4 or scores.dtype not in TC_DTYPE or (kind == "prob_sums" and scores.dtype != torch.float32):
+        raise ValueError("class scores are a [N,C,H,W] tensor: float32, bfloat16 or float16 logits, or float32 probability sums")
+    return scores.contiguous()
+
+
+def uncertainty_maps(scores: torch.Tensor, *, kind: str = "logits", views: int = 1, entropy: bool = True, confidence: bool = True,
+                     pred: bool = False, view_entropy_sum: Optional[torch.Tensor] = None) -> Uncertainty:
+    """The maps of tc_uncert_maps for CUDA class scores [N,C,H,W], one launch: `kind` "logits" (fp32, bf16 or fp16; softmax in registers) or
+    "prob_sums" (fp32 sums of `views` probability vectors, the accumulator of tc_tta_accumulate).  `view_entropy_sum`: fp32 [N,H,W], the sum of
+    the views' own normalised entropies; the mutual information `max(0, entropy - view_entropy_sum / views)` is returned with it.  What is
+    not asked for is None and is never written.  Nothing is synchronised."""
+    inv = _check_views(views)
+    scores = _check_scores(scores, kind)
+    N, C, H, W = scores.shape
+    dev = scores.device
+    if not (entropy or confidence or pred or view_entropy_sum is not None):
+        raise ValueError("ask for at least one map")
+    ves = view_entropy_sum
+    if ves is not None:
+        if not ves.is_cuda or ves.dtype != torch.float32 or tuple(ves.shape) != (N, H, W):
+            raise ValueError(f"view_entropy_sum is a float32 CUDA tensor of shape {(N, H, W)}")
+        ves = ves.contiguous()
+    new = lambda dt: torch.empty((N, H, W), dtype=dt, device=dev)
+    e, c = (new(torch.float32) if entropy else None), (new(torch.float32) if confidence else None)
+    m, p = (new(torch.float32) if ves is not None else None), (new(torch.uint8) if pred else None)
+    ptr = lambda t: None if t is None else t.data_ptr()
+    lib().tc_uncert_maps(scores.data_ptr(), TC_DTYPE[scores.dtype], UNCERT_KINDS[kind], inv, ptr(ves), ptr(e), ptr(c), ptr(m), ptr(p), N, C, H, W,
+                         torch.cuda.current_stream(dev).cuda_stream)
+    return Uncertainty(p, e, c, m)
+
+
+@torch.no_grad()
+def predict_uncertainty(model, slices: torch.Tensor, batch: int = 16, tta: Optional[TTA] = None, *,
+                        out_size: Optional[Tuple[int, int]] = None) -> Uncertainty:
+    """`predict_probs`' batch loop and views (`_predict`), and from its accumulator the four maps of `Uncertainty`, each [N,X,Y] with
+    (X, Y) = `out_size` or the slices' own size.  Per view one tc_uncert_maps on the view's logits adds that view's entropy, at the
+    un-transformed position, into a view-entropy sum; after the last view one tc_uncert_maps per batch on the summed probabilities writes all
+    maps.  With `out_size` the accumulator is resampled bilinearly first (tc_resample_scores), and the view-entropy sum with it, as a
+    one-class map.  `mutual_information` is None with fewer than two views.  `pred` is the argmax of the summed probabilities."""
+    _check_tta(tta, tuple(slices.shape[1:]))
+    out_size = _check_out_size(out_size)
+    if slices.shape[0] == 0:
+        raise ValueError("predict_uncertainty needs at least one slice")
+    views = (0,) if tta is None else tuple(map(int, tta.views))
+    N, H, W = slices.shape
+    ves = torch.empty((N, H, W), dtype=torch.float32, device=slices.device) if len(views) > 1 else None
+    sums = _predict(model, slices, batch, views, out_size, labels=False, ves=ves)
+    if ves is not None and tuple(sums.shape[2:]) != (H, W):
+        ves = torch.cat([resample_scores(ves[i:i + batch].unsqueeze(1), tuple(sums.shape[2:]), scores=True, pred=False)[0][:, 0]
+                         for i in range(0, N, batch)])
+    parts = [uncertainty_maps(sums[i:i + batch], kind="prob_sums", views=len(views), pred=True,
+                              view_entropy_sum=None if ves is None else ves[i:i + batch]) for i in range(0, N, batch)]
+    return Uncertainty(*(None if part[0] is None else torch.cat(part) for part in zip(*parts)))
+
+
+def calibration_stats(scores: torch.Tensor, labels: torch.Tensor, calibration: Calibration = Calibration(), *, kind: str = "logits",
+                      views: int = 1, work: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The raw int64 slots of tc_calib_stats, on the device, for CUDA class scores [N,C,H,W] (`kind`, `views`: as `uncertainty_maps`) and
+    uint8 labels [N,H,W]: [bins][3] (count, confidence sum in units of 2^-32, correct), [4] (n, NLL sum and Brier sum as the bits of doubles,
+    correct), [C][3] per predicted class (count, entropy sum in units of 2^-32, correct).  Two launches, nothing synchronised.
+    `decode_calibration_stats` turns them into a float64 vector that is additive over batches, volumes and ranks.  `work`: the scratch of an
+    earlier call with the same bins and classes (`calibration_work`), so that a loop over batches allocates it once."""
+    scores = _check_scores(scores, kind)
+    inv = _check_views(views)
+    N, C, H, W = scores.shape
+    _check_calibration(calibration, C)
+    if not labels.is_cuda:
+        raise RuntimeError(NO_CPU)
+    if labels.dtype != torch.uint8 or tuple(labels.shape) != (N, H, W):
+        raise ValueError(f"labels are a uint8 CUDA tensor of shape {(N, H, W)}")
+    labels = labels.contiguous()
+    L, dev = lib(), scores.device
+    if work is None:
+        work = calibration_work(calibration.bins, C, dev)
+    elif not work.is_cuda or work.dtype != torch.int64 or work.numel() * 8 < int(L.tc_calib_work_bytes(calibration.bins, C)) or not work.is_contiguous():
+        raise ValueError("work is the int64 CUDA scratch of calibration_work(bins, classes, device)")
+    out = torch.empty(int(L.tc_calib_out_slots(calibration.bins, C)), dtype=torch.int64, device=dev)
+    L.tc_calib_stats(scores.data_ptr(), TC_DTYPE[scores.dtype], UNCERT_KINDS[kind], inv, labels.data_ptr(),
+                     -1 if calibration.ignore_index is None else calibration.ignore_index, TC_CALIB_FOREGROUND if calibration.foreground_only else 0,
+                     calibration.bins, N, C, H, W, work.data_ptr(), out.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+    return out
+
+
+def calibration_work(bins: int, classes: int, device) -> torch.Tensor:
+    """The scratch of tc_calib_stats for `bins` and `classes` (tc_calib_work_bytes; 304 KiB at 15 and 9): it needs no initialisation."""
+    return torch.empty(int(lib().tc_calib_work_bytes(bins, classes)) // 8, dtype=torch.int64, device=device)
+
+
+def decode_calibration_stats(stats, bins: int):
+    """The int64 slots of `calibration_stats` (a tensor, on the device or not, or a NumPy array) as a float64 vector of the same kind and layout:
+    the counts as they are (exact below 2^53), the two fixed-point sums divided by 2^32, the NLL and Brier sums read as the doubles they
+    are.  Decoded vectors add: over batches, volumes and ranks."""
+    if isinstance(stats, torch.Tensor):
+        if stats.dtype != torch.int64 or stats.dim() != 1:
+            raise ValueError("raw calibration statistics are a flat int64 tensor")
+        out = stats.to(torch.float64)
+        out[3 * bins + 1:3 * bins + 3] = stats[3 * bins + 1:3 * bins + 3].view(torch.float64)
+    else:
+        stats = np.ascontiguousarray(stats)
+        if stats.dtype != np.int64 or stats.ndim != 1:
+            raise ValueError("raw calibration statistics are a flat int64 array")
+        out = stats.astype(np.float64)
+        out[3 * bins + 1:3 * bins + 3] = stats[3 * bins + 1:3 * bins + 3].view(np.float64)
+    out[1:3 * bins:3] /= 2.0 ** 32
+    out[3 * bins + 5::3] /= 2.0 ** 32
+    return out
+
+
+def calibration_from_stats(stats, bins: int, classes: int) -> dict:
+    """ECE and its companions from the slots of `calibration_stats` -- raw int64, or decoded and summed float64 (`decode_calibration_stats`):
+        {"ece": sum_b n_b / n |acc_b - conf_b|, "mce": max_b |acc_b - conf_b| over the non-empty bins, "nll", "brier": means over the n
+         counted pixels, "accuracy", "n", "bins": [{"count", "confidence", "accuracy"}], "classes": [{"count", "entropy", "accuracy"}]}
+    with the means of an empty bin or class, and everything at n = 0, equal to 0."""
+    if isinstance(stats, torch.Tensor):
+        stats = stats.detach().cpu().numpy()
+    stats = np.asarray(stats)
+    if stats.dtype == np.int64:
+        stats = decode_calibration_stats(stats, bins)
+    if stats.dtype != np.float64 or stats.shape != (3 * bins + 4 + 3 * classes,):
+        raise ValueError(f"calibration statistics for {bins} bins and {classes} classes are {3 * bins + 4 + 3 * classes} int64 or float64 slots")
+    table, (n, nll, brier, correct), per_class = stats[:3 * bins].reshape(bins, 3), stats[3 * bins:3 * bins + 4], stats[3 * bins + 4:].reshape(classes, 3)
+    mean = lambda total, count: float(total / count) if count > 0 else 0.0
+    rows = [{"count": int(c), "confidence": mean(s, c), "accuracy": mean(k, c)} for c, s, k in table]
+    gaps = [(r["count"], abs(r["accuracy"] - r["confidence"])) for r in rows if r["count"] > 0]
+    return {"ece": float(sum(c * g for c, g in gaps) / n) if n > 0 else 0.0, "mce": max((g for _, g in gaps), default=0.0),
+            "nll": mean(nll, n), "brier": mean(brier, n), "accuracy": mean(correct, n), "n": int(n), "bins": rows,
+            "classes": [{"count": int(c), "entropy": mean(s, c), "accuracy": mean(k, c)} for c, s, k in per_class]}
+
+
+def calibration_stats_host(probs: np.ndarray, labels: np.ndarray, calibration: Calibration = Calibration()) -> np.ndarray:
+    """The decoded float64 slots of `calibration_stats` from NumPy, by the definitions of include/transception_uncertainty.h for probabilities
+    p [N,C,H,W] (the values as given, widened to float64) and labels [N,H,W]: the bin by the header's float32 product, the confidence sum
+    by its truncation to 2^-32 (exact for float32 probabilities), entropy, NLL and Brier in float64."""
+    probs, labels = np.asarray(probs), np.asarray(labels)
+    if probs.ndim != 4 or labels.shape != probs.shape[:1] + probs.shape[2:]:
+        raise ValueError("calibration on the host takes probabilities [N,C,H,W] and labels [N,H,W]")
+    C, bins = probs.shape[1], calibration.bins
+    _check_calibration(calibration, C)
+    p = np.moveaxis(probs, 1, -1).reshape(-1, C)
+    y = labels.reshape(-1).astype(np.int64)
+    pred = p.argmax(axis=1)                                                # the first maximum
+    counted = y < C
+    if calibration.ignore_index is not None:
+        counted &= y != calibration.ignore_index
+    if calibration.foreground_only:
+        counted &= (y > 0) | (pred > 0)
+    p, y, pred = p[counted], y[counted], pred[counted]
+    conf32 = p.max(axis=1).astype(np.float32) if len(p) else np.zeros(0, np.float32)
+    b = np.minimum(bins - 1, (conf32 * np.float32(bins)).astype(np.int64))
+    p = p.astype(np.float64)
+    conf = np.floor(conf32.astype(np.float64) * 2.0 ** 32) / 2.0 ** 32
+    with np.errstate(divide="ignore", invalid="ignore"):
+        h = -np.where(p > 0, p * np.log(p), 0.0).sum(axis=1) / math.log(C) if C > 1 else np.zeros(len(p))
+    h = np.clip(h, 0.0, 1.0)
+    rows = np.arange(len(p))
+    nll = -np.log(np.maximum(p[rows, y], float(np.finfo(np.float32).tiny)))
+    onehot = np.zeros_like(p)
+    onehot[rows, y] = 1.0
+    brier = ((p - onehot) ** 2).sum(axis=1)
+    ok = (pred == y).astype(np.float64)
+    out = np.zeros(3 * bins + 4 + 3 * C, dtype=np.float64)
+    for j, w in enumerate((None, conf, ok)):
+        out[j:3 * bins:3] = np.bincount(b, weights=w, minlength=bins)
+    out[3 * bins:3 * bins + 4] = (len(p), math.fsum(nll.tolist()), math.fsum(brier.tolist()), ok.sum())
+    for j, w in enumerate((None, h, ok)):
+        out[3 * bins + 4 + j::3] = np.bincount(pred, weights=w, minlength=C)
+    return out
+
+
+def calibration_host(probs: np.ndarray, labels: np.ndarray, calibration: Calibration = Calibration()) -> dict:
+    """`calibration_from_stats`' dict from NumPy in float64 (`calibration_stats_host`), plus "stats": the counterpart of the `*_host` functions."""
+    stats = calibration_stats_host(probs, labels, calibration)
+    return dict(calibration_from_stats(stats, calibration.bins, np.asarray(probs).shape[1]), stats=stats)
+
+
+@torch.no_grad()
+def evaluate_volume_calibration(model, image: np.ndarray, label: np.ndarray, classes: int = 9, patch_size=(224, 224), batch: int = 16,
+                                tta: Optional[TTA] = None, *, calibration: Calibration = Calibration()) -> dict:
+    """Calibration of one [D,X,Y] volume, measured where the scores live: at the network size.  The image goes there by the order-3 zoom of
+    `evaluate_volume`, the label volume by `zoom_labels`, the order-0 rule the training labels go through; the class probabilities summed
+    over the views of `tta` (None: the one plain pass) are `predict_probs`' accumulator, and tc_calib_stats reads it batch by batch.  Nothing
+    of the label's size times the classes is made.  Returns `calibration_from_stats`' dict plus "stats": the decoded float64 slots (NumPy),
+    which add over volumes."""
+    _check_calibration(calibration, classes)
+    _check_tta(tta, tuple(patch_size))
+    image, label = np.asarray(image), np.asarray(label)
+    if image.ndim != 3 or image.shape != label.shape:
+        raise ValueError("calibration takes an image volume [D,X,Y] and a label volume of the same shape")
+    dev = next(model.parameters()).device
+    if dev.type != "cuda":
+        raise RuntimeError(NO_CPU)
+    D, X, Y = image.shape
+    resize = (X, Y) != tuple(patch_size)
+    vol = torch.from_numpy(np.ascontiguousarray(image, np.float32)).to(dev)
+    lab = torch.from_numpy(np.ascontiguousarray(label).astype(np.uint8)).to(dev)
+    if resize:
+        vol, lab = zoom_volume_to_network(vol, tuple(patch_size)), zoom_labels(lab, tuple(patch_size))
+    views = (0,) if tta is None else tuple(map(int, tta.views))
+    sums = _predict(model, vol, batch, views, None, labels=False)
+    if sums.shape[1] != classes:
+        raise ValueError(f"the model returned {sums.shape[1]} classes, not {classes}")
+    total, work = None, calibration_work(calibration.bins, classes, dev)
+    for i in range(0, D, batch):
+        part = decode_calibration_stats(calibration_stats(sums[i:i + batch], lab[i:i + batch], calibration, kind="prob_sums", views=len(views),
+                                                          work=work), calibration.bins)
+        total = part if total is None else total.add_(part)
+    stats = total.cpu().numpy()
+    return dict(calibration_from_stats(stats, calibration.bins, classes), stats=stats)
+
+
+def calibration_line(c: dict) -> str:
+    """The figures of a `calibration_from_stats` dict as the log lines carry them."""
+    return 'ece %f mce %f nll %f brier %f accuracy %f n %d' % (c["ece"], c["mce"], c["nll"], c["brier"], c["accuracy"], c["n"])
+
+
+def inference_calibration(model, volumes, classes: int = 9, img_size: int = 224, batch: int = 16, log=None, tta: Optional[TTA] = None, *,
+                          calibration: Calibration = Calibration()) -> dict:
+    """`evaluate_volume_calibration` over `volumes` = iterable of (image, label, case name), and the calibration of the POOL: the slots of all
+    volumes are added and decoded once -- ECE is defined over a test set, it is not the mean of the cases' ECEs.
+        {"cases": [{"name", ...the case's dict}], "overall": {...the pool's dict, with its "stats"}}"""
+    _check_calibration(calibration, classes)
+    _check_tta(tta)
+    cases, total = [], None
+    for i, (image, label, name) in enumerate(volumes):
+        c = evaluate_volume_calibration(model, np.asarray(image), np.asarray(label), classes, (img_size, img_size), batch, tta, calibration=calibration)
+        total = c["stats"].copy() if total is None else total + c["stats"]
+        cases.append(dict(c, name=name))
+        if log:
+            log(' idx %d case %s calibration %s' % (i, name, calibration_line(c)))
+    if not cases:
+        raise ValueError("inference_calibration() needs at least one volume")
+    overall = dict(calibration_from_stats(total, calibration.bins, classes), stats=total)
+    if log:
+        log('Calibration over %d cases: %s' % (len(cases), calibration_line(overall)))
+    return {"cases": cases, "overall": overall}

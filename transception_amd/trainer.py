@@ -28,7 +28,8 @@ import torch
 import torch.distributed as dist
 
 from .data import DeviceLoader, SynapseSlices
-from .evaluate import RESAMPLE_MODES, SURFACE_KEYS, TTA, VALID_OPTION, PostProcess, SurfaceMetrics, inference, inference_report
+from .evaluate import (RESAMPLE_MODES, SURFACE_KEYS, TTA, VALID_OPTION, Calibration, PostProcess, SurfaceMetrics, calibration_from_stats,
+                       calibration_line, inference, inference_calibration, inference_report)
 from .train import (DynamicLossScale, FusedAdamW, FusedSGD, GraphedStep, SegLoss, WeightEMA, check_class_weights, check_ema_decay,
                     check_focal_tversky, check_ignore_index, cosine_lr, train_step)
 
@@ -102,6 +103,8 @@ class TrainConfig:
             raise ValueError(f"surface_metrics must be None or an evaluate.SurfaceMetrics, got {self.surface_metrics!r}")
         if self.surface_metrics is not None:
             self.surface_metrics.tolerances(self.num_classes)         # one tolerance, or one per class 1..num_classes-1
+        if not VALID_OPTION["calibration"](self.calibration):
+            raise ValueError(f"calibration must be None or an evaluate.Calibration, got {self.calibration!r}")
         check_focal_tversky(self.focal_gamma, self.overlap, self.tversky_alpha, self.tversky_beta)
         make_loss_scale(self.loss_scale)
         check_class_weights("class_weights", self.class_weights, self.num_classes, need_positive=True)
@@ -117,11 +120,14 @@ class TrainConfig:
 # again).  `repr` does show them, after the fields.
 #   surface_metrics: an evaluate.SurfaceMetrics -- the evaluation after a checkpoint then runs `inference_report` and `hist["surface"]` collects
 #     its overall ASD / ASSD / HD / surface Dice beside `hist["dice"]` and `hist["hd95"]`; None: `inference`, as before;
+#   calibration: an evaluate.Calibration -- the evaluation after a checkpoint then also runs `inference_calibration` on the rank's share of the
+#     volumes (one more prediction pass per volume), the decoded statistics are all-reduced as one float64 vector and `hist["calibration"]`
+#     collects the pool's ECE / MCE / NLL / Brier / accuracy with its reliability table; None: no key, no pass, no launch;
 #   focal_gamma, overlap, tversky_alpha, tversky_beta: the loss (train.SegLoss has the definition) -- the focal exponent of the
 #     cross-entropy, "dice" or "tversky" for the overlap term, and the Tversky weights of false positives and false negatives;
 #   resample: what the evaluation resamples to the label's size (evaluate.evaluate_volume: "labels", the reference's order-0 zoom of the
 #     argmax, or "scores", bilinear class scores and then the argmax).
-KEYWORD_OPTIONS = (("surface_metrics", Optional[SurfaceMetrics], None),
+KEYWORD_OPTIONS = (("surface_metrics", Optional[SurfaceMetrics], None), ("calibration", Optional[Calibration], None),
                    ("focal_gamma", float, 0.0), ("overlap", str, "dice"), ("tversky_alpha", float, 0.5), ("tversky_beta", float, 0.5),
                    ("resample", str, "labels"))
 
@@ -247,6 +253,8 @@ def trainer_synapse(cfg: TrainConfig, model, snapshot_path: str, volumes: Option
         hist["loss_scale"] = []                                   # the scale after the step of each log line
     if cfg.surface_metrics is not None:
         hist["surface"] = []                                      # per evaluation: inference_report's `overall`, {key: mean over cases and classes}
+    if cfg.calibration is not None:
+        hist["calibration"] = []                                  # per evaluation: the pool's calibration_from_stats dict
     step = None
     iter_num = 0
     for x, y in loader:
@@ -298,6 +306,8 @@ def trainer_synapse(cfg: TrainConfig, model, snapshot_path: str, volumes: Option
                             dist.broadcast(buf, src=0, group=group)
                         vols = vols[rank::world]
                     res = torch.zeros(3 + (len(SURFACE_KEYS) if cfg.surface_metrics is not None else 0), dtype=torch.float64, device=dev)
+                    if cfg.calibration is not None:               # the decoded slots: counts and sums, additive over the ranks
+                        calib = torch.zeros(3 * cfg.calibration.bins + 4 + 3 * cfg.num_classes, dtype=torch.float64, device=dev)
                     if vols:
                         if rank == 0:
                             log(f"Running Inference after epoch {epoch_num}")
@@ -311,6 +321,10 @@ def trainer_synapse(cfg: TrainConfig, model, snapshot_path: str, volumes: Option
                                 overall = inference_report(model, vols, cfg.num_classes, cfg.img_size, surface=cfg.surface_metrics, **options)["overall"]
                                 mean_dice, mean_hd95 = overall["dice"], overall["hd95"]
                                 res[3:] = torch.tensor([overall[key] * len(vols) for key in SURFACE_KEYS], dtype=torch.float64)
+                            if cfg.calibration is not None:
+                                pool = inference_calibration(model, vols, cfg.num_classes, cfg.img_size, log=log, tta=cfg.tta,
+                                                             calibration=cfg.calibration)["overall"]
+                                calib.copy_(torch.from_numpy(pool["stats"]))
                         res[0], res[1], res[2] = mean_dice * len(vols), mean_hd95 * len(vols), len(vols)
                         model.train()
                     if distributed:
@@ -319,6 +333,12 @@ def trainer_synapse(cfg: TrainConfig, model, snapshot_path: str, volumes: Option
                     hist["hd95"].append(float(res[1] / res[2].clamp(min=1)))
                     if cfg.surface_metrics is not None:           # all-reduced like the two means above
                         hist["surface"].append(dict(zip(SURFACE_KEYS, (res[3:] / res[2].clamp(min=1)).tolist())))
+                    if cfg.calibration is not None:
+                        if distributed:
+                            dist.all_reduce(calib, group=group)
+                        hist["calibration"].append(calibration_from_stats(calib.cpu().numpy(), cfg.calibration.bins, cfg.num_classes))
+                        if distributed and rank == 0:             # the lines above are each rank's own share; this one is the pool of all ranks
+                            log('Calibration over all ranks: ' + calibration_line(hist["calibration"][-1]))
     hist["iterations"] = iter_num
     if isinstance(opt, FusedAdamW):
         hist["optimizer_step"] = opt.device_step()                # updates applied, as the device counted them: iterations minus skipped
