@@ -36,6 +36,7 @@ SIDE_HEADERS = (SideHeader("POST", "transception_post.h", "TC_POST_ABI_VERSION",
                 SideHeader("BRIDGE", "transception_bridge.h", "TC_BRIDGE_ABI_VERSION", "tc_bridge_abi_version", "bridge LayerNorm"),
                 SideHeader("SURFACE", "transception_surface.h", "TC_SURFACE_ABI_VERSION", "tc_surface_abi_version", "surface metrics"),
                 SideHeader("UNCERT", "transception_uncertainty.h", "TC_UNCERT_ABI_VERSION", "tc_uncert_abi_version", "uncertainty / calibration"),
+                SideHeader("TOPK", "transception_topk.h", "TC_TOPK_ABI_VERSION", "tc_topk_abi_version", "top-k loss"),
                 SideHeader("LOSS", "transception_loss.h", "TC_LOSS_ABI_VERSION", "tc_loss_abi_version", "focal / Tversky loss"))
 
 SCALARS = {"int": C.c_int, "long long": C.c_longlong, "float": C.c_float, "double": C.c_double,

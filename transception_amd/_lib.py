@@ -6,7 +6,7 @@ which replace no reference call site, have a header and a version of their own (
 weight averaging (include/transception_ema.h -> EMA), the test-time augmentation (include/transception_tta.h -> TTA) and the resampling of
 class scores (include/transception_resample.h -> RESAMPLE), the focal / Tversky loss (include/transception_loss.h -> LOSS) and the directed
 surface-distance statistics (include/transception_surface.h -> SURFACE) and the uncertainty maps and calibration statistics
-(include/transception_uncertainty.h -> UNCERT).
+(include/transception_uncertainty.h -> UNCERT) and the top-k cross-entropy (include/transception_topk.h -> TOPK).
 
 There is deliberately NO fallback: if the shared library is missing or a call returns a non-zero
 status the host raises.  (The CPU oracle under oracle/ is test infrastructure and is never imported here.)
@@ -26,7 +26,7 @@ SIGNATURES = {name: f.argtypes for name, f in ABI.functions.items()}     # every
 K, S = ABI.constants, ABI.structs
 SIDE = {s.attr: _header.load(s.path) for s in _header.SIDE_HEADERS}       # the headers of their own: one line each in _header.SIDE_HEADERS
 POST, EMA, TTA, RESAMPLE, BRIDGE, LOSS = SIDE["POST"], SIDE["EMA"], SIDE["TTA"], SIDE["RESAMPLE"], SIDE["BRIDGE"], SIDE["LOSS"]
-SURFACE, UNCERT = SIDE["SURFACE"], SIDE["UNCERT"]
+SURFACE, UNCERT, TOPK = SIDE["SURFACE"], SIDE["UNCERT"], SIDE["TOPK"]
 
 ABI_VERSION = K["TC_ABI_VERSION"]
 TC_F32, TC_BF16, TC_F16 = K["TC_F32"], K["TC_BF16"], K["TC_F16"]
@@ -39,7 +39,7 @@ TC_AUG_SKIP, TC_AUG_FROM_RAW = K["TC_AUG_SKIP"], K["TC_AUG_FROM_RAW"]
 ATTN_DKV_SPLITS = K["TC_ATTN_DKV_SPLITS"]
 TC_METRIC_NO_SOURCE, TC_METRIC_SELECT_WORK_BYTES = K["TC_METRIC_NO_SOURCE"], K["TC_METRIC_SELECT_WORK_BYTES"]
 TC_IGNORE_NONE = K["TC_IGNORE_NONE"]
-POST_ABI_VERSION, EMA_ABI_VERSION, TTA_ABI_VERSION, RESAMPLE_ABI_VERSION, BRIDGE_ABI_VERSION, SURFACE_ABI_VERSION, UNCERT_ABI_VERSION, LOSS_ABI_VERSION = (SIDE[s.attr].constants[s.version] for s in _header.SIDE_HEADERS)
+POST_ABI_VERSION, EMA_ABI_VERSION, TTA_ABI_VERSION, RESAMPLE_ABI_VERSION, BRIDGE_ABI_VERSION, SURFACE_ABI_VERSION, UNCERT_ABI_VERSION, TOPK_ABI_VERSION, LOSS_ABI_VERSION = (SIDE[s.attr].constants[s.version] for s in _header.SIDE_HEADERS)
 TC_OVERLAP_DICE, TC_OVERLAP_TVERSKY = LOSS.constants["TC_OVERLAP_DICE"], LOSS.constants["TC_OVERLAP_TVERSKY"]
 TC_CC_LARGEST, TC_CC_MIN_VOXELS = POST.constants["TC_CC_LARGEST"], POST.constants["TC_CC_MIN_VOXELS"]
 TC_RESAMPLE_MAX_EXTENT = RESAMPLE.constants["TC_RESAMPLE_MAX_EXTENT"]

@@ -14,7 +14,7 @@ from ._header import HEADER, SIDE_HEADERS
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libtransception_hip.so")
-SOURCES = ["gemm.hip", "norm.hip", "dwconv.hip", "softmax.hip", "attention.hip", "attention_seg.hip", "elementwise.hip", "train.hip", "factoratt.hip", "data.hip", "mixffn.hip", "mixffn_bwd.hip", "effatt.hip", "cbam.hip", "ripm.hip", "linln.hip", "lncls.hip", "legacy.hip", "metrics.hip", "postprocess.hip", "ema.hip", "tta.hip", "resample.hip", "surface.hip", "uncertainty.hip"]
+SOURCES = ["gemm.hip", "norm.hip", "dwconv.hip", "softmax.hip", "attention.hip", "attention_seg.hip", "elementwise.hip", "train.hip", "factoratt.hip", "data.hip", "mixffn.hip", "mixffn_bwd.hip", "effatt.hip", "cbam.hip", "ripm.hip", "linln.hip", "lncls.hip", "legacy.hip", "metrics.hip", "postprocess.hip", "ema.hip", "tta.hip", "resample.hip", "surface.hip", "uncertainty.hip", "topk.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=fast", "-munsafe-fp-atomics"]
 
 

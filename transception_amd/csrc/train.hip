@@ -3,6 +3,7 @@
 // DiceLoss.forward(weight=...), utils.py:34-47) and the fused SGD-momentum update (trainer.py:125).
 #include "tc_common.h"
 #include "../../include/transception_loss.h"
+#include "../../include/transception_topk.h"
 
 namespace {
 
@@ -55,6 +56,14 @@ template <typename T> __device__ __forceinline__ void tok_row_store(T* dp, int n
 // other instantiations, which therefore keep their instruction sequence too.  gamma and the overlap mode are run-time values.
 template <bool FT> struct LossOpts {};
 template <> struct LossOpts<true> { float gamma; int tversky; float alpha, beta; };
+// TOPK (the top-k cross-entropy, tc_seg_loss_*_topk; include/transception_topk.h has the definition) is a further variant, of the FT bodies, in
+// the same manner: every line it adds sits under `if constexpr (TOPK)` and its pointers travel in a last argument that is empty otherwise.  The
+// forward stores each pixel's CE term in a value map instead of summing it; the backward weighs the CE gradient by the pixel's selection
+// weight, which it takes from the stored value against the threshold t = state[5] and the tie share f = state[7] of tc_topk_select.
+template <bool TOPK> struct TopkFwd {};
+template <> struct TopkFwd<true> { float* values; };
+template <bool TOPK> struct TopkBwd {};
+template <> struct TopkBwd<true> { const float* values; const double* state; float inv_world; };
 
 // the focal CE factor of a pixel: q^gamma, with gamma = 0 giving 1 for every q (q = 0 included)
 __device__ __forceinline__ float focal_pow(float q, float gamma) { return gamma == 0.f ? 1.f : powf(q, gamma); }
@@ -62,11 +71,12 @@ __device__ __forceinline__ float focal_pow(float q, float gamma) { return gamma 
 // logarithm to 0, where the true value is -q.  Below, the logarithm of the clamped p_t as the other variants take it
 __device__ __forceinline__ float focal_log_pt(float pt, float q) { return q < 0.25f ? log1pf(-q) : logf(fmaxf(pt, 1e-38f)); }
 
-template <typename T, bool WEIGHTED, bool FT = false>
+template <typename T, bool WEIGHTED, bool FT = false, bool TOPK = false>
 __global__ __launch_bounds__(256) void seg_loss_fwd_kernel(const T* __restrict__ logits, const long long* __restrict__ labels,
                                                            float* __restrict__ prob, float* __restrict__ sums, int B, int ncls, int HW, int ld,
-                                                           const float* __restrict__ weights, int ignore, LossOpts<FT> ft) {
+                                                           const float* __restrict__ weights, int ignore, LossOpts<FT> ft, TopkFwd<TOPK> tk) {
     static_assert(WEIGHTED || !FT, "FT extends the WEIGHTED variant");
+    static_assert(FT || !TOPK, "TOPK extends the FT variant");
     __shared__ float red[4][1 + 3 * MAXCLS];
     __shared__ float wce[WEIGHTED ? MAXCLS : 1];
     if constexpr (WEIGHTED) {
@@ -112,6 +122,14 @@ __global__ __launch_bounds__(256) void seg_loss_fwd_kernel(const T* __restrict__
                     if (k == lab) { I[k] += pk; Y[k] += 1.f; pt = pk; } else q += pk;
                 }
             }
+            if constexpr (TOPK) {
+                // the pixel's term goes to the value map, sign bit cleared (a NaN keeps a place above +inf in the select's bit order);
+                // -1 marks an ignored pixel; a counted pixel whose label is no class has the term 0, as it adds nothing above
+                float vi = -1.f;
+                if (counted) vi = (unsigned)lab < (unsigned)ncls ? wce[lab] * focal_pow(q, ft.gamma) * focal_log_pt(pt, q) : 0.f;
+                tk.values[i] = counted ? __uint_as_float(__float_as_uint(vi) & 0x7fffffffu) : vi;
+                continue;
+            }
             if (counted && (unsigned)lab < (unsigned)ncls) ce -= wce[lab] * focal_pow(q, ft.gamma) * focal_log_pt(pt, q);
             continue;
         }
@@ -145,6 +163,7 @@ __global__ __launch_bounds__(256) void seg_loss_fwd_kernel(const T* __restrict__
         if (lane == 0) { red[wave][1 + 3 * k] = a; red[wave][2 + 3 * k] = b; red[wave][3 + 3 * k] = c; }
     }
     __syncthreads();
+    if constexpr (TOPK) { if (threadIdx.x == 0) return; }          // sums[0] is tc_topk_select's
     if (threadIdx.x < 1 + 3 * ncls)
         atomicAdd(sums + threadIdx.x, red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x]);
 }
@@ -156,13 +175,17 @@ __global__ __launch_bounds__(256) void seg_loss_fwd_kernel(const T* __restrict__
 //
 // FT: under Tversky ca / cb are the coefficients of g_k = ca_k [k = lab] + cb_k (cb is NOT multiplied by p_k) from I, Y and P = sums[3 + 3k];
 // per pixel the CE factor is additionally multiplied by m = q^gamma (1 - gamma p_t log p_t / q), and p_t - 1 is taken as -q.
-template <typename T, bool WEIGHTED, bool FT = false>
+//
+// TOPK: the CE factor is w_ce / (world k) with k = state[2] of this rank's select (0 when nothing is counted: no CE gradient), times the
+// pixel's selection weight: 1 above the threshold, the tie share at it, 0 below, by the bit patterns the select ordered.
+template <typename T, bool WEIGHTED, bool FT = false, bool TOPK = false>
 __global__ __launch_bounds__(256) void seg_loss_bwd_kernel(const float* __restrict__ prob, const long long* __restrict__ labels,
                                                            const float* __restrict__ sums, T* __restrict__ dlogits, int B, int ncls,
                                                            int HW, float w_ce, float w_dice, float n_pix, float gscale, const float* __restrict__ gscale_dev, int ld,
                                                            const T* __restrict__ logits, int ldl, const float* __restrict__ weights, int ignore,
-                                                           LossOpts<FT> ft) {
+                                                           LossOpts<FT> ft, TopkBwd<TOPK> tk) {
     static_assert(WEIGHTED || !FT, "FT extends the WEIGHTED variant");
+    static_assert(FT || !TOPK, "TOPK extends the FT variant");
     if (gscale_dev) gscale *= *gscale_dev;
     const bool vin = !prob && !(ldl & 7) && ldl >= ((ncls + 7) & ~7) && !((uintptr_t)logits & 15);
     const bool vout = ld > 0 && !(ld & 7) && ld >= ((ncls + 7) & ~7) && !((uintptr_t)dlogits & 15);
@@ -196,6 +219,7 @@ __global__ __launch_bounds__(256) void seg_loss_bwd_kernel(const float* __restri
         float n_eff = 0.f;
         for (int k = 0; k < ncls; ++k) n_eff += wy[k];              // class order, the same in every thread and every workgroup
         cew = n_eff > 0.f ? w_ce / n_eff : 0.f;
+        if constexpr (TOPK) cew = tk.state[2] > 0.0 ? (float)((double)w_ce * (double)tk.inv_world / tk.state[2]) : 0.f;
     } else {
         cew = w_ce / n_pix;
     }
@@ -237,7 +261,11 @@ __global__ __launch_bounds__(256) void seg_loss_bwd_kernel(const float* __restri
             float mod = 1.f;
             if (ft.gamma != 0.f) mod = q > 0.f ? powf(q, ft.gamma) * (1.f - ft.gamma * pt * focal_log_pt(pt, q) / q) : 0.f;
             const bool counted = lab != ignore;
-            const float cw = cew * ((unsigned)lab < (unsigned)ncls ? wce[lab] : 1.f) * mod;
+            float cw = cew * ((unsigned)lab < (unsigned)ncls ? wce[lab] : 1.f) * mod;
+            if constexpr (TOPK) {
+                const unsigned vb = __float_as_uint(tk.values[i]), tb = __float_as_uint((float)tk.state[5]);
+                cw *= vb > tb ? 1.f : (vb == tb ? (float)tk.state[7] : 0.f);       // (an ignored pixel's -1 is above every t; it writes zeros below)
+            }
             T* dp = ld ? dlogits + i * ld : dlogits + (long long)b * ncls * HW + p;
             const long long ks = ld ? 1 : HW;
             if (sizeof(T) == 2 && vout) {
@@ -539,7 +567,7 @@ extern "C" int tc_seg_loss_fwd(const void* logits, const long long* labels, floa
     if (!logits || !labels || !prob || !sums || B <= 0 || ncls <= 0 || ncls > MAXCLS || HW <= 0 || (long long)B * HW >= 0x7fffffffLL) return TC_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
     TC_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((seg_loss_fwd_kernel<T, false>), dim3(tc_blocks((long long)B * HW, 256, 1024)), dim3(256), 0, s,
-                                                (const T*)logits, labels, prob, sums, B, ncls, HW, 0, (const float*)nullptr, 0, LossOpts<false>{}));
+                                                (const T*)logits, labels, prob, sums, B, ncls, HW, 0, (const float*)nullptr, 0, LossOpts<false>{}, TopkFwd<false>{}));
     return tc_launch_status();
 }
 
@@ -548,7 +576,7 @@ extern "C" int tc_seg_loss_fwd_tok(const void* logits, int ld, const long long* 
     if (!logits || !labels || !sums || B <= 0 || ncls <= 0 || ncls > MAXCLS || HW <= 0 || ld < ncls || (long long)B * HW >= 0x7fffffffLL) return TC_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
     TC_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((seg_loss_fwd_kernel<T, false>), dim3(tc_blocks((long long)B * HW, 256, 1024)), dim3(256), 0, s,
-                                                (const T*)logits, labels, prob, sums, B, ncls, HW, ld, (const float*)nullptr, 0, LossOpts<false>{}));
+                                                (const T*)logits, labels, prob, sums, B, ncls, HW, ld, (const float*)nullptr, 0, LossOpts<false>{}, TopkFwd<false>{}));
     return tc_launch_status();
 }
 
@@ -609,7 +637,7 @@ extern "C" int tc_seg_loss_fwd_w(const void* logits, int ld, const long long* la
         return TC_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
     TC_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((seg_loss_fwd_kernel<T, true>), dim3(tc_blocks((long long)B * HW, 256, 1024)), dim3(256), 0, s,
-                                                (const T*)logits, labels, prob, sums, B, ncls, HW, ld, weights, ignore_index, LossOpts<false>{}));
+                                                (const T*)logits, labels, prob, sums, B, ncls, HW, ld, weights, ignore_index, LossOpts<false>{}, TopkFwd<false>{}));
     return tc_launch_status();
 }
 
@@ -624,7 +652,7 @@ extern "C" int tc_seg_loss_bwd_w(const float* prob, const void* logits, int ldl,
     hipStream_t s = (hipStream_t)stream;
     TC_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((seg_loss_bwd_kernel<T, true>), dim3(tc_blocks((long long)B * HW, 256, 2048)), dim3(256), 0, s,
                                                 prob, labels, sums, (T*)dlogits, B, ncls, HW, w_ce, w_dice, 0.f, gscale, gscale_dev, ld,
-                                                (const T*)logits, ldl, weights, ignore_index, LossOpts<false>{}));
+                                                (const T*)logits, ldl, weights, ignore_index, LossOpts<false>{}, TopkBwd<false>{}));
     return tc_launch_status();
 }
 
@@ -646,11 +674,13 @@ extern "C" int tc_seg_loss_fwd_ft(const void* logits, int ld, const long long* l
     hipStream_t s = (hipStream_t)stream;
     const LossOpts<true> ft{gamma, overlap == TC_OVERLAP_TVERSKY, 0.f, 0.f};
     TC_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((seg_loss_fwd_kernel<T, true, true>), dim3(tc_blocks((long long)B * HW, 256, 1024)), dim3(256), 0, s,
-                                                (const T*)logits, labels, prob, sums, B, ncls, HW, ld, weights, ignore_index, ft));
+                                                (const T*)logits, labels, prob, sums, B, ncls, HW, ld, weights, ignore_index, ft, TopkFwd<false>{}));
     return tc_launch_status();
 }
 
 // tc_seg_loss_value_w's expression with the overlap term chosen by `overlap`; sums[0] already carries the focal factor
+// TOPK (tc_seg_loss_value_topk): sums[0] IS the cross-entropy, the mean over ranks of each rank's top-k mean
+template <bool TOPK = false>
 __global__ void seg_loss_value_ft_kernel(const float* __restrict__ sums, const float* __restrict__ weights, int ncls, double w_ce, double w_dice,
                                          int tversky, double alpha, double beta, float* __restrict__ out3) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
@@ -662,7 +692,7 @@ __global__ void seg_loss_value_ft_kernel(const float* __restrict__ sums, const f
         if (tversky) acc += wd * (1.0 - (inter + 1e-5) / ((1.0 - alpha - beta) * inter + alpha * zsum + beta * ysum + 1e-5));
         else acc += wd * (1.0 - (2.0 * inter + 1e-5) / (zsum + ysum + 1e-5));
     }
-    const double ce = n_eff > 0.0 ? (double)sums[0] / n_eff : 0.0;
+    const double ce = TOPK ? (double)sums[0] : n_eff > 0.0 ? (double)sums[0] / n_eff : 0.0;
     const double ov = acc / (double)ncls;
     out3[0] = (float)(w_ce * ce + w_dice * ov);
     out3[1] = (float)ce;
@@ -672,7 +702,7 @@ __global__ void seg_loss_value_ft_kernel(const float* __restrict__ sums, const f
 extern "C" int tc_seg_loss_value_ft(const float* sums, const float* weights, int ncls, double w_ce, double w_dice, int overlap, double alpha,
                                     double beta, float* out3, void* stream) {
     if (!sums || !out3 || ncls <= 0 || ncls > MAXCLS || !loss_opts_ok(0.0, overlap, alpha, beta)) return TC_ERR_ARG;
-    hipLaunchKernelGGL(seg_loss_value_ft_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, sums, weights, ncls, w_ce, w_dice,
+    hipLaunchKernelGGL(seg_loss_value_ft_kernel<false>, dim3(1), dim3(64), 0, (hipStream_t)stream, sums, weights, ncls, w_ce, w_dice,
                        (int)(overlap == TC_OVERLAP_TVERSKY), alpha, beta, out3);
     return tc_launch_status();
 }
@@ -689,7 +719,45 @@ extern "C" int tc_seg_loss_bwd_ft(const float* prob, const void* logits, int ldl
     const LossOpts<true> ft{gamma, tv, tv ? alpha : 0.f, tv ? beta : 0.f};
     TC_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((seg_loss_bwd_kernel<T, true, true>), dim3(tc_blocks((long long)B * HW, 256, 2048)), dim3(256), 0, s,
                                                 prob, labels, sums, (T*)dlogits, B, ncls, HW, w_ce, w_dice, 0.f, gscale, gscale_dev, ld,
-                                                (const T*)logits, ldl, weights, ignore_index, ft));
+                                                (const T*)logits, ldl, weights, ignore_index, ft, TopkBwd<false>{}));
+    return tc_launch_status();
+}
+
+// ---- top-k cross-entropy (include/transception_topk.h): the TOPK variant of the FT kernels; the select between them is csrc/topk.hip
+extern "C" int tc_seg_loss_fwd_topk(const void* logits, int ld, const long long* labels, const float* weights, int ignore_index, float gamma,
+                                    int overlap, float* prob, float* sums, float* values, int B, int ncls, int HW, int dtype, void* stream) {
+    if (!logits || !labels || !sums || !values || B <= 0 || ncls <= 0 || ncls > MAXCLS || HW <= 0 || (ld != 0 && ld < ncls) || (ld == 0 && !prob) ||
+        (ignore_index >= 0 && ignore_index < ncls) || (long long)B * HW >= 0x7fffffffLL || !loss_opts_ok(gamma, overlap, 0.5, 0.5))
+        return TC_ERR_ARG;
+    hipStream_t s = (hipStream_t)stream;
+    const LossOpts<true> ft{gamma, overlap == TC_OVERLAP_TVERSKY, 0.f, 0.f};
+    TC_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((seg_loss_fwd_kernel<T, true, true, true>), dim3(tc_blocks((long long)B * HW, 256, 1024)), dim3(256), 0, s,
+                                                (const T*)logits, labels, prob, sums, B, ncls, HW, ld, weights, ignore_index, ft, TopkFwd<true>{values}));
+    return tc_launch_status();
+}
+
+extern "C" int tc_seg_loss_value_topk(const float* sums, const float* weights, int ncls, double w_ce, double w_dice, int overlap, double alpha,
+                                      double beta, float* out3, void* stream) {
+    if (!sums || !out3 || ncls <= 0 || ncls > MAXCLS || !loss_opts_ok(0.0, overlap, alpha, beta)) return TC_ERR_ARG;
+    hipLaunchKernelGGL(seg_loss_value_ft_kernel<true>, dim3(1), dim3(64), 0, (hipStream_t)stream, sums, weights, ncls, w_ce, w_dice,
+                       (int)(overlap == TC_OVERLAP_TVERSKY), alpha, beta, out3);
+    return tc_launch_status();
+}
+
+extern "C" int tc_seg_loss_bwd_topk(const float* prob, const void* logits, int ldl, const long long* labels, const float* weights, int ignore_index,
+                                    const float* sums, void* dlogits, int ld, int B, int ncls, int HW, float w_ce, float w_dice, float gamma,
+                                    int overlap, float alpha, float beta, float gscale, const float* gscale_dev, const float* values,
+                                    const double* state, float inv_world, int dtype, void* stream) {
+    if ((!prob && (!logits || ldl < ncls || ld == 0)) || !labels || !sums || !dlogits || !values || !state || ((uintptr_t)state & 7) || B <= 0 ||
+        ncls <= 0 || ncls > MAXCLS || HW <= 0 || (ld != 0 && ld < ncls) || (ignore_index >= 0 && ignore_index < ncls) ||
+        (long long)B * HW >= 0x7fffffffLL || !loss_opts_ok(gamma, overlap, alpha, beta) || !(inv_world > 0.f && inv_world <= 1.f))
+        return TC_ERR_ARG;
+    hipStream_t s = (hipStream_t)stream;
+    const bool tv = overlap == TC_OVERLAP_TVERSKY;
+    const LossOpts<true> ft{gamma, tv, tv ? alpha : 0.f, tv ? beta : 0.f};
+    TC_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((seg_loss_bwd_kernel<T, true, true, true>), dim3(tc_blocks((long long)B * HW, 256, 2048)), dim3(256), 0, s,
+                                                prob, labels, sums, (T*)dlogits, B, ncls, HW, w_ce, w_dice, 0.f, gscale, gscale_dev, ld,
+                                                (const T*)logits, ldl, weights, ignore_index, ft, TopkBwd<true>{values, state, inv_world}));
     return tc_launch_status();
 }
 
@@ -708,7 +776,7 @@ extern "C" int tc_seg_loss_bwd(const float* prob, const long long* labels, const
     hipStream_t s = (hipStream_t)stream;
     TC_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((seg_loss_bwd_kernel<T, false>), dim3(tc_blocks((long long)B * HW, 256, 2048)), dim3(256), 0, s,
                                                 prob, labels, sums, (T*)dlogits, B, ncls, HW, w_ce, w_dice, n_pix_global, gscale, gscale_dev, 0, (const T*)nullptr, 0,
-                                                (const float*)nullptr, 0, LossOpts<false>{}));
+                                                (const float*)nullptr, 0, LossOpts<false>{}, TopkBwd<false>{}));
     return tc_launch_status();
 }
 
@@ -721,7 +789,7 @@ extern "C" int tc_seg_loss_bwd_tok(const float* prob, const void* logits, int ld
     hipStream_t s = (hipStream_t)stream;
     TC_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((seg_loss_bwd_kernel<T, false>), dim3(tc_blocks((long long)B * HW, 256, 2048)), dim3(256), 0, s,
                                                 prob, labels, sums, (T*)dlogits, B, ncls, HW, w_ce, w_dice, n_pix_global, gscale, gscale_dev, ld, (const T*)logits, ldl,
-                                                (const float*)nullptr, 0, LossOpts<false>{}));
+                                                (const float*)nullptr, 0, LossOpts<false>{}, TopkBwd<false>{}));
     return tc_launch_status();
 }
 

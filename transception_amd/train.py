@@ -56,7 +56,7 @@ OVERLAPS = {"dice": TC_OVERLAP_DICE, "tversky": TC_OVERLAP_TVERSKY}     # SegLos
 
 
 def loss_from_sums(sums: torch.Tensor, n_pix: float, w_ce: float, w_dice: float, weights: Optional[torch.Tensor] = None, *,
-                   overlap: str = "dice", tversky_alpha: float = 0.5, tversky_beta: float = 0.5):
+                   overlap: str = "dice", tversky_alpha: float = 0.5, tversky_beta: float = 0.5, topk: bool = False):
     """0.4*CE + 0.6*Dice from the (global) sums: trainer.py:141-143, utils.py:34-47 (smooth 1e-5, mean over classes).
     Device sums: one tc_seg_loss_value launch.  Host sums (the gloo tests): the same expression in torch, double.
 
@@ -67,14 +67,20 @@ def loss_from_sums(sums: torch.Tensor, n_pix: float, w_ce: float, w_dice: float,
     overlap="tversky" (sums of the tc_seg_loss_fwd_ft forward under TC_OVERLAP_TVERSKY: the third per-class sum is P_k = sum p): the
     second term is sum_k w_dice[k] (1 - (I_k + 1e-5) / ((1 - a - b) I_k + a P_k + b Y_k + 1e-5)) / classes with a, b = tversky_alpha,
     tversky_beta, and the CE denominator is sum_k w_ce[k] Y_k whether weights are given or not.  A focal gamma needs nothing here:
-    sums[0] carries the factor already."""
+    sums[0] carries the factor already.
+
+    topk (sums of the tc_seg_loss_fwd_topk forward after tc_topk_select, include/transception_topk.h): sums[0] IS the cross-entropy, the
+    mean over the ranks of each rank's top-k mean; nothing divides it."""
     ncls = (sums.numel() - 1) // 3
     if overlap not in OVERLAPS:
         raise ValueError(f"overlap must be one of {tuple(OVERLAPS)}, got {overlap!r}")
     if sums.is_cuda:
         out3 = torch.empty(3, dtype=torch.float32, device=sums.device)
         stream = torch.cuda.current_stream(sums.device).cuda_stream
-        if overlap != "dice":
+        if topk:
+            lib().tc_seg_loss_value_topk(sums.data_ptr(), None if weights is None else weights.data_ptr(), ncls, float(w_ce), float(w_dice),
+                                         OVERLAPS[overlap], float(tversky_alpha), float(tversky_beta), out3.data_ptr(), stream)
+        elif overlap != "dice":
             lib().tc_seg_loss_value_ft(sums.data_ptr(), None if weights is None else weights.data_ptr(), ncls, float(w_ce), float(w_dice),
                                        OVERLAPS[overlap], float(tversky_alpha), float(tversky_beta), out3.data_ptr(), stream)
         elif weights is None:
@@ -91,7 +97,10 @@ def loss_from_sums(sums: torch.Tensor, n_pix: float, w_ce: float, w_dice: float,
         per_class = 1.0 - (inter + 1e-5) / ((1.0 - a - b) * inter + a * zsum + b * ysum + 1e-5)
         if weights is None:
             weights = torch.ones(2 * ncls, dtype=torch.float64)
-    if weights is None:
+    if topk:
+        ce = s[0]
+        dice = per_class.mean() if weights is None else (weights.double()[ncls:] * per_class).sum() / ncls
+    elif weights is None:
         ce = s[0] / n_pix
         dice = per_class.mean()
     else:
@@ -154,6 +163,18 @@ def check_focal_tversky(gamma, overlap, alpha, beta) -> tuple:
     if alpha + beta == 0:
         raise ValueError("tversky_alpha + tversky_beta must be > 0")
     return float(gamma), overlap, float(alpha), float(beta)
+
+
+def check_ce_topk(frac, ncls: int) -> Optional[float]:
+    """SegLoss(ce_topk=...): None (off) stays None; else a number in (0, 1], not a bool, as a float.  Anything else is a ValueError, and so
+    is top-k above the 16 classes the loss kernels take."""
+    if frac is None:
+        return None
+    if isinstance(frac, bool) or not isinstance(frac, numbers.Real) or not math.isfinite(frac) or not 0.0 < frac <= 1.0:
+        raise ValueError(f"ce_topk must be None or a number in (0, 1], got {frac!r}")
+    if ncls > 16:
+        raise ValueError(f"the top-k loss kernels take at most 16 classes, got {ncls}")
+    return float(frac)
 
 
 class DynamicLossScale:
@@ -253,14 +274,29 @@ def _overlap_of(route) -> dict:
     """loss_from_sums' overlap keywords for a SegLoss._route: none for the plain and the class-weighted loss."""
     if route is None or len(route) == 2:
         return {}
-    return {"overlap": route[3], "tversky_alpha": route[4], "tversky_beta": route[5]}
+    kw = {"overlap": route[3], "tversky_alpha": route[4], "tversky_beta": route[5]}
+    if len(route) == 7:                        # top-k: sums[0] is the cross-entropy itself
+        kw["topk"] = True
+    return kw
+
+
+def _inv_world(group) -> float:
+    """1 / (number of ranks whose sums are added): the share of a rank's top-k mean in the global cross-entropy."""
+    return 1.0 / dist.get_world_size(group) if comm_on(group) else 1.0
+
+
+def _topk_buffers(n_pix: int, device):
+    """(value map, select scratch) of the top-k cross-entropy: 4 bytes per pixel and tc_topk_work_bytes()."""
+    return (torch.empty(n_pix, dtype=torch.float32, device=device),
+            torch.empty((lib().tc_topk_work_bytes() + 7) // 8, dtype=torch.int64, device=device))
 
 
 class _SegLossFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, logits, labels, ncls, w_ce, w_dice, group, loss_scale=1.0, route=None):
         """route: None (the plain loss), or SegLoss._route's (weights tensor or None, ignore_index as the kernels take it) -- the
-        class-weighted / ignoring entries, NCHW through ld = 0 -- or its six-element form, for the tc_seg_loss_*_ft entries."""
+        class-weighted / ignoring entries, NCHW through ld = 0 -- or its six-element form, for the tc_seg_loss_*_ft entries, or its
+        seven-element form (the state tensor last) for the tc_seg_loss_*_topk entries and tc_topk_select."""
         L = lib()
         logits = logits.contiguous()
         B, C, H, W = logits.shape
@@ -274,9 +310,15 @@ class _SegLossFn(torch.autograd.Function):
         elif len(route) == 2:
             L.tc_seg_loss_fwd_w(logits.data_ptr(), 0, labels.data_ptr(), route[0].data_ptr(), route[1], prob.data_ptr(), sums.data_ptr(),
                                 B, ncls, H * W, _dt(logits), stream)
-        else:                                  # focal CE / Tversky overlap: (weights, ignore_index, gamma, overlap, alpha, beta)
+        elif len(route) == 6:                  # focal CE / Tversky overlap: (weights, ignore_index, gamma, overlap, alpha, beta)
             L.tc_seg_loss_fwd_ft(logits.data_ptr(), 0, labels.data_ptr(), route[0].data_ptr(), route[1], route[2], OVERLAPS[route[3]],
                                  prob.data_ptr(), sums.data_ptr(), B, ncls, H * W, _dt(logits), stream)
+        else:                                  # top-k CE: the value map, then this rank's select BEFORE the sums travel
+            values, work = _topk_buffers(B * H * W, logits.device)
+            L.tc_seg_loss_fwd_topk(logits.data_ptr(), 0, labels.data_ptr(), route[0].data_ptr(), route[1], route[2], OVERLAPS[route[3]],
+                                   prob.data_ptr(), sums.data_ptr(), values.data_ptr(), B, ncls, H * W, _dt(logits), stream)
+            L.tc_topk_select(values.data_ptr(), B * H * W, route[6].data_ptr(), sums.data_ptr(), _inv_world(group), work.data_ptr(), stream)
+            ctx.topk = (values, route[6].clone(), _inv_world(group))      # the state as this forward left it: a later forward overwrites it
         sums, n_pix, world = seg_sums_allreduce(sums, float(B * H * W), group)
         loss, ce, dice = loss_from_sums(sums, n_pix, w_ce, w_dice, None if route is None else route[0], **_overlap_of(route))
         ctx.save_for_backward(prob, labels, sums)
@@ -304,10 +346,16 @@ class _SegLossFn(torch.autograd.Function):
         elif len(ctx.route) == 2:
             L.tc_seg_loss_bwd_w(prob.data_ptr(), None, 0, labels.data_ptr(), ctx.route[0].data_ptr(), ctx.route[1], sums.data_ptr(),
                                 d.data_ptr(), 0, B, ncls, H * W, float(w_ce), float(w_dice), loss_scale, gl.data_ptr(), _dt(d), stream)
-        else:
+        elif len(ctx.route) == 6:
             w, ii, gamma, overlap, alpha, beta = ctx.route
             L.tc_seg_loss_bwd_ft(prob.data_ptr(), None, 0, labels.data_ptr(), w.data_ptr(), ii, sums.data_ptr(), d.data_ptr(), 0, B, ncls, H * W,
                                  float(w_ce), float(w_dice), gamma, OVERLAPS[overlap], alpha, beta, loss_scale, gl.data_ptr(), _dt(d), stream)
+        else:
+            w, ii, gamma, overlap, alpha, beta, _ = ctx.route
+            values, state, inv_world = ctx.topk
+            L.tc_seg_loss_bwd_topk(prob.data_ptr(), None, 0, labels.data_ptr(), w.data_ptr(), ii, sums.data_ptr(), d.data_ptr(), 0, B, ncls, H * W,
+                                   float(w_ce), float(w_dice), gamma, OVERLAPS[overlap], alpha, beta, loss_scale, gl.data_ptr(),
+                                   values.data_ptr(), state.data_ptr(), inv_world, _dt(d), stream)
         return d, None, None, None, None, None, None, None
 
 
@@ -334,11 +382,21 @@ class SegLoss(torch.nn.Module):
                 off class k and FN_k = sum (1 - p_k) on it.  alpha = beta = 0.5 is the LINEAR Dice 2 I / (P + Y), not the reference's squared
                 one, which overlap="dice" stays.
     The returned triple is then (loss, focal CE, overlap term).  These four are scalars, not device memory: a captured step (GraphedStep)
-    keeps the values it was captured with, and changing them needs a new GraphedStep."""
+    keeps the values it was captured with, and changing them needs a new GraphedStep.
+
+    ce_topk (None: off -- no launch, no allocation, the calls above; include/transception_topk.h has the definition and the gradient): a
+    fraction in (0, 1].  The CE is then the mean of the k = max(1, min(n, ceil(ce_topk n))) LARGEST per-pixel terms w[y_i] q_i^gamma nll_i
+    of the n counted pixels -- nnU-Net's TopK loss, online hard-example mining -- chosen on the device by an exact select; it combines with
+    every argument above.  Two things to know: the divisor is k whatever the class weights (ce_topk=1 with ce_weight is the mean of the
+    weighted terms, not torch's weighted mean), and pixels tied at the threshold share the places left there equally, so the gradient is a
+    function of the values (torch.topk picks among ties arbitrarily).  Across ranks each rank selects among its own pixels and the CE is
+    the mean of the ranks' top-k means.  The returned triple is (loss, top-k CE, overlap term).  The fraction lives in device memory
+    (topk_state(device)[0]): set_topk writes it in place and the next call -- a replay of a captured step included -- follows it."""
 
     def __init__(self, n_classes: int = 9, w_ce: float = 0.4, w_dice: float = 0.6, group=None,
                  loss_scale: Union[float, DynamicLossScale] = 1.0, ce_weight=None, dice_weight=None, ignore_index: Optional[int] = None,
-                 focal_gamma: float = 0.0, overlap: str = "dice", tversky_alpha: float = 0.5, tversky_beta: float = 0.5):
+                 focal_gamma: float = 0.0, overlap: str = "dice", tversky_alpha: float = 0.5, tversky_beta: float = 0.5,
+                 ce_topk: Optional[float] = None):
         """loss_scale: the gradient that leaves this loss is multiplied by it (the reported loss is not) -- loss scaling for float16
         storage; FusedSGD.step divides it out again (train_step wires the two together).  A float is a static scale; a
         DynamicLossScale is read from device memory by the backward kernel and adjusts itself after every update.
@@ -355,7 +413,9 @@ class SegLoss(torch.nn.Module):
             raise ValueError(f"the class-weighted loss kernels take at most 16 classes, got {n_classes}")
         if self.focal_tversky and n_classes > 16:
             raise ValueError(f"the focal / Tversky loss kernels take at most 16 classes, got {n_classes}")
+        self.ce_topk = check_ce_topk(ce_topk, n_classes)
         self._weights = {}                               # device -> fp32 [2 * n_classes]
+        self._topk_state = {}                            # device -> fp64 [8]: the fraction, then what tc_topk_select leaves
 
     @property
     def weighted(self) -> bool:
@@ -373,19 +433,51 @@ class SegLoss(torch.nn.Module):
 
     def weights(self, device) -> torch.Tensor:
         """The [2 * n_classes] weight tensor of `device` (CE weights, then Dice weights; ones where none were given)."""
-        d = torch.device(device)
-        if d.type == "cuda" and d.index is None:
-            d = torch.device("cuda", torch.cuda.current_device())
+        d = self._device(device)
         if d not in self._weights:
             self._weights[d] = self._host_weights().to(d)
         return self._weights[d]
 
+    def _device(self, device) -> torch.device:
+        d = torch.device(device)
+        if d.type == "cuda" and d.index is None:
+            d = torch.device("cuda", torch.cuda.current_device())
+        return d
+
+    def topk_state(self, device) -> torch.Tensor:
+        """The [8] float64 state of the top-k select on `device`: [0] the fraction (read on the device), [1..7] n, k, n_gt, n_eq, t, S, f as
+        the last select left them.  Created on first use and never replaced: captured launches hold its address."""
+        if self.ce_topk is None:
+            raise ValueError("this SegLoss was built with ce_topk=None")
+        d = self._device(device)
+        if d not in self._topk_state:
+            self._topk_state[d] = torch.tensor([self.ce_topk] + [0.0] * 7, dtype=torch.float64).to(d)
+        return self._topk_state[d]
+
+    def set_topk(self, frac: float) -> None:
+        """A new fraction, written IN PLACE into every device's state: the next call or replay selects with it (no new capture)."""
+        if self.ce_topk is None:
+            raise ValueError("this SegLoss was built with ce_topk=None: top-k cannot be switched on afterwards")
+        if frac is None:
+            raise ValueError("ce_topk cannot be switched off afterwards")
+        self.ce_topk = check_ce_topk(frac, self.n_classes)
+        for st in self._topk_state.values():
+            st[0:1].fill_(self.ce_topk)
+
+    def topk_stats(self, device) -> dict:
+        """What the last select on `device` found: {n, k, n_gt, n_eq, threshold, tie_share} (reads the state back: a host sync)."""
+        st = self.topk_state(device).cpu().tolist()
+        return {"n": int(st[1]), "k": int(st[2]), "n_gt": int(st[3]), "n_eq": int(st[4]), "threshold": st[5], "tie_share": st[7]}
+
     def _route(self, device):
         """None for the plain loss; else (weights tensor, ignore_index or the kernels' "off" value) for the tc_seg_loss_*_w entries; with
         a focal_gamma above 0 or overlap="tversky" that pair followed by (focal_gamma, overlap, tversky_alpha, tversky_beta), for the
-        tc_seg_loss_*_ft entries."""
-        if not self.weighted and not self.focal_tversky:
+        tc_seg_loss_*_ft entries; with ce_topk set those six followed by the state tensor, for the tc_seg_loss_*_topk entries."""
+        if not self.weighted and not self.focal_tversky and self.ce_topk is None:
             return None
+        if self.ce_topk is not None:
+            return (self.weights(device), IGNORE_NONE if self.ignore_index is None else self.ignore_index, self.focal_gamma, self.overlap,
+                    self.tversky_alpha, self.tversky_beta, self.topk_state(device))
         pair = self.weights(device), IGNORE_NONE if self.ignore_index is None else self.ignore_index
         if not self.focal_tversky:
             return pair
@@ -1036,7 +1128,8 @@ class GraphedStep:
     """A whole training step captured into hipGraphs and replayed: ~1800 kernel launches per step become graph launches,
     removing the host from the loop.  Inputs are copied into static buffers; the learning rate is a device scalar
     (FusedSGD.set_lr).  The loss's scalars -- w_ce, w_dice, focal_gamma, overlap, tversky_alpha, tversky_beta -- are kernel arguments
-    and keep the values of the capture: changing them needs a new GraphedStep (the class weights live in device memory and do not).
+    and keep the values of the capture: changing them needs a new GraphedStep (the class weights live in device memory and do not, and
+    neither does the top-k fraction: SegLoss.set_topk).
 
     world == 1: ONE graph = zero_grad + forward + loss + backward + SGD (through torch.autograd).
     world  > 1: no collective is ever captured.  Three graphs with the two RCCL all-reduces between them, driven through
@@ -1052,9 +1145,12 @@ class GraphedStep:
         loader-fed loop is then graph launch after graph launch, with no eager launch in between."""
         self.model, self.loss_fn, self.opt, self.group = model, loss_fn, opt, group
         self._pre = pre
+        self._topk = None                                # top-k CE: (value map, select scratch), allocated by the first _fwd
         self.x, self.y = images.clone(), labels.clone().long().contiguous()
         self._dtype = model.compute_dtype                # the captured launches hold pointers into this storage type's working copy
         _wire_loss_scale(loss_fn, opt, images.device)
+        if getattr(loss_fn, "ce_topk", None) is not None:
+            loss_fn.topk_state(images.device)            # exists before anything is captured
         self.distributed = comm_on(group)
         self.split = self.distributed or force_split
         side = torch.cuda.Stream()
@@ -1134,9 +1230,16 @@ class GraphedStep:
         elif len(route) == 2:
             L.tc_seg_loss_fwd_w(logits.data_ptr(), logits.stride(0), self.y.data_ptr(), route[0].data_ptr(), route[1], None,
                                 self._sums.data_ptr(), B, C, H * W, _dt(logits), stream)
-        else:                                  # focal CE / Tversky overlap: the scalars are baked into the captured launches
+        elif len(route) == 6:                  # focal CE / Tversky overlap: the scalars are baked into the captured launches
             L.tc_seg_loss_fwd_ft(logits.data_ptr(), logits.stride(0), self.y.data_ptr(), route[0].data_ptr(), route[1], route[2],
                                  OVERLAPS[route[3]], None, self._sums.data_ptr(), B, C, H * W, _dt(logits), stream)
+        else:                                  # top-k CE: value map and scratch held for the life of the step; this rank's select runs here,
+            if self._topk is None:             # BEFORE the sums travel, and leaves its share of the global CE in sums[0]
+                self._topk = _topk_buffers(B * H * W, logits.device)
+            L.tc_seg_loss_fwd_topk(logits.data_ptr(), logits.stride(0), self.y.data_ptr(), route[0].data_ptr(), route[1], route[2],
+                                   OVERLAPS[route[3]], None, self._sums.data_ptr(), self._topk[0].data_ptr(), B, C, H * W, _dt(logits), stream)
+            L.tc_topk_select(self._topk[0].data_ptr(), B * H * W, route[6].data_ptr(), self._sums.data_ptr(), _inv_world(self.group),
+                             self._topk[1].data_ptr(), stream)
         self._npix_local = float(B * H * W)
 
     def _reduce_sums(self):
@@ -1162,11 +1265,16 @@ class GraphedStep:
         elif len(route) == 2:                  # the CE denominator comes from the (all-reduced) sums: no pixel count is passed
             L.tc_seg_loss_bwd_w(None, lg.data_ptr(), lg.stride(0), self.y.data_ptr(), route[0].data_ptr(), route[1], self._sums.data_ptr(),
                                 d.data_ptr(), d.stride(0), B, C, H * W, float(lf.w_ce), float(lf.w_dice), gscale, gscale_dev, _dt(d), stream)
-        else:
+        elif len(route) == 6:
             w, ii, gamma, overlap, alpha, beta = route
             L.tc_seg_loss_bwd_ft(None, lg.data_ptr(), lg.stride(0), self.y.data_ptr(), w.data_ptr(), ii, self._sums.data_ptr(), d.data_ptr(),
                                  d.stride(0), B, C, H * W, float(lf.w_ce), float(lf.w_dice), gamma, OVERLAPS[overlap], alpha, beta, gscale,
                                  gscale_dev, _dt(d), stream)
+        else:
+            w, ii, gamma, overlap, alpha, beta, state = route
+            L.tc_seg_loss_bwd_topk(None, lg.data_ptr(), lg.stride(0), self.y.data_ptr(), w.data_ptr(), ii, self._sums.data_ptr(), d.data_ptr(),
+                                   d.stride(0), B, C, H * W, float(lf.w_ce), float(lf.w_dice), gamma, OVERLAPS[overlap], alpha, beta, gscale,
+                                   gscale_dev, self._topk[0].data_ptr(), state.data_ptr(), _inv_world(self.group), _dt(d), stream)
         M._backward(self._G, self._out_var, d, until="encoder_done")     # loss gradient, decoders, bridge
 
     def _bwd_leg(self, until: Optional[str]):

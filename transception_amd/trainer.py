@@ -30,7 +30,7 @@ import torch.distributed as dist
 from .data import DeviceLoader, SynapseSlices
 from .evaluate import (RESAMPLE_MODES, SURFACE_KEYS, TTA, VALID_OPTION, Calibration, PostProcess, SurfaceMetrics, calibration_from_stats,
                        calibration_line, inference, inference_calibration, inference_report)
-from .train import (DynamicLossScale, FusedAdamW, FusedSGD, GraphedStep, SegLoss, WeightEMA, check_class_weights, check_ema_decay,
+from .train import (DynamicLossScale, FusedAdamW, FusedSGD, GraphedStep, SegLoss, WeightEMA, check_ce_topk, check_class_weights, check_ema_decay,
                     check_focal_tversky, check_ignore_index, cosine_lr, train_step)
 
 OPTIMIZERS = ("sgd", "adamw", "adam")
@@ -106,6 +106,7 @@ class TrainConfig:
         if not VALID_OPTION["calibration"](self.calibration):
             raise ValueError(f"calibration must be None or an evaluate.Calibration, got {self.calibration!r}")
         check_focal_tversky(self.focal_gamma, self.overlap, self.tversky_alpha, self.tversky_beta)
+        check_ce_topk(self.ce_topk, self.num_classes)
         make_loss_scale(self.loss_scale)
         check_class_weights("class_weights", self.class_weights, self.num_classes, need_positive=True)
         check_ignore_index(self.ignore_index, self.num_classes)
@@ -123,12 +124,14 @@ class TrainConfig:
 #   calibration: an evaluate.Calibration -- the evaluation after a checkpoint then also runs `inference_calibration` on the rank's share of the
 #     volumes (one more prediction pass per volume), the decoded statistics are all-reduced as one float64 vector and `hist["calibration"]`
 #     collects the pool's ECE / MCE / NLL / Brier / accuracy with its reliability table; None: no key, no pass, no launch;
+#   ce_topk: None, or a fraction in (0, 1] -- the cross-entropy is then the mean of that fraction's largest per-pixel terms only (train.SegLoss,
+#     include/transception_topk.h) and the log line's loss_ce is that top-k CE; None: no launch, no allocation, the calls made today;
 #   focal_gamma, overlap, tversky_alpha, tversky_beta: the loss (train.SegLoss has the definition) -- the focal exponent of the
 #     cross-entropy, "dice" or "tversky" for the overlap term, and the Tversky weights of false positives and false negatives;
 #   resample: what the evaluation resamples to the label's size (evaluate.evaluate_volume: "labels", the reference's order-0 zoom of the
 #     argmax, or "scores", bilinear class scores and then the argmax).
 KEYWORD_OPTIONS = (("surface_metrics", Optional[SurfaceMetrics], None), ("calibration", Optional[Calibration], None),
-                   ("focal_gamma", float, 0.0), ("overlap", str, "dice"), ("tversky_alpha", float, 0.5), ("tversky_beta", float, 0.5),
+                   ("ce_topk", Optional[float], None), ("focal_gamma", float, 0.0), ("overlap", str, "dice"), ("tversky_alpha", float, 0.5), ("tversky_beta", float, 0.5),
                    ("resample", str, "labels"))
 
 
@@ -222,7 +225,7 @@ def trainer_synapse(cfg: TrainConfig, model, snapshot_path: str, volumes: Option
     scaler = loss_scale if isinstance(loss_scale, DynamicLossScale) else None
     loss_fn = SegLoss(cfg.num_classes, group=group, loss_scale=loss_scale, ce_weight=cfg.class_weights, dice_weight=cfg.class_weights,
                       ignore_index=cfg.ignore_index, focal_gamma=cfg.focal_gamma, overlap=cfg.overlap, tversky_alpha=cfg.tversky_alpha,
-                      tversky_beta=cfg.tversky_beta)
+                      tversky_beta=cfg.tversky_beta, **({} if cfg.ce_topk is None else {"ce_topk": cfg.ce_topk}))
     opt = make_optimizer(cfg, model)
     ema = None
     if cfg.ema_decay is not None:
